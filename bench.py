@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Throughput of the MI355X relevance engine on the reference's headline path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the roofline
+in it comes from the timed steps' own launch events and costs no run).  ``--full`` adds,
+after the timed region, what takes runs of its own: the builder leg, the rank-delta
+parity sample against the reference's fixture and the CPU baseline (``--builder-preds``
+and ``--no-cpu-baseline`` trim those); without it their fields are null.
+``--dump-outputs DIR`` writes what the last timed step returned as ``DIR/<name>.npy``.
 
 Metric (BASELINE.json): candidate explanations evaluated per second,
 including post-training, plus the rank-delta match rate.  A unit is one
@@ -332,6 +339,19 @@ def parity_sample(eng, wl, fixture, fallback):
     return pred, cands, ents, out
 
 
+def dump_outputs(path, relevances, details):
+    """``--dump-outputs``: what the last timed step's engine batch returned, as float64
+    ``.npy`` files (a few KB): ``relevances`` -- one per candidate, in order, what
+    ``compute_relevance_pipeline`` returns for the batch -- and of every post-training
+    behind them (``engine.last_results``) the target's rank and score, columns
+    (post-trained, base)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "relevances.npy"), np.asarray(relevances, np.float64).reshape(-1))
+    for key in ("target_rank", "target_score"):
+        arr = np.asarray([(pt[key], base[key]) for pt, base in details], np.float64).reshape(-1, 2)
+        np.save(os.path.join(path, key + "s.npy"), arr)
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -428,10 +448,15 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="complex-fb15k237-sufficient", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the builder leg, the parity sample against the "
+                         "reference's fixture and the CPU baseline (their fields are null without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (relevances, target ranks and scores) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--preds-per-step", type=int, default=None, help="override the workload's predictions per step")
     ap.add_argument("--builder-preds", type=int, default=4,
-                    help="predictions explained end to end by the builder leg after the timed region (0: none)")
+                    help="with --full: predictions explained end to end by the builder leg after the timed region (0: none)")
     args = ap.parse_args()
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -517,6 +542,12 @@ def main():
     elapsed = time.perf_counter() - t0
     log(f"[rank {rank}] timed region {elapsed * 1e3:.1f} ms, of which the pipeline call {t_call * 1e3:.1f} ms")
     recs = [[r, 0, 0, 0, 0] for o in outs for out in o for r in out]
+    if args.dump_outputs and rank == 0:
+        # the last timed step, before a later leg replaces the engine's last_results
+        det = eng.last_results if outs else []
+        if wl["mode"] == "sufficient":
+            det = [pb for rj in det for pb in rj]
+        dump_outputs(args.dump_outputs, [r for out in (outs[-1] if outs else []) for r in out], det)
     hot = [0.0, 0.0, 0]
     ivs = []
     for st in eng.last_batch_stats:
@@ -585,15 +616,15 @@ def main():
                       "time base); avg_launch_ms = mean launch duration")
 
     builder = None
-    if args.builder_preds > 0:
+    if args.full and args.builder_preds > 0:
         # the whole builder over the workload's first predictions (every rank, the slots of
         # each engine batch sharded as above), after the timed singleton region
         builder = builder_leg(model, ds, wl, args.builder_preds, kd.SlotSharding() if world > 1 else None)
         log(f"[rank {rank}] builder leg: {json.dumps(builder)}")
 
     cpu = None
-    parity = None
-    if rank == 0:
+    parity, fixture = {}, None
+    if args.full and rank == 0:
         # rank-delta match rate against the reference itself: the committed fixture's
         # prediction and candidates, run through the engine after the timed region
         fixture = load_fixture(args.workload)
@@ -635,7 +666,7 @@ def main():
                                           f"the rest), one all-gather per batch"},
                 "rank_delta_match_rate": (parity.get("fp32") or {}).get("match_rate"),
                 "rank_delta_max_abs_diff": (parity.get("fp32") or {}).get("max_abs_diff"),
-                "rank_delta_vs": "the reference (fp32, CPU) on the fixture "
+                "rank_delta_vs": None if not args.full else "the reference (fp32, CPU) on the fixture "
                                  + ((fixture or {}).get("_file") or "tests/golden/fullsize/<workload>.json (absent)"),
                 "rank_delta_match_rate_ref_fp64": (parity.get("fp64") or {}).get("match_rate"),
                 "rank_delta_max_abs_diff_ref_fp64": (parity.get("fp64") or {}).get("max_abs_diff"),

@@ -14,7 +14,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 RUNNER = os.path.join(HERE, "bench_standin.py")
-ARGS = ["--workload", "transe-fb15k237-necessary", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+ARGS = ["--workload", "transe-fb15k237-necessary", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
         "--builder-preds", "1"]
 
 
@@ -45,6 +45,27 @@ def test_bench_gpus2_launches_two_ranks_and_matches_one():
     # the builder leg (one prediction end to end) on two ranks equals the one-rank leg
     assert two["builder"]["relevances"] == one["builder"]["relevances"] > 0
     assert two["builder"]["evaluated"] == one["builder"]["evaluated"]
+
+
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """Without ``--full`` the legs after the timed region do not run (their fields are null),
+    and ``--dump-outputs`` writes the one timed step's results: the relevances hash to the
+    line's ``results_sha16``, with a (post-trained, base) rank and score behind each."""
+    import hashlib
+    import numpy as np
+    out = str(tmp_path / "dump")
+    line = _line(["--gpus", "1", "--workload", "transe-fb15k237-necessary", "--steps", "1", "--warmup", "0",
+                  "--preds-per-step", "1", "--dump-outputs", out])
+    assert line["steps"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    for k in ("builder", "cpu_baseline", "rank_delta_match_rate", "rank_delta_match_rate_ref_fp64"):
+        assert line[k] is None, k
+    assert sorted(os.listdir(out)) == ["relevances.npy", "target_ranks.npy", "target_scores.npy"]
+    rel, ranks, scores = (np.load(os.path.join(out, n + ".npy")) for n in ("relevances", "target_ranks", "target_scores"))
+    assert rel.dtype == ranks.dtype == scores.dtype == np.float64
+    assert len(rel) == line["config"]["candidates_per_step"] > 0
+    assert ranks.shape == scores.shape == (len(rel), 2)
+    assert hashlib.sha256(rel.tobytes()).hexdigest()[:16] == line["results_sha16"]
+    assert np.all(ranks >= 1) and np.all(ranks == np.round(ranks)) and np.all(np.isfinite(scores))
 
 
 def test_bench_world_size_mismatch_refused():

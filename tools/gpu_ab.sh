@@ -13,7 +13,7 @@ O=gpurun_out/$tag; mkdir -p $O
 for rep in $(seq 1 $reps); do
   for v in "${vals[@]}"; do
     f=$O/ab_${var}_${v}_$rep
-    env "$var=$v" timeout -k 10 600 python bench.py --workload "$wl" --steps "$steps" --warmup 1 --no-cpu-baseline \
+    env "$var=$v" timeout -k 10 600 python bench.py --workload "$wl" --steps "$steps" --warmup 1 --full --no-cpu-baseline \
       > $f.json 2> $f.err
     python -c "import json;d=json.load(open('$f.json'));print('$var=$v', round(d['value'],1), 'cand/s', round(d['ms_per_step'],1), 'ms/step', 'match', d.get('rank_delta_match_rate'), 'frac', d['roofline']['frac'])"
   done

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 ROOT=$(pwd)
 timeout -k 10 480 python -m pytest tests -m gpu -q -x > "$OUT/tests.log" 2>&1
 for w in $WLS; do
-  timeout -k 10 400 python bench.py --workload "$w" --steps 3 --warmup 1 > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
+  timeout -k 10 400 python bench.py --workload "$w" --steps 3 --warmup 1 --full > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
 done
 export TMPDIR=/tmp
 cd /tmp

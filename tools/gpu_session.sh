@@ -81,11 +81,11 @@ run_step() {
     bench)
       local w=${a[1]} st=${a[2]:-3} wu=${a[3]:-1} envs=() tagx=""
       if [ -n "${a[4]}" ]; then IFS=',' read -r -a envs <<< "${a[4]}"; tagx="_$(echo ${a[4]} | tr ',=/' '___')"; fi
-      env "${envs[@]}" timeout -k 10 600 python bench.py --workload $w --steps $st --warmup $wu --no-cpu-baseline --builder-preds 0 \
+      env "${envs[@]}" timeout -k 10 600 python bench.py --workload $w --steps $st --warmup $wu --full --no-cpu-baseline --builder-preds 0 \
         > $O/bench_$w$tagx.json 2> $O/bench_$w$tagx.err || { tail -5 $O/bench_$w$tagx.err; return 1; }
       python3 -c "import json,sys;d=json.load(open(sys.argv[1]));print(sys.argv[2], round(d['value'],1), 'cand/s', round(d['ms_per_step'],2), 'ms', 'frac', d['roofline']['frac'], 'fp64', d.get('rank_delta_match_rate_ref_fp64'))" $O/bench_$w$tagx.json "$w$tagx" ;;
     benchcpu)
-      timeout -k 10 500 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || return 1
+      timeout -k 10 500 python bench.py --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err || return 1
       cut -c1-400 $O/bench_default.json ;;
     builderab)
       # builderab:<VAR>:<v1,v2,..>[:reps[:preds]]: the default line's builder leg, alternating env values
@@ -93,7 +93,7 @@ run_step() {
       IFS=',' read -r -a vals <<< "${a[2]}"
       for rep in $(seq 1 $reps); do
         for v in "${vals[@]}"; do
-          env "$var=$v" timeout -k 10 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --builder-preds $np \
+          env "$var=$v" timeout -k 10 400 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --builder-preds $np \
             > $O/builderab_${var}_${v}_$rep.json 2> $O/builderab_${var}_${v}_$rep.err || { tail -5 $O/builderab_${var}_${v}_$rep.err; return 1; }
           python3 -c "import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]);b=d['builder'];print(sys.argv[2], round(b['value'],1), 'rel/s', b['relevances'], 'rel', b['evaluated'], 'eval', b['engine_batches'], 'batches', b.get('time_split_s'), {k: v['#relevances_equal'] and v['top10_rules_equal'] for k, v in b.get('reference_match_first_prediction', {}).items() if k != 'fixture'})" $O/builderab_${var}_${v}_$rep.json "$var=$v"
         done
@@ -103,7 +103,7 @@ run_step() {
       local np=${a[1]:-4}
       export TMPDIR=/tmp
       (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace -d $R/$O/bprof -o run -- \
-        python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --builder-preds $np > $R/$O/bprof.json 2> $R/$O/bprof.err) || return 1
+        python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --builder-preds $np > $R/$O/bprof.json 2> $R/$O/bprof.err) || return 1
       local win=$(python3 -c "import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]);print(d['builder']['execution_time_s'])" $O/bprof.json)
       python3 tools/timeline.py $O/bprof/run_results.db --window $win --skip-end 0 --gaps > $O/builder_timeline.txt 2>&1
       rm -rf $O/bprof
@@ -149,7 +149,7 @@ run_step() {
         for v in "${vals[@]}"; do
           local lib=$R/kelpie_amd/libkelpie_hip.so
           [ $v != base ] && lib=$R/variants/lib_$v.so
-          KELPIE_HIP_LIB=$lib timeout -k 10 600 python bench.py --workload $w --steps $st --warmup 1 --no-cpu-baseline --builder-preds 0 \
+          KELPIE_HIP_LIB=$lib timeout -k 10 600 python bench.py --workload $w --steps $st --warmup 1 --full --no-cpu-baseline --builder-preds 0 \
             > $O/libab_${w}_${v}_$rep.json 2> $O/libab_${w}_${v}_$rep.err || { tail -5 $O/libab_${w}_${v}_$rep.err; return 1; }
           python3 -c "import json,sys;d=json.load(open(sys.argv[1]));print(sys.argv[2], round(d['value'],1), 'cand/s', round(d['ms_per_step'],2), 'ms', 'frac', d['roofline']['frac'], 'fp64', d.get('rank_delta_match_rate_ref_fp64'))" $O/libab_${w}_${v}_$rep.json "$w $v"
         done
