@@ -11,7 +11,7 @@ LIB := kelpie_amd/libkelpie_hip.so
 
 all: $(LIB)
 
-build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp include/kelpie_hip.h
+build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp include/kelpie_hip.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -62,4 +62,11 @@ build/san/host_tsan: $(SAN_SRC) include/kelpie_hip.h
 	@mkdir -p build/san
 	$(CXX) $(SAN_FLAGS) -fsanitize=thread $(SAN_SRC) -o $@
 
-.PHONY: asan tsan
+# the post-training batch check (kp_batch_check.hpp, no HIP) alone in
+# tests/native/batch_check_driver.cpp; run by tests/test_batch_check.py (CPU suite)
+batch_asan: build/san/batch_check_asan
+build/san/batch_check_asan: tests/native/batch_check_driver.cpp kelpie_amd/csrc/kp_batch_check.hpp include/kelpie_hip.h
+	@mkdir -p build/san
+	$(CXX) -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
+
+.PHONY: asan tsan batch_asan

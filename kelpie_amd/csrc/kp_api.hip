@@ -145,7 +145,7 @@ int kp_ctx_create(int device, const kp_model_desc* m, kp_ctx** out) {
     // returning it to the driver; the device's default pool (torch, RCCL) is left alone
     {
       hipMemPool_t pool = device_pool(device);
-      for (DevBuf* d : c->bound_buffers()) {
+      for (DevBuf* d : c->buffers()) {
         d->s = c->stream;
         d->pool = pool;
       }
@@ -179,17 +179,9 @@ int kp_ctx_destroy(kp_ctx* c) {
   if (!c) return KP_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (float* p : {c->dE, c->dR, c->dEt, c->d_conv_w, c->d_conv_b, c->d_fc_w, c->d_fc_b, c->d_bn_a, c->d_bn_b})
+  for (float* p : {c->dE, c->dR, c->d_conv_w, c->d_conv_b, c->d_fc_w, c->d_fc_wt, c->d_fc_b, c->d_bn_a, c->d_bn_b})
     if (p) (void)hipFree(p);
-  for (auto& b : c->ws) b.release();
-  c->e3.release();
-  c->e3ts.release();
-  c->e3pre.release();
-  c->eT.release();
-  c->cvf_fw3.release();
-  c->cvf_bw3.release();
-  for (DevBuf* b : {&c->cv_wtm, &c->cv_trel, &c->cv_wtl, &c->cv_wfm, &c->cv_wlc}) b->release();
-  for (auto& b : c->cvs) b.release();
+  for (DevBuf* b : c->buffers()) b->release();
   if (c->stream) (void)hipStreamSynchronize(c->stream);  // the stream-ordered frees above
   train_state_free(c);
   cv_train_free(c);

@@ -3,11 +3,14 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <mutex>
 #include <algorithm>
+#include <array>
+#include <cstdint>
 #include <cstring>
+#include <mutex>
 #include <string>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/kelpie_hip.h"
@@ -81,6 +84,110 @@ struct DevBuf {
   }
 };
 
+// ----------------------------------------------------------------------------
+// the context's device buffers, by name.  Each struct below holds DevBufs only and lists
+// every one of them in all(); kp_ctx::buffers() joins the lists, and kp_ctx_create (stream
+// and pool binding) and kp_ctx_destroy (release) walk nothing else.  KP_WS_COMPLETE fails
+// the build when a member is added to a struct but not to its list, so no buffer can be
+// left unbound (an unbound buffer grows with hipMalloc / hipFree, which synchronise the
+// whole device).  A context belongs to one model family; the other families' buffers stay
+// empty.
+// ----------------------------------------------------------------------------
+#define KP_WS_COMPLETE(S)                                                                          \
+  static_assert(sizeof(S) == sizeof(DevBuf) * std::tuple_size<decltype(std::declval<S&>().all())>::value, \
+                #S "::all() must list every DevBuf member")
+
+// images of the frozen tables and layers, built on first use and kept (their *_ready flags
+// are in kp_ctx)
+struct ImageBufs {
+  DevBuf e3;                // kp_attn3's split image of dE
+  DevBuf e3ts, e3pre;       // kp_attn3's fp64 tile sums / prefix sums of dE over tiles
+  DevBuf eT;                // dE transposed [dp][round_up(n_ent, 256)] fp32 (fp64 rank scoring)
+  DevBuf cvf_fw3, cvf_bw3;  // kp_cv_fused.hpp's permuted split images of the ConvE FC weight
+  DevBuf cv_wtm, cv_trel;   // shared-encoder split: map-row-18-19 FC columns, the relations' FC terms
+  DevBuf cv_wtl, cv_wfm;    // the kelpie rows' FC columns and the mid columns, transposed
+  DevBuf cv_wlc;            // the kelpie rows' FC columns [dim][4608]
+  auto all() {
+    return std::array{&e3, &e3ts, &e3pre, &eT, &cvf_fw3, &cvf_bw3, &cv_wtm, &cv_trel, &cv_wtl, &cv_wfm, &cv_wlc};
+  }
+};
+KP_WS_COMPLETE(ImageBufs);
+
+// the rank of the post-trained rows (every *_posttrain_rank; kp_posttrain.hpp fills it).
+// Two borrowers outside a post-training call, kept so that a context allocates what it
+// always did: complex_all_scores uploads its heads / relations into pred / po, and
+// transe_all_scores writes its score matrix into scores.
+struct RankWs {
+  DevBuf pred;            // [ns][3] the ranked triples (ComplEx, TransE: their fp64 query kernels)
+  DevBuf po;              // [ns] their objects
+  DevBuf filt_off, filt;  // the filter CSR
+  DevBuf target, rank;    // [ns] results
+  DevBuf q64, t64;        // fp64 ranking queries [ns][dp]; target | kelpie column scores [2][ns]
+  DevBuf scores;          // fp32 score matrix [ns][ld] (KP_TE_RANK / KP_CV_RANK = f32)
+  DevBuf bits;            // launch_rank_f64's filter bitmap (kp_rank.hip owns it)
+  auto all() { return std::array{&pred, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &scores, &bits}; }
+};
+KP_WS_COMPLETE(RankWs);
+
+// kp_complex.hip
+struct ComplexWs {
+  DevBuf x, s1, s2;                // kelpie rows [ns][dp] and their Adagrad / Adam moments
+  DevBuf plans, queries, targets;  // CxPlan, CxQuery, the queries' frozen targets
+  DevBuf pairs, acts;              // frozen-head (h, r) pairs; per-step active slots
+  DevBuf stepq, stept;             // per-step query / tail items
+  DevBuf contrib;                  // per-step gradient contributions [items][dp]
+  DevBuf tsum, qpair, lsef;        // target sums [queries][dp]; pair queries [pairs][dp], their frozen lse
+  DevBuf am, al, ao;               // attention split results (max, sum, output)
+  DevBuf qs;                       // the step's queries [nq][dp]
+  DevBuf score_q, score_out;       // complex_scores_dev's queries, complex_all_scores' scores
+  auto all() {
+    return std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
+                      &tsum, &qpair, &lsef, &am, &al, &ao, &qs, &score_q, &score_out};
+  }
+};
+KP_WS_COMPLETE(ComplexWs);
+
+// kp_transe.hip
+struct TranseWs {
+  DevBuf x;                 // kelpie rows [ns][dp]
+  DevBuf slots, rows, rng;  // TeSlot, the batch's training rows and draws
+  DevBuf order;             // slots, longest first
+  DevBuf heads, rels;       // score queries: the ranked triples' (-1, relation), and transe_all_scores' pairs
+  auto all() { return std::array{&x, &slots, &rows, &rng, &order, &heads, &rels}; }
+};
+KP_WS_COMPLETE(TranseWs);
+
+// kp_conve.hip
+struct ConveWs {
+  DevBuf x, s1, s2;               // kelpie rows [ns][dp] and their Adam moments
+  DevBuf kinst, finst, acts;      // CvInst, CvFInst, CvAct
+  DevBuf tails;                   // the kelpie pairs' distinct tails
+  DevBuf keep_bits;               // the dropout keep bits plus a zero guard word
+  DevBuf fcf, fpairs;             // frozen-head pairs: FC rows [pairs][dim] and their (h, r)
+  DevBuf flat;                    // flattened feature maps [rows][hidden]: the frozen pairs', then the
+                                  // step's (unfused path), then encode_eval's
+  DevBuf slab;                    // FC split-K slabs [KS][rows][dim]; encode_eval's FC output
+  DevBuf relu, g3;                // fused path: ReLU bytes; kp_cv_dx's split gradient
+  DevBuf sr_src, sr_rng, psr;     // shared-encoder split: kelpie rows' sources, pair ranges, pair -> row
+  DevBuf relu_s, slab_l;          // its kelpie rows' ReLU bytes and FC slabs [KSL][rows][dim]
+  DevBuf mid, map_l, map_m;       // pairs' mid FC terms; kelpie rows' / pairs' map rows (then gradients)
+  DevBuf gs, dls;                 // kelpie rows' summed pair dfc; their lhs image gradient
+  DevBuf q;                       // encoder output: the step's rows in the loop (dQ), the ranked
+                                  // triples' rows after it (dQr)
+  DevBuf enc_src, enc_bits;       // per-step encoder rows: sources and keep-bit offsets
+  DevBuf fchunks, fpart;          // frozen-head pairs' chunks per step and their partial gradients
+  DevBuf gscale;                  // 1 / (b (n_ent + 1)) per kelpie instance
+  DevBuf o;                       // attention output [rows * splits][dp]
+  DevBuf dfc, gk, dflat, dl;      // backward: dL/dfc, g . x, dL/dflat (unfused), lhs image gradient
+  DevBuf rank_src;                // the ranked triples' encoder sources
+  auto all() {
+    return std::array{&x, &s1, &s2, &kinst, &finst, &acts, &tails, &keep_bits, &fcf, &fpairs, &flat, &slab,
+                      &relu, &g3, &sr_src, &sr_rng, &psr, &relu_s, &slab_l, &mid, &map_l, &map_m, &gs, &dls,
+                      &q, &enc_src, &enc_bits, &fchunks, &fpart, &gscale, &o, &dfc, &gk, &dflat, &dl, &rank_src};
+  }
+};
+KP_WS_COMPLETE(ConveWs);
+
 struct Timing {
   double device_s = 0.0;  // whole call on the device (first upload .. last kernel)
   double loop_s = 0.0;    // post-training loop
@@ -92,7 +199,7 @@ struct Timing {
 struct kp_train_state;  // kp_train.hip: optimizer state of a full-model training run
 struct kp_cv_train;     // kp_train_conve.hip: ConvE full-model training state
 
-struct kp_ctx {
+struct kp_ctx : ImageBufs {
   int device = 0;
   int n_cu = 256;  // compute units of the device (one attention workgroup per CU)
   hipStream_t stream = nullptr;
@@ -102,53 +209,54 @@ struct kp_ctx {
   int hidden = 0;                              // ConvE
   float* dE = nullptr;                         // [n_ent][dp] zero-padded
   float* dR = nullptr;                         // [n_rel2][dp]
-  float* dEt = nullptr;                        // TransE: ||E_e||^2 etc (unused for others)
   // ConvE frozen layers
   float* d_conv_w = nullptr;
   float* d_conv_b = nullptr;
   float* d_fc_w = nullptr;   // [dim][hidden]
+  float* d_fc_wt = nullptr;  // [hidden][dim], the unfused backward GEMM's operand (conve_fc_wt, on first use)
   float* d_fc_b = nullptr;
   float* d_bn_a = nullptr;
   float* d_bn_b = nullptr;
   std::vector<float> hE;     // host copy (ConvE/TransE helpers)
-  DevBuf ws[32];             // workspace slots (see each model file)
+  // per-batch workspaces (the once-built images are the ImageBufs base)
+  RankWs rank;
+  ComplexWs cx;
+  TranseWs te;
+  ConveWs cv;
   std::string err;
   Timing timing;
   bool time_hot = true;
   // attention contraction: 0 = fp32 MFMA (kp_attn.hpp), 1 = bf16x3 MFMA (kp_attn3.hpp)
   int attn_mode = 0;
   int attn_part = 0;  // kp_attn3 partition: 0 chosen per launch, 1 stream-K, 2 XCD-grouped ranges (KP_ATTN_PART)
-  DevBuf e3;               // kp_attn3's split image of dE, built on first use
-  bool e3_ready = false;
-  DevBuf e3ts, e3pre;      // kp_attn3's fp64 tile sums / prefix sums of dE over tiles
-  bool e3pre_ready = false;
-  DevBuf eT;               // dE transposed [dp][round_up(n_ent, 256)] fp32 (fp64 rank scoring), on first use
+  bool e3_ready = false;     // ImageBufs::e3
+  bool e3pre_ready = false;  // e3ts, e3pre
   bool eT_ready = false;
   int cv_fused = 1;        // ConvE d = 200: fused encoder kernels (kp_cv_fused.hpp), KP_CV_FUSED
   int cv_rank64 = 1;       // ConvE post-training rank on fp64 logits (KP_CV_RANK=f32: fp32 sigmoid scores)
   int cv_dx_block = 0;     // ConvE: the 256-thread kp_cv_dx instead of kp_cv_dx1 (KP_CV_DX=block, A/B)
   int te_norm = 2;         // TransE score norm p (kp_model_desc.norm_p): 2 or 1
   int te_rank64 = 1;       // TransE post-training rank on fp64 squared distances (KP_TE_RANK=f32: fp32 norms)
-  DevBuf cvf_fw3, cvf_bw3;  // their permuted split images of the FC weight (built once)
-  bool cvf_ready = false;
+  bool cvf_ready = false;   // cvf_fw3, cvf_bw3
   int cv_shared = 1;        // ConvE fused path: the shared-encoder split (kp_cv_fused.hpp), KP_CV_SHARED
-  DevBuf cv_wtm, cv_trel;   // its map-row-18-19 FC columns and the relations' FC terms (built once)
-  DevBuf cv_wtl, cv_wfm;    // the kelpie rows' FC columns and the mid columns, transposed (built once)
-  DevBuf cv_wlc;            // the kelpie rows' FC columns [dim][4608] (built once)
-  bool cv_shared_ready = false;
-  DevBuf cvs[14];           // per-batch ConvE workspaces (kp_conve.hip)
+  bool cv_shared_ready = false;  // cv_wtm, cv_trel, cv_wtl, cv_wfm, cv_wlc
   int attn3_wpc[2] = {0, 0};  // co-resident kp_attn3 workgroups per CU, [softmax, BCE] (occupancy API)
   kp_train_state* train = nullptr;  // kp_train_epoch's state (freed with the context)
   kp_cv_train* cvtrain = nullptr;   // kp_conve_train_*'s state (freed with the context)
   std::vector<hipEvent_t> evpool;
   std::vector<std::pair<double, double>> hot_pairs;  // (work units, seconds) per hot launch
   std::vector<double> hot_iv;  // [start, end] per hot launch, seconds since the device's time base
-  // the workspaces that live on the context's stream (DevBuf::s)
-  std::vector<DevBuf*> bound_buffers() {
-    std::vector<DevBuf*> v = {&e3, &e3ts, &e3pre, &eT, &cvf_fw3, &cvf_bw3,
-                              &cv_wtm, &cv_trel, &cv_wtl, &cv_wfm, &cv_wlc};
-    for (auto& b : ws) v.push_back(&b);
-    for (auto& b : cvs) v.push_back(&b);
+  // every DevBuf of the context: all of them live on its stream (DevBuf::s).  kp_ctx holds
+  // no DevBuf of its own; a new one goes into one of the structs above, whose all() then
+  // has to name it
+  std::vector<DevBuf*> buffers() {
+    std::vector<DevBuf*> v;
+    auto add = [&v](auto list) { v.insert(v.end(), list.begin(), list.end()); };
+    add(ImageBufs::all());
+    add(rank.all());
+    add(cx.all());
+    add(te.all());
+    add(cv.all());
     return v;
   }
   hipEvent_t event(size_t i) {

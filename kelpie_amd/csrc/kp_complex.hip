@@ -24,7 +24,6 @@
 //   the batch, so every epoch reuses one plan; otherwise each (epoch, step)
 //   gets its own plan from the permutation.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -32,6 +31,7 @@
 
 #include "kp_attn.hpp"
 #include "kp_attn3.hpp"
+#include "kp_posttrain.hpp"
 
 namespace {
 using namespace kpattn;
@@ -518,13 +518,8 @@ int cx_pick_db(int dim) {
   return -1;
 }
 
-// KP_HOST_TIMES=1 (diagnostic): per call, on stderr, the host time before the first upload
-// (checks and planning), up to the last launch enqueued, and waiting for the device
-static const bool g_host_times = std::getenv("KP_HOST_TIMES") != nullptr;
-static double host_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
+// KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time before the first upload (checks
+// and planning), up to the last launch enqueued, and waiting for the device
 void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   const double t_in = g_host_times ? host_ms() : 0.0;
   const int DBV = c->dp / 16;
@@ -533,22 +528,9 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   const int hpbs = hp->batch_size;
   KP_REQUIRE(hpbs > 0 && hp->epochs >= 0, "ComplEx: bad batch_size/epochs");
   const int E = hp->epochs;
-  // every id is checked before it indexes a host vector or a device table (as ConvE / TransE)
-  KP_REQUIRE(ns >= 0 && bt->row_off[0] == 0, "ComplEx: bad row_off");
-  for (int s = 0; s < ns; ++s) {
-    KP_REQUIRE(bt->row_off[s + 1] >= bt->row_off[s], "ComplEx: bad row_off");
-    KP_REQUIRE(bt->pred[3 * s] == K, "ComplEx: the ranked triple must start at the kelpie entity");
-    KP_REQUIRE(bt->pred[3 * s + 1] >= 0 && bt->pred[3 * s + 1] < c->n_rel2, "ComplEx: ranked relation out of range");
-    KP_REQUIRE(bt->pred[3 * s + 2] >= 0 && bt->pred[3 * s + 2] <= K, "ComplEx: ranked object out of range");
-    KP_REQUIRE(bt->filt_off[s + 1] >= bt->filt_off[s], "ComplEx: bad filt_off");
-  }
-  for (int64_t i = 0; i < (int64_t)bt->row_off[ns]; ++i) {
-    const int32_t* rw = bt->rows + 3 * i;
-    KP_REQUIRE(rw[0] >= 0 && rw[0] <= K && rw[2] >= 0 && rw[2] <= K && rw[1] >= 0 && rw[1] < c->n_rel2,
-               "ComplEx: row id out of range");
-  }
-  for (int64_t i = 0; i < (int64_t)bt->filt_off[ns]; ++i)
-    KP_REQUIRE(bt->filt[i] >= 0 && bt->filt[i] <= K, "ComplEx: filter id out of range");
+  // every id is checked before it indexes a host vector or a device table, as in every
+  // model family (kp_batch_check.hpp)
+  require_batch(c, bt, "ComplEx");
 
   std::vector<CxPlan> plans;
   std::vector<CxQuery> pqs;
@@ -636,7 +618,6 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   for (int s = 0; s < ns; ++s) {
     const int r0 = bt->row_off[s], r1 = bt->row_off[s + 1];
     const int R = r1 - r0;
-    KP_REQUIRE(R >= 0, "ComplEx: bad row_off");
     const int32_t* rows = bt->rows + 3 * (size_t)r0;
     plan_base[s] = (int)plans.size();
     if (R == 0 || E == 0) {
@@ -696,44 +677,31 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   const int DP = c->dp;
   const double t_plan = g_host_times ? host_ms() : 0.0;
   // ---- uploads
-  float* dX = nullptr;
-  {
-    std::vector<float> xp((size_t)ns * DP, 0.f);
-    for (int s = 0; s < ns; ++s)
-      std::memcpy(&xp[(size_t)s * DP], bt->x0 + (size_t)s * c->dim, sizeof(float) * c->dim);
-    dX = upload(c, c->ws[0], xp.data(), xp.size());
-  }
-  float* dS1 = reinterpret_cast<float*>(c->ws[1].ensure(sizeof(float) * (size_t)ns * DP));
-  float* dS2 = reinterpret_cast<float*>(c->ws[2].ensure(sizeof(float) * (size_t)ns * DP));
+  std::vector<float> xp;
+  float* dX = upload_x0(c, c->cx.x, bt, xp);
+  float* dS1 = reinterpret_cast<float*>(c->cx.s1.ensure(sizeof(float) * (size_t)ns * DP));
+  float* dS2 = reinterpret_cast<float*>(c->cx.s2.ensure(sizeof(float) * (size_t)ns * DP));
   KP_HIP(hipMemsetAsync(dS1, 0, sizeof(float) * (size_t)ns * DP, c->stream));
   KP_HIP(hipMemsetAsync(dS2, 0, sizeof(float) * (size_t)ns * DP, c->stream));
-  CxPlan* dPlans = upload(c, c->ws[3], plans.data(), plans.size());
-  CxQuery* dPq = upload(c, c->ws[4], pqs.data(), pqs.size());
-  int32_t* dTg = upload(c, c->ws[6], targets.data(), targets.size());
-  int2* dPairs = upload(c, c->ws[7], pairs.data(), pairs.size());
-  int4* dActs = upload(c, c->ws[8], acts.data(), acts.size());
-  int4* dStepQ = upload(c, c->ws[9], stepq.data(), std::max<size_t>(1, stepq.size()));
-  DevBuf& bStepT = c->ws[24];
-  int4* dStepT = upload(c, bStepT, stept.data(), std::max<size_t>(1, stept.size()));
-  float* dContrib = reinterpret_cast<float*>(c->ws[25].ensure(sizeof(float) * (size_t)std::max(1, max_items) * DP));
+  CxPlan* dPlans = upload(c, c->cx.plans, plans.data(), plans.size());
+  CxQuery* dPq = upload(c, c->cx.queries, pqs.data(), pqs.size());
+  int32_t* dTg = upload(c, c->cx.targets, targets.data(), targets.size());
+  int2* dPairs = upload(c, c->cx.pairs, pairs.data(), pairs.size());
+  int4* dActs = upload(c, c->cx.acts, acts.data(), acts.size());
+  int4* dStepQ = upload(c, c->cx.stepq, stepq.data(), std::max<size_t>(1, stepq.size()));
+  int4* dStepT = upload(c, c->cx.stept, stept.data(), std::max<size_t>(1, stept.size()));
+  float* dContrib = reinterpret_cast<float*>(c->cx.contrib.ensure(sizeof(float) * (size_t)std::max(1, max_items) * DP));
   const int npq = (int)pqs.size(), npairs = (int)pairs.size();
-  float* dTsum = reinterpret_cast<float*>(c->ws[10].ensure(sizeof(float) * (size_t)std::max(npq, 1) * DP));
-  float* dQpair = reinterpret_cast<float*>(c->ws[11].ensure(sizeof(float) * (size_t)std::max(npairs, 1) * DP));
-  float* dLsef = reinterpret_cast<float*>(c->ws[12].ensure(sizeof(float) * (size_t)std::max(npairs, 1)));
+  float* dTsum = reinterpret_cast<float*>(c->cx.tsum.ensure(sizeof(float) * (size_t)std::max(npq, 1) * DP));
+  float* dQpair = reinterpret_cast<float*>(c->cx.qpair.ensure(sizeof(float) * (size_t)std::max(npairs, 1) * DP));
+  float* dLsef = reinterpret_cast<float*>(c->cx.lsef.ensure(sizeof(float) * (size_t)std::max(npairs, 1)));
 
   // the ranking's inputs and buffers now, ahead of the step loop: an upload from pageable
   // memory after the loop waited for the whole loop on the device, so the rank kernels
   // were enqueued only then (a host round trip per batch with the context idle)
-  double* dQ64 = reinterpret_cast<double*>(c->ws[29].ensure(sizeof(double) * (size_t)ns * DP));
-  double* dT64 = reinterpret_cast<double*>(c->ws[30].ensure(sizeof(double) * 2 * (size_t)ns));
-  int32_t* dPred = upload(c, c->ws[18], bt->pred, (size_t)ns * 3);
-  std::vector<int32_t> po(ns);
-  for (int s = 0; s < ns; ++s) po[s] = bt->pred[3 * s + 2];
-  int32_t* dPo = upload(c, c->ws[19], po.data(), po.size());
-  int32_t* dFo = upload(c, c->ws[20], bt->filt_off, (size_t)ns + 1);
-  int32_t* dF = upload(c, c->ws[21], bt->filt, (size_t)bt->filt_off[ns]);
-  float* dTarget = reinterpret_cast<float*>(c->ws[22].ensure(sizeof(float) * (size_t)ns));
-  int64_t* dRank = reinterpret_cast<int64_t*>(c->ws[23].ensure(sizeof(int64_t) * (size_t)ns));
+  const Rank64Dev r64 = rank64_buffers(c, ns);
+  int32_t* dPred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
+  const RankDev rk = upload_rank_inputs(c, bt);
 
   const int half = c->dim / 2;
   KP_HIP(hipEventRecord(c->ev0, c->stream));
@@ -753,10 +721,10 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
     step_plan[t] = attn_plan_ctx(c, std::max(nq, 1), c->n_ent, slots_attn);
     att_rows = std::max(att_rows, (size_t)nq * step_plan[t].wk.n_parts);
   }
-  float* dAm = reinterpret_cast<float*>(c->ws[13].ensure(sizeof(float) * att_rows));
-  float* dAl = reinterpret_cast<float*>(c->ws[14].ensure(sizeof(float) * att_rows));
-  float* dAO = reinterpret_cast<float*>(c->ws[15].ensure(sizeof(float) * att_rows * DP));
-  float* dQs = reinterpret_cast<float*>(c->ws[26].ensure(sizeof(float) * (size_t)std::max(max_nq, 1) * DP));
+  float* dAm = reinterpret_cast<float*>(c->cx.am.ensure(sizeof(float) * att_rows));
+  float* dAl = reinterpret_cast<float*>(c->cx.al.ensure(sizeof(float) * att_rows));
+  float* dAO = reinterpret_cast<float*>(c->cx.ao.ensure(sizeof(float) * att_rows * DP));
+  float* dQs = reinterpret_cast<float*>(c->cx.qs.ensure(sizeof(float) * (size_t)std::max(max_nq, 1) * DP));
   if (npairs > 0) {
     hipLaunchKernelGGL(kp_cx_qpair, dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP, half, dPairs, npairs,
                        dQpair);
@@ -833,51 +801,25 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
 
   // ---- ranking: scores of (kelpie, p, .) over E plus the kelpie column, in fp64
   // (launch_rank_f64: at the reference init the target's neighbours are ~1e-5 relative away)
-  CX_DISPATCH(DBV, launch_rankq64<DB>(c, dX, dPred, ns, dQ64, dT64, dT64 + ns));
-  launch_rank_f64(c, ns, dQ64, dT64, dT64 + ns, dPo, dFo, dF, dTarget, dRank);
+  CX_DISPATCH(DBV, launch_rankq64<DB>(c, dX, dPred, ns, r64.q, r64.t, r64.kcol));
+  launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
 
-  if (bt->out_x) {
-    std::vector<float> xp((size_t)ns * DP);
-    KP_HIP(hipMemcpyAsync(xp.data(), dX, sizeof(float) * xp.size(), hipMemcpyDeviceToHost, c->stream));
-    KP_HIP(hipStreamSynchronize(c->stream));
-    for (int s = 0; s < ns; ++s)
-      std::memcpy(bt->out_x + (size_t)s * c->dim, &xp[(size_t)s * DP], sizeof(float) * c->dim);
-  }
-  KP_HIP(hipMemcpyAsync(bt->out_score, dTarget, sizeof(float) * ns, hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(bt->out_rank, dRank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
-  const double t_enq = g_host_times ? host_ms() : 0.0;
-  KP_HIP(hipStreamSynchronize(c->stream));
+  const double t_enq = download_results(c, bt, dX, rk, xp);
+  const double t_done = g_host_times ? host_ms() : 0.0;
   if (g_host_times)
     std::fprintf(stderr,
                  "[kp_cx] slots %d steps %d: plan %.2f ms, enqueue %.2f ms (uploads+pairs %.2f, step 0 %.2f, step 1 "
                  "%.2f, to T/2 %.2f, to T-1 %.2f), wait %.2f ms\n",
                  ns, T, t_plan - t_in, t_enq - t_plan, t_loop0 - t_plan, t_steps[0] - t_loop0, t_steps[1] - t_steps[0],
-                 t_steps[2] - t_steps[1], t_steps[3] - t_steps[2], host_ms() - t_enq);
-  float ms_all = 0.f, ms_loop = 0.f;
-  KP_HIP(hipEventElapsedTime(&ms_all, c->ev0, c->ev1));
-  KP_HIP(hipEventElapsedTime(&ms_loop, h0, h1));
-  double hot = 0.0;
-  for (size_t i = 0; i < c->hot_pairs.size(); ++i) {
-    float ms = 0.f;
-    KP_HIP(hipEventElapsedTime(&ms, c->event(2 * i), c->event(2 * i + 1)));
-    c->hot_pairs[i].second = ms * 1e-3;
-    hot += ms * 1e-3;
-    kp_push_interval(c, c->event(2 * i), c->event(2 * i + 1));
-  }
-  c->timing.device_s = ms_all * 1e-3;
-  c->timing.loop_s = ms_loop * 1e-3;
-  c->timing.hot_s = hot;
-  c->timing.hot_launches = hot_launches;
-  double work = 0.0;
-  for (auto& pr : c->hot_pairs) work += pr.first * (double)c->n_ent;
-  c->timing.hot_work = work;
+                 t_steps[2] - t_steps[1], t_steps[3] - t_steps[2], t_done - t_enq);
+  record_hot_timing(c, hot_launches, h0, h1);
 }
 
 void complex_scores_dev(kp_ctx* c, int n, const int32_t* dh, const int32_t* dr, float* dS, int ld) {
   if (n <= 0) return;
   const int DP = c->dp;
-  float* dQ = reinterpret_cast<float*>(c->ws[17].ensure(sizeof(float) * (size_t)n * DP));
+  float* dQ = reinterpret_cast<float*>(c->cx.score_q.ensure(sizeof(float) * (size_t)n * DP));
   hipLaunchKernelGGL(kp_cx_scoreq, dim3(n), dim3(128), 0, c->stream, c->dE, c->dR, DP, c->dim / 2, dh, dr, n, dQ);
   KP_HIP(hipGetLastError());
   launch_score_gemm(c, dQ, n, dS, ld, 0);
@@ -885,9 +827,11 @@ void complex_scores_dev(kp_ctx* c, int n, const int32_t* dh, const int32_t* dr, 
 
 void complex_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rels, float* out) {
   if (n <= 0) return;
-  int32_t* dh = upload(c, c->ws[18], heads, (size_t)n);
-  int32_t* dr = upload(c, c->ws[19], rels, (size_t)n);
-  float* dS = reinterpret_cast<float*>(c->ws[16].ensure(sizeof(float) * (size_t)n * c->n_ent));
+  // the pairs go through the rank's two id buffers (idle outside complex_posttrain_rank)
+  // rather than two of their own, which keeps the context's device allocations as they were
+  int32_t* dh = upload(c, c->rank.pred, heads, (size_t)n);
+  int32_t* dr = upload(c, c->rank.po, rels, (size_t)n);
+  float* dS = reinterpret_cast<float*>(c->cx.score_out.ensure(sizeof(float) * (size_t)n * c->n_ent));
   complex_scores_dev(c, n, dh, dr, dS, c->n_ent);
   KP_HIP(hipMemcpyAsync(out, dS, sizeof(float) * (size_t)n * c->n_ent, hipMemcpyDeviceToHost, c->stream));
   KP_HIP(hipStreamSynchronize(c->stream));

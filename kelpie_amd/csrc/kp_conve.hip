@@ -21,7 +21,6 @@
 //   kelpie-column corrections and the encoder backward (kp_cv_dx, FC^T GEMM,
 //   kp_cv_conv_bwd) -> kp_cv_update (+ the kelpie-column gradient of every pair;
 //   pairs with a frozen head reuse their precomputed FC output) -> Adam.
-#include <chrono>
 #include <cstdio>
 #include <cmath>
 #include <unordered_map>
@@ -29,6 +28,7 @@
 #include "kp_attn.hpp"
 #include "kp_attn3.hpp"
 #include "kp_cv_fused.hpp"
+#include "kp_posttrain.hpp"
 
 int cx_pick_db(int dim);
 
@@ -644,8 +644,8 @@ CvConst make_const(kp_ctx* c, const kp_hp* hp) {
 void encode_eval(kp_ctx* c, int n, const int2* dsrc, const float* dX, float* dQ) {
   if (n <= 0) return;
   CvConst k = make_const(c, nullptr);
-  float* dflat = reinterpret_cast<float*>(c->ws[12].ensure(sizeof(float) * (size_t)n * c->hidden));
-  float* dfc = reinterpret_cast<float*>(c->ws[13].ensure(sizeof(float) * (size_t)n * c->dim));
+  float* dflat = reinterpret_cast<float*>(c->cv.flat.ensure(sizeof(float) * (size_t)n * c->hidden));
+  float* dfc = reinterpret_cast<float*>(c->cv.slab.ensure(sizeof(float) * (size_t)n * c->dim));
   KP_CONV_FWD(dim3(n), dim3(256), 0, c->stream, n, dsrc, c->dE, dX, c->dR, k, c->d_conv_w,
                      c->d_conv_b, c->d_bn_a, c->d_bn_b, nullptr, nullptr, dflat);
   KP_HIP(hipGetLastError());
@@ -679,15 +679,11 @@ static void conve_fused_images(kp_ctx* c, const __bf16** fw, const __bf16** bw) 
 
 void conve_encode_dev(kp_ctx* c, int n, const int2* d_src, float* d_out) { encode_eval(c, n, d_src, nullptr, d_out); }
 
-// KP_HOST_TIMES=1 (diagnostic): per call, on stderr, the host time of the planning, the
-// uploads, enqueueing the step loop, and the rank with the final wait
-static const bool g_cv_host_times = std::getenv("KP_HOST_TIMES") != nullptr;
-static double cv_host_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
+// KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time of the planning, the uploads,
+// enqueueing the step loop, and the rank with the final wait
 void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
-  const double t_in = g_cv_host_times ? cv_host_ms() : 0.0;
+  const double t_in = g_host_times ? host_ms() : 0.0;
+  require_batch(c, bt, "ConvE");
   const int ns = bt->n_slots;
   const int K = c->n_ent;
   const int DP = c->dp;
@@ -717,12 +713,10 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   int T = 0;
   for (int s = 0; s < ns; ++s) {
     const int r0 = bt->row_off[s], r1 = bt->row_off[s + 1];
-    KP_REQUIRE(r1 >= r0, "ConvE: bad row_off");
     std::unordered_map<long long, int> idx;
     auto& P = plan[s].pairs;
     for (int j = r0; j < r1; ++j) {
       const int h = bt->rows[3 * j], r = bt->rows[3 * j + 1], t = bt->rows[3 * j + 2];
-      KP_REQUIRE(h >= 0 && h <= K && t >= 0 && t <= K && r >= 0 && r < c->n_rel2, "ConvE: row id out of range");
       const long long key = (long long)h * c->n_rel2 + r;
       auto it = idx.find(key);
       if (it == idx.end()) {
@@ -874,36 +868,35 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   fin_off[T] = (int)finst.size();
   act_o[T] = (int)acts.size();
 
-  const double t_plan = g_cv_host_times ? cv_host_ms() : 0.0;
+  const double t_plan = g_host_times ? host_ms() : 0.0;
   // ---------------- uploads
-  std::vector<float> xp((size_t)ns * DP, 0.f);
-  for (int s = 0; s < ns; ++s) std::memcpy(&xp[(size_t)s * DP], bt->x0 + (size_t)s * c->dim, sizeof(float) * c->dim);
-  float* dX = upload(c, c->ws[0], xp.data(), xp.size());
-  float* dS1 = reinterpret_cast<float*>(c->ws[1].ensure(sizeof(float) * xp.size()));
-  float* dS2 = reinterpret_cast<float*>(c->ws[2].ensure(sizeof(float) * xp.size()));
+  std::vector<float> xp;
+  float* dX = upload_x0(c, c->cv.x, bt, xp);
+  float* dS1 = reinterpret_cast<float*>(c->cv.s1.ensure(sizeof(float) * xp.size()));
+  float* dS2 = reinterpret_cast<float*>(c->cv.s2.ensure(sizeof(float) * xp.size()));
   KP_HIP(hipMemsetAsync(dS1, 0, sizeof(float) * xp.size(), c->stream));
   KP_HIP(hipMemsetAsync(dS2, 0, sizeof(float) * xp.size(), c->stream));
-  CvInst* dKI = upload(c, c->ws[3], kinst.data(), std::max<size_t>(1, kinst.size()));
-  CvFInst* dFI = upload(c, c->ws[4], finst.data(), std::max<size_t>(1, finst.size()));
-  CvAct* dAct = upload(c, c->ws[5], acts.data(), std::max<size_t>(1, acts.size()));
-  int32_t* dTails = upload(c, c->ws[6], tails.data(), std::max<size_t>(1, tails.size()));
+  CvInst* dKI = upload(c, c->cv.kinst, kinst.data(), std::max<size_t>(1, kinst.size()));
+  CvFInst* dFI = upload(c, c->cv.finst, finst.data(), std::max<size_t>(1, finst.size()));
+  CvAct* dAct = upload(c, c->cv.acts, acts.data(), std::max<size_t>(1, acts.size()));
+  int32_t* dTails = upload(c, c->cv.tails, tails.data(), std::max<size_t>(1, tails.size()));
   const int64_t nbits = bt->rng_off[ns];
   // the keep bits, plus one zero guard word (kp_cv_fwd_fused reads a row's input bits as
   // a 64-bit window)
-  int32_t* dBits = reinterpret_cast<int32_t*>(c->ws[7].ensure(sizeof(int32_t) * (size_t)(nbits + 2)));
+  int32_t* dBits = reinterpret_cast<int32_t*>(c->cv.keep_bits.ensure(sizeof(int32_t) * (size_t)(nbits + 2)));
   if (nbits > 0)
     KP_HIP(hipMemcpyAsync(dBits, bt->rng, sizeof(int32_t) * (size_t)nbits, hipMemcpyHostToDevice, c->stream));
   KP_HIP(hipMemsetAsync(dBits + nbits, 0, 2 * sizeof(int32_t), c->stream));
   const int nfp = kc.fr_step ? 0 : (int)fpairs.size();
 
-  const double t_up = g_cv_host_times ? cv_host_ms() : 0.0;
+  const double t_up = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipEventRecord(c->ev0, c->stream));
   // frozen-head pairs without an input / feature-map dropout: FC output (pre-dropout)
   // once per batch
-  float* dFcf = reinterpret_cast<float*>(c->ws[8].ensure(sizeof(float) * (size_t)std::max(1, nfp) * c->dim));
+  float* dFcf = reinterpret_cast<float*>(c->cv.fcf.ensure(sizeof(float) * (size_t)std::max(1, nfp) * c->dim));
   if (nfp > 0) {
-    int2* dFp = upload(c, c->ws[9], fpairs.data(), fpairs.size());
-    float* dflat = reinterpret_cast<float*>(c->ws[12].ensure(sizeof(float) * (size_t)nfp * c->hidden));
+    int2* dFp = upload(c, c->cv.fpairs, fpairs.data(), fpairs.size());
+    float* dflat = reinterpret_cast<float*>(c->cv.flat.ensure(sizeof(float) * (size_t)nfp * c->hidden));
     KP_CONV_FWD(dim3(nfp), dim3(256), 0, c->stream, nfp, dFp, c->dE, dX, c->dR, kc,
                        c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, nullptr, nullptr, dflat);
     KP_HIP(hipGetLastError());
@@ -915,16 +908,16 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   const int KS = fused ? kpcvf::NSPLIT : 8;  // split-K of the FC forward
   const int mk = std::max(1, max_k);
   const int me = std::max(1, max_enc);  // encoder rows per step (kelpie pairs + per-step frozen pairs)
-  float* dflat = reinterpret_cast<float*>(c->ws[12].ensure(sizeof(float) * (size_t)std::max(fused ? 1 : me, nfp) * c->hidden));
-  float* dslab = reinterpret_cast<float*>(c->ws[13].ensure(sizeof(float) * (size_t)KS * me * c->dim));
+  float* dflat = reinterpret_cast<float*>(c->cv.flat.ensure(sizeof(float) * (size_t)std::max(fused ? 1 : me, nfp) * c->hidden));
+  float* dslab = reinterpret_cast<float*>(c->cv.slab.ensure(sizeof(float) * (size_t)KS * me * c->dim));
   const __bf16* cvf_fw = nullptr;
   const __bf16* cvf_bw = nullptr;
   uint8_t* dRelu = nullptr;
   __bf16* dG3 = nullptr;
   if (fused) {
     conve_fused_images(c, &cvf_fw, &cvf_bw);
-    dRelu = reinterpret_cast<uint8_t*>(c->ws[24].ensure((size_t)me * kpcvf::MASK_B));
-    dG3 = reinterpret_cast<__bf16*>(c->ws[25].ensure(3 * sizeof(__bf16) * (size_t)mk * kpcvf::KB));
+    dRelu = reinterpret_cast<uint8_t*>(c->cv.relu.ensure((size_t)me * kpcvf::MASK_B));
+    dG3 = reinterpret_cast<__bf16*>(c->cv.g3.ensure(3 * sizeof(__bf16) * (size_t)mk * kpcvf::KB));
   }
   // the shared-encoder split (kp_cv_fused.hpp): kelpie rows' map rows 0-17 in NB_L bands,
   // the pairs' rows 18-19 in NB_M, the relations' rows 20-37 (once per context) in NB_L
@@ -976,25 +969,25 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
       bo.release();
       c->cv_shared_ready = true;
     }
-    dSrSrc = upload(c, c->cvs[0], sr_src.data(), std::max<size_t>(1, sr_src.size()));
-    dSrRng = upload(c, c->cvs[1], sr_rng.data(), std::max<size_t>(1, sr_rng.size()));
-    dPsr = upload(c, c->cvs[2], psr.data(), std::max<size_t>(1, psr.size()));
-    dReluS = reinterpret_cast<uint8_t*>(c->cvs[3].ensure((size_t)msr * kpcvf::MASK_B));
+    dSrSrc = upload(c, c->cv.sr_src, sr_src.data(), std::max<size_t>(1, sr_src.size()));
+    dSrRng = upload(c, c->cv.sr_rng, sr_rng.data(), std::max<size_t>(1, sr_rng.size()));
+    dPsr = upload(c, c->cv.psr, psr.data(), std::max<size_t>(1, psr.size()));
+    dReluS = reinterpret_cast<uint8_t*>(c->cv.relu_s.ensure((size_t)msr * kpcvf::MASK_B));
     KP_HIP(hipMemsetAsync(dReluS, 0, (size_t)msr * kpcvf::MASK_B, c->stream));  // rows 18-19 stay 0
-    dSlabL = reinterpret_cast<float*>(c->cvs[4].ensure(sizeof(float) * (size_t)kpcvf::KSL * msr * c->dim));
-    dMapM = reinterpret_cast<float*>(c->cvs[9].ensure(sizeof(float) * (size_t)mk * kpcvf::NMID));
-    dMid = reinterpret_cast<float*>(c->cvs[5].ensure(sizeof(float) * (size_t)mk * c->dim));
-    dMapL = reinterpret_cast<float*>(c->cvs[6].ensure(sizeof(float) * (size_t)msr * kpcvf::NLHS));
-    dGs = reinterpret_cast<float*>(c->cvs[7].ensure(sizeof(float) * (size_t)msr * c->dim));
-    dDls = reinterpret_cast<float*>(c->cvs[8].ensure(sizeof(float) * (size_t)msr * DP));
+    dSlabL = reinterpret_cast<float*>(c->cv.slab_l.ensure(sizeof(float) * (size_t)kpcvf::KSL * msr * c->dim));
+    dMapM = reinterpret_cast<float*>(c->cv.map_m.ensure(sizeof(float) * (size_t)mk * kpcvf::NMID));
+    dMid = reinterpret_cast<float*>(c->cv.mid.ensure(sizeof(float) * (size_t)mk * c->dim));
+    dMapL = reinterpret_cast<float*>(c->cv.map_l.ensure(sizeof(float) * (size_t)msr * kpcvf::NLHS));
+    dGs = reinterpret_cast<float*>(c->cv.gs.ensure(sizeof(float) * (size_t)msr * c->dim));
+    dDls = reinterpret_cast<float*>(c->cv.dls.ensure(sizeof(float) * (size_t)msr * DP));
   }
   const int n_dl = fused ? kpcvf::NSPLIT : 1;  // lhs image-gradient slabs per pair (kp_cv_bwd_fused, reduced in slab 0)
-  float* dQ = reinterpret_cast<float*>(c->ws[14].ensure(sizeof(float) * (size_t)me * DP));
-  int2* dSrc = upload(c, c->ws[15], enc_src.data(), std::max<size_t>(1, enc_src.size()));
-  int4* dFch = upload(c, c->cvs[10], fchunks.data(), std::max<size_t>(1, fchunks.size()));
-  float* dFpart = reinterpret_cast<float*>(c->ws[31].ensure(sizeof(float) * (size_t)std::max(1, max_fch) * c->dim));
-  CvBits* dEncBits = upload(c, c->ws[26], enc_bits.data(), std::max<size_t>(1, enc_bits.size()));
-  float* dgs = reinterpret_cast<float*>(c->ws[16].ensure(sizeof(float) * (size_t)std::max<size_t>(1, kinst.size())));
+  float* dQ = reinterpret_cast<float*>(c->cv.q.ensure(sizeof(float) * (size_t)me * DP));
+  int2* dSrc = upload(c, c->cv.enc_src, enc_src.data(), std::max<size_t>(1, enc_src.size()));
+  int4* dFch = upload(c, c->cv.fchunks, fchunks.data(), std::max<size_t>(1, fchunks.size()));
+  float* dFpart = reinterpret_cast<float*>(c->cv.fpart.ensure(sizeof(float) * (size_t)std::max(1, max_fch) * c->dim));
+  CvBits* dEncBits = upload(c, c->cv.enc_bits, enc_bits.data(), std::max<size_t>(1, enc_bits.size()));
+  float* dgs = reinterpret_cast<float*>(c->cv.gscale.ensure(sizeof(float) * (size_t)std::max<size_t>(1, kinst.size())));
   {
     std::vector<float> gsv(kinst.size());
     for (size_t i = 0; i < kinst.size(); ++i) gsv[i] = 1.0f / (float)((long long)kinst[i].b * (long long)(K + 1));
@@ -1019,11 +1012,11 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
     step_plan[t] = attn_plan_ctx(c, std::max(nk, 1), K, attn_slots);
     o_rows = std::max(o_rows, (size_t)nk * step_plan[t].wk.n_parts);
   }
-  float* dO = reinterpret_cast<float*>(c->ws[17].ensure(sizeof(float) * o_rows * DP));
-  float* ddfc = reinterpret_cast<float*>(c->ws[18].ensure(sizeof(float) * (size_t)mk * c->dim));
-  float* dgk = reinterpret_cast<float*>(c->ws[19].ensure(sizeof(float) * (size_t)mk));
-  float* ddflat = reinterpret_cast<float*>(c->ws[20].ensure(sizeof(float) * (size_t)(fused ? 1 : mk) * c->hidden));
-  float* ddl = reinterpret_cast<float*>(c->ws[21].ensure(sizeof(float) * (size_t)n_dl * mk * DP));
+  float* dO = reinterpret_cast<float*>(c->cv.o.ensure(sizeof(float) * o_rows * DP));
+  float* ddfc = reinterpret_cast<float*>(c->cv.dfc.ensure(sizeof(float) * (size_t)mk * c->dim));
+  float* dgk = reinterpret_cast<float*>(c->cv.gk.ensure(sizeof(float) * (size_t)mk));
+  float* ddflat = reinterpret_cast<float*>(c->cv.dflat.ensure(sizeof(float) * (size_t)(fused ? 1 : mk) * c->hidden));
+  float* ddl = reinterpret_cast<float*>(c->cv.dl.ensure(sizeof(float) * (size_t)n_dl * mk * DP));
   float* dWt = conve_fc_wt(c);
   // the masks' multipliers as the fused kernels take them (1: not drawn)
   const float s_in = kc.has_in ? kc.scale_in : 1.0f, s_fm = kc.has_fm ? kc.scale_fm : 1.0f;
@@ -1035,7 +1028,6 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   opt.eps = hp->eps;
   opt.one_minus_b1 = (float)(1.0 - (double)hp->beta1);
   opt.one_minus_b2 = (float)(1.0 - (double)hp->beta2);
-  double hot = 0.0, work = 0.0;
   int64_t launches = 0;
   c->hot_pairs.clear();
   c->hot_iv.clear();
@@ -1191,79 +1183,48 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
     }
   }
 
-  const double t_loop = g_cv_host_times ? cv_host_ms() : 0.0;
+  const double t_loop = g_host_times ? host_ms() : 0.0;
   // ---------------- rank: sigmoid(enc(x, R_p) . E_e), kelpie column, maximizer
   std::vector<int2> rsrc(ns);
-  std::vector<int32_t> po(ns);
-  for (int s = 0; s < ns; ++s) {
-    KP_REQUIRE(bt->pred[3 * s] == K, "ConvE: the ranked triple must start at the kelpie entity");
-    KP_REQUIRE(bt->pred[3 * s + 1] >= 0 && bt->pred[3 * s + 1] < c->n_rel2, "ConvE: ranked relation out of range");
-    KP_REQUIRE(bt->pred[3 * s + 2] >= 0 && bt->pred[3 * s + 2] <= K, "ConvE: ranked object out of range");
-    rsrc[s] = make_int2(-s - 1, bt->pred[3 * s + 1]);
-    po[s] = bt->pred[3 * s + 2];
-  }
-  int2* dRsrc = upload(c, c->ws[11], rsrc.data(), rsrc.size());
-  float* dQr = reinterpret_cast<float*>(c->ws[14].ensure(sizeof(float) * (size_t)std::max(ns, mk) * DP));
+  for (int s = 0; s < ns; ++s) rsrc[s] = make_int2(-s - 1, bt->pred[3 * s + 1]);
+  int2* dRsrc = upload(c, c->cv.rank_src, rsrc.data(), rsrc.size());
+  float* dQr = reinterpret_cast<float*>(c->cv.q.ensure(sizeof(float) * (size_t)std::max(ns, mk) * DP));
   encode_eval(c, ns, dRsrc, dX, dQr);
-  int32_t* dPo = upload(c, c->ws[22], po.data(), po.size());
-  int32_t* dFo = upload(c, c->ws[23], bt->filt_off, (size_t)ns + 1);
-  // context buffers (a per-call buffer's hipFree waits for the whole device, every context)
-  int32_t* dF = upload(c, c->cvs[11], bt->filt, (size_t)std::max(1, bt->filt_off[ns]));
-  float* dTarget = reinterpret_cast<float*>(c->cvs[12].ensure(sizeof(float) * ns));
-  int64_t* dRank = reinterpret_cast<int64_t*>(c->cvs[13].ensure(sizeof(int64_t) * ns));
+  const RankDev rk = upload_rank_inputs(c, bt);
   if (c->cv_rank64) {
-    double* dQ64 = reinterpret_cast<double*>(c->ws[29].ensure(sizeof(double) * (size_t)ns * DP));
-    double* dT64 = reinterpret_cast<double*>(c->ws[30].ensure(sizeof(double) * 2 * (size_t)ns));
-    hipLaunchKernelGGL(kp_cv_rankq64, dim3(ns), dim3(64), 0, c->stream, dQr, dX, c->dE, K, DP, dPo, ns, dQ64, dT64,
-                       dT64 + ns);
+    const Rank64Dev r64 = rank64_buffers(c, ns);
+    hipLaunchKernelGGL(kp_cv_rankq64, dim3(ns), dim3(64), 0, c->stream, dQr, dX, c->dE, K, DP, rk.po, ns, r64.q, r64.t,
+                       r64.kcol);
     KP_HIP(hipGetLastError());
-    launch_rank_f64(c, ns, dQ64, dT64, dT64 + ns, dPo, dFo, dF, dTarget, dRank, RANK64_SIGMOID);
+    launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_SIGMOID);
   } else {
     const int ld = round_up(K + 1, 4);
-    float* dScores = reinterpret_cast<float*>(c->ws[10].ensure(sizeof(float) * (size_t)ns * ld));
+    float* dScores = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)ns * ld));
     launch_score_gemm(c, dQr, ns, dScores, ld, 1);
     hipLaunchKernelGGL(kp_cv_kcol, dim3(ns), dim3(64), 0, c->stream, ns, kc, dQr, dX, dScores, ld);
     KP_HIP(hipGetLastError());
-    launch_rank_count(c, ns, dScores, ld, K + 1, dPo, dFo, dF, 0, dTarget, dRank);
+    launch_rank_count(c, ns, dScores, ld, K + 1, rk.po, rk.filt_off, rk.filt, 0, rk.target, rk.rank);
   }
   KP_HIP(hipEventRecord(c->ev1, c->stream));
-  if (bt->out_x) KP_HIP(hipMemcpyAsync(xp.data(), dX, sizeof(float) * xp.size(), hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(bt->out_score, dTarget, sizeof(float) * ns, hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(bt->out_rank, dRank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipStreamSynchronize(c->stream));
-  if (g_cv_host_times)
+  download_results(c, bt, dX, rk, xp);
+  if (g_host_times)
     std::fprintf(stderr, "[kp_cv] slots %d steps %d pairs %zu: plan %.2f ms, uploads %.2f ms, loop enqueue %.2f ms, "
                  "rank + wait %.2f ms\n", ns, T, kinst.size(), t_plan - t_in, t_up - t_plan, t_loop - t_up,
-                 cv_host_ms() - t_loop);
-  if (bt->out_x)
-    for (int s = 0; s < ns; ++s) std::memcpy(bt->out_x + (size_t)s * c->dim, &xp[(size_t)s * DP], sizeof(float) * c->dim);
-  float ms_all = 0.f;
-  KP_HIP(hipEventElapsedTime(&ms_all, c->ev0, c->ev1));
-  for (size_t i = 0; i < c->hot_pairs.size(); ++i) {
-    float ms = 0.f;
-    KP_HIP(hipEventElapsedTime(&ms, c->event(2 * i), c->event(2 * i + 1)));
-    hot += ms * 1e-3;
-    kp_push_interval(c, c->event(2 * i), c->event(2 * i + 1));
-    work += c->hot_pairs[i].first * (double)K;
-  }
-  c->timing.device_s = ms_all * 1e-3;
-  c->timing.loop_s = ms_all * 1e-3;
-  c->timing.hot_s = hot;
-  c->timing.hot_launches = launches;
-  c->timing.hot_work = work;
+                 host_ms() - t_loop);
+  record_hot_timing(c, launches, c->ev0, c->ev1);  // the whole call counts as its loop
 }
 
 float* conve_fc_wt(kp_ctx* c) {
   // FC weight transposed [hidden][dim] for the backward GEMM (built once, kept in the context)
-  if (!c->dEt) {
+  if (!c->d_fc_wt) {
     std::vector<float> w((size_t)c->dim * c->hidden), wt((size_t)c->dim * c->hidden);
     KP_HIP(hipMemcpy(w.data(), c->d_fc_w, sizeof(float) * w.size(), hipMemcpyDeviceToHost));
     for (int o = 0; o < c->dim; ++o)
       for (int j = 0; j < c->hidden; ++j) wt[(size_t)j * c->dim + o] = w[(size_t)o * c->hidden + j];
-    KP_HIP(hipMalloc(&c->dEt, sizeof(float) * wt.size()));
-    KP_HIP(hipMemcpy(c->dEt, wt.data(), sizeof(float) * wt.size(), hipMemcpyHostToDevice));
+    KP_HIP(hipMalloc(&c->d_fc_wt, sizeof(float) * wt.size()));
+    KP_HIP(hipMemcpy(c->d_fc_wt, wt.data(), sizeof(float) * wt.size(), hipMemcpyHostToDevice));
   }
-  return c->dEt;
+  return c->d_fc_wt;
 }
 
 void conve_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* d_rels, float* d_out, int ld) {

@@ -1,0 +1,114 @@
+// kp_posttrain.hpp -- the host work the three *_posttrain_rank functions share: the batch
+// check, the kelpie rows' padding, the rank inputs, the result download and the hot-launch
+// timing.  Everything model-specific (planning, launches, where in the call the rank inputs
+// are uploaded) stays in kp_complex.hip / kp_transe.hip / kp_conve.hip.
+#pragma once
+
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+
+#include "kp_batch_check.hpp"
+#include "kp_common.hpp"
+
+// KP_HOST_TIMES=1 (diagnostic): ComplEx and ConvE print, per call on stderr, the host time
+// of their phases (planning, uploads, enqueueing the loop, waiting for the device)
+inline const bool g_host_times = std::getenv("KP_HOST_TIMES") != nullptr;
+inline double host_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// the structural checks of kp_batch_check.hpp, thrown as KP_EINVAL under the model's name;
+// first thing in every *_posttrain_rank, so a malformed batch leaves no device work in flight
+inline void require_batch(const kp_ctx* c, const kp_batch* bt, const char* model) {
+  if (const char* why = kp_check_batch(c->n_ent, c->n_rel2, c->dim, bt))
+    throw KpError{KP_EINVAL, std::string(model) + ": " + why};
+}
+
+// x0 [ns][dim] zero-padded to [ns][dp] in `xp` (kept by the caller for download_results)
+// and uploaded into `b`
+inline float* upload_x0(kp_ctx* c, DevBuf& b, const kp_batch* bt, std::vector<float>& xp) {
+  const int ns = bt->n_slots;
+  xp.assign((size_t)ns * c->dp, 0.f);
+  for (int s = 0; s < ns; ++s)
+    std::memcpy(&xp[(size_t)s * c->dp], bt->x0 + (size_t)s * c->dim, sizeof(float) * c->dim);
+  return upload(c, b, xp.data(), xp.size());
+}
+
+// the rank's inputs and results on the device (c->rank)
+struct RankDev {
+  int32_t* po;        // [ns] the ranked objects
+  int32_t* filt_off;  // the filter CSR
+  int32_t* filt;
+  float* target;  // [ns]
+  int64_t* rank;  // [ns]
+};
+
+// upload the ranked objects and the filter CSR, size the result buffers.  The caller
+// chooses where in its call this happens: an upload's position decides what it overlaps.
+inline RankDev upload_rank_inputs(kp_ctx* c, const kp_batch* bt) {
+  const int ns = bt->n_slots;
+  std::vector<int32_t> po(ns);
+  for (int s = 0; s < ns; ++s) po[s] = bt->pred[3 * s + 2];
+  RankDev r;
+  r.po = upload(c, c->rank.po, po.data(), po.size());
+  r.filt_off = upload(c, c->rank.filt_off, bt->filt_off, (size_t)ns + 1);
+  r.filt = upload(c, c->rank.filt, bt->filt, (size_t)bt->filt_off[ns]);
+  r.target = reinterpret_cast<float*>(c->rank.target.ensure(sizeof(float) * (size_t)ns));
+  r.rank = reinterpret_cast<int64_t*>(c->rank.rank.ensure(sizeof(int64_t) * (size_t)ns));
+  return r;
+}
+
+// launch_rank_f64's fp64 operands: the queries [ns][dp], and the target scores [ns]
+// followed by the kelpie column scores [ns]
+struct Rank64Dev {
+  double *q, *t, *kcol;
+};
+inline Rank64Dev rank64_buffers(kp_ctx* c, int ns) {
+  Rank64Dev r;
+  r.q = reinterpret_cast<double*>(c->rank.q64.ensure(sizeof(double) * (size_t)ns * c->dp));
+  r.t = reinterpret_cast<double*>(c->rank.t64.ensure(sizeof(double) * 2 * (size_t)ns));
+  r.kcol = r.t + ns;
+  return r;
+}
+
+// the tail of a call: enqueue the downloads of the kelpie rows (when out_x is set), the
+// target scores and the ranks, wait for the stream once, unpad the rows into out_x.
+// Returns the host time at which the wait began (0 unless KP_HOST_TIMES).
+inline double download_results(kp_ctx* c, const kp_batch* bt, const float* dX, const RankDev& r,
+                               std::vector<float>& xp) {
+  const int ns = bt->n_slots;
+  if (bt->out_x) KP_HIP(hipMemcpyAsync(xp.data(), dX, sizeof(float) * xp.size(), hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipMemcpyAsync(bt->out_score, r.target, sizeof(float) * ns, hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipMemcpyAsync(bt->out_rank, r.rank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
+  const double t_wait = g_host_times ? host_ms() : 0.0;
+  KP_HIP(hipStreamSynchronize(c->stream));
+  if (bt->out_x)
+    for (int s = 0; s < ns; ++s)
+      std::memcpy(bt->out_x + (size_t)s * c->dim, &xp[(size_t)s * c->dp], sizeof(float) * c->dim);
+  return t_wait;
+}
+
+// the timing of a call whose hot launches were bracketed by the context's event pairs
+// (2i, 2i + 1), one c->hot_pairs entry (work units, 0) each: the call (ev0 -> ev1), its
+// loop (loop0 -> loop1), each hot launch's duration and interval, and the work sum in
+// units of n_ent.  After the stream has been synchronised.
+inline void record_hot_timing(kp_ctx* c, int64_t hot_launches, hipEvent_t loop0, hipEvent_t loop1) {
+  float ms_all = 0.f, ms_loop = 0.f;
+  KP_HIP(hipEventElapsedTime(&ms_all, c->ev0, c->ev1));
+  KP_HIP(hipEventElapsedTime(&ms_loop, loop0, loop1));
+  double hot = 0.0, work = 0.0;
+  for (size_t i = 0; i < c->hot_pairs.size(); ++i) {
+    float ms = 0.f;
+    KP_HIP(hipEventElapsedTime(&ms, c->event(2 * i), c->event(2 * i + 1)));
+    c->hot_pairs[i].second = ms * 1e-3;
+    hot += ms * 1e-3;
+    kp_push_interval(c, c->event(2 * i), c->event(2 * i + 1));
+    work += c->hot_pairs[i].first * (double)c->n_ent;
+  }
+  c->timing.device_s = ms_all * 1e-3;
+  c->timing.loop_s = ms_loop * 1e-3;
+  c->timing.hot_s = hot;
+  c->timing.hot_launches = hot_launches;
+  c->timing.hot_work = work;
+}

@@ -320,7 +320,7 @@ void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* 
   }
   const int n_cols = c->n_ent + 1;
   const int nwords = (n_cols + 31) / 32;
-  uint32_t* bits = reinterpret_cast<uint32_t*>(c->ws[28].ensure(sizeof(uint32_t) * (size_t)n_slots * nwords));
+  uint32_t* bits = reinterpret_cast<uint32_t*>(c->rank.bits.ensure(sizeof(uint32_t) * (size_t)n_slots * nwords));
   unsigned long long* rank = reinterpret_cast<unsigned long long*>(d_rank);
   hipLaunchKernelGGL(kp_rank_filter_bits, dim3(n_slots), dim3(256), 0, c->stream, n_slots, nwords, d_filt_off, d_filt,
                      n_cols, bits);

@@ -573,9 +573,9 @@ void conve_train_step(kp_ctx* c, int B, const int32_t* pairs, const int32_t* tai
   KP_HIP(hipStreamSynchronize(s));
   // the tables and layers changed: every derived image is stale
   c->e3_ready = c->e3pre_ready = c->eT_ready = c->cvf_ready = false;
-  if (c->dEt) {
-    (void)hipFree(c->dEt);
-    c->dEt = nullptr;
+  if (c->d_fc_wt) {
+    (void)hipFree(c->d_fc_wt);
+    c->d_fc_wt = nullptr;
   }
 }
 

@@ -22,7 +22,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "kp_common.hpp"
+#include "kp_posttrain.hpp"
 
 namespace {
 
@@ -514,26 +514,22 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   const int ns = bt->n_slots;
   const int DP = c->dp;
   const bool l1 = c->te_norm == 1;
+  require_batch(c, bt, "TransE");
   KP_REQUIRE(hp->neg_ratio >= 1 && hp->batch_size >= 1 && hp->epochs >= 0, "TransE: bad hyper-parameters");
   std::vector<TeSlot> slots(ns);
   for (int s = 0; s < ns; ++s) {
     const int R = bt->row_off[s + 1] - bt->row_off[s];
-    KP_REQUIRE(R >= 0, "TransE: bad row_off");
     slots[s] = TeSlot{bt->row_off[s], R, (long long)bt->rng_off[s]};
     KP_REQUIRE(bt->rng_off[s + 1] - bt->rng_off[s] >= (int64_t)hp->epochs * 3 * R,
                "TransE: missing per-epoch draws (order | entities | head_or_tail)");
   }
   const int total_rows = bt->row_off[ns];
-  for (int i = 0; i < 3 * total_rows; ++i)
-    KP_REQUIRE(bt->rows[i] >= 0 && bt->rows[i] <= ((i % 3) == 1 ? c->n_rel2 - 1 : c->n_ent),
-               "TransE: row id out of range");
-  std::vector<float> xp((size_t)ns * DP, 0.f);
-  for (int s = 0; s < ns; ++s) std::memcpy(&xp[(size_t)s * DP], bt->x0 + (size_t)s * c->dim, sizeof(float) * c->dim);
-  float* dX = upload(c, c->ws[0], xp.data(), xp.size());
-  TeSlot* dSlots = upload(c, c->ws[1], slots.data(), slots.size());
-  int32_t* dRows = upload(c, c->ws[2], bt->rows, (size_t)std::max(1, 3 * total_rows));
+  std::vector<float> xp;
+  float* dX = upload_x0(c, c->te.x, bt, xp);
+  TeSlot* dSlots = upload(c, c->te.slots, slots.data(), slots.size());
+  int32_t* dRows = upload(c, c->te.rows, bt->rows, (size_t)std::max(1, 3 * total_rows));
   const int64_t nrng = bt->rng_off[ns];
-  int32_t* dRng = upload(c, c->ws[3], bt->rng, (size_t)std::max<int64_t>(1, nrng));
+  int32_t* dRng = upload(c, c->te.rng, bt->rng, (size_t)std::max<int64_t>(1, nrng));
 
   TeHp h{};
   h.epochs = hp->epochs;
@@ -552,7 +548,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   std::vector<int32_t> order(ns);
   for (int s = 0; s < ns; ++s) order[s] = s;
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return slots[a].R > slots[b].R; });
-  int32_t* dOrder = upload(c, c->ws[12], order.data(), order.size());
+  int32_t* dOrder = upload(c, c->te.order, order.data(), order.size());
   KP_REQUIRE(DP <= 512, "TransE: dimension > 512 not supported");
   int max_r = 0;
   for (int s = 0; s < ns; ++s) max_r = std::max(max_r, slots[s].R);
@@ -600,41 +596,26 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
 
   // ---- rank: scores of (kelpie, p, .) = ||(x + R_p) - E_e||_p, minimizer
   const int ld = round_up(c->n_ent + 1, 4);
-  std::vector<int32_t> heads(ns, -1), rels(ns), po(ns);
-  for (int s = 0; s < ns; ++s) {
-    rels[s] = bt->pred[3 * s + 1];
-    po[s] = bt->pred[3 * s + 2];
-    KP_REQUIRE(bt->pred[3 * s] == c->n_ent, "TransE: the ranked triple must start at the kelpie entity");
-  }
-  int32_t* dH = upload(c, c->ws[4], heads.data(), heads.size());
-  int32_t* dRl = upload(c, c->ws[5], rels.data(), rels.size());
-  int32_t* dPo = upload(c, c->ws[6], po.data(), po.size());
-  int32_t* dFo = upload(c, c->ws[7], bt->filt_off, (size_t)ns + 1);
-  int32_t* dF = upload(c, c->ws[8], bt->filt, (size_t)std::max(1, bt->filt_off[ns]));
-  float* dTarget = reinterpret_cast<float*>(c->ws[10].ensure(sizeof(float) * ns));
-  int64_t* dRank = reinterpret_cast<int64_t*>(c->ws[11].ensure(sizeof(int64_t) * ns));
+  std::vector<int32_t> heads(ns, -1), rels(ns);
+  for (int s = 0; s < ns; ++s) rels[s] = bt->pred[3 * s + 1];
+  int32_t* dH = upload(c, c->te.heads, heads.data(), heads.size());
+  int32_t* dRl = upload(c, c->te.rels, rels.data(), rels.size());
+  const RankDev rk = upload_rank_inputs(c, bt);
   if (c->te_rank64) {
-    int32_t* dPred = upload(c, c->ws[13], bt->pred, (size_t)ns * 3);
-    double* dQ64 = reinterpret_cast<double*>(c->ws[29].ensure(sizeof(double) * (size_t)ns * DP));
-    double* dT64 = reinterpret_cast<double*>(c->ws[30].ensure(sizeof(double) * 2 * (size_t)ns));
+    int32_t* dPred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
+    const Rank64Dev r64 = rank64_buffers(c, ns);
     hipLaunchKernelGGL(kp_te_rankq64, dim3(ns), dim3(64), 0, c->stream, dX, c->dR, c->dE, c->n_ent, DP, dPred, ns,
-                       dQ64, dT64, dT64 + ns, l1 ? 1 : 0);
+                       r64.q, r64.t, r64.kcol, l1 ? 1 : 0);
     KP_HIP(hipGetLastError());
-    launch_rank_f64(c, ns, dQ64, dT64, dT64 + ns, dPo, dFo, dF, dTarget, dRank, l1 ? RANK64_DIST1 : RANK64_DIST);
+    launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank,
+                    l1 ? RANK64_DIST1 : RANK64_DIST);
   } else {
-    float* dScores = reinterpret_cast<float*>(c->ws[9].ensure(sizeof(float) * (size_t)ns * ld));
+    float* dScores = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)ns * ld));
     launch_te_scores(c, ns, dH, dRl, dX, dScores, ld, c->n_ent);
-    launch_rank_count(c, ns, dScores, ld, c->n_ent + 1, dPo, dFo, dF, 1, dTarget, dRank);
+    launch_rank_count(c, ns, dScores, ld, c->n_ent + 1, rk.po, rk.filt_off, rk.filt, 1, rk.target, rk.rank);
   }
   KP_HIP(hipEventRecord(c->ev1, c->stream));
-  if (bt->out_x) {
-    KP_HIP(hipMemcpyAsync(xp.data(), dX, sizeof(float) * xp.size(), hipMemcpyDeviceToHost, c->stream));
-  }
-  KP_HIP(hipMemcpyAsync(bt->out_score, dTarget, sizeof(float) * ns, hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(bt->out_rank, dRank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipStreamSynchronize(c->stream));
-  if (bt->out_x)
-    for (int s = 0; s < ns; ++s) std::memcpy(bt->out_x + (size_t)s * c->dim, &xp[(size_t)s * DP], sizeof(float) * c->dim);
+  download_results(c, bt, dX, rk, xp);
   float ms_all = 0.f, ms_hot = 0.f;
   KP_HIP(hipEventElapsedTime(&ms_all, c->ev0, c->ev1));
   KP_HIP(hipEventElapsedTime(&ms_hot, ea, eb));
@@ -655,9 +636,11 @@ void transe_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* 
 
 void transe_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rels, float* out) {
   if (n <= 0) return;
-  int32_t* dh = upload(c, c->ws[4], heads, (size_t)n);
-  int32_t* dr = upload(c, c->ws[5], rels, (size_t)n);
-  float* dS = reinterpret_cast<float*>(c->ws[9].ensure(sizeof(float) * (size_t)n * c->n_ent));
+  int32_t* dh = upload(c, c->te.heads, heads, (size_t)n);
+  int32_t* dr = upload(c, c->te.rels, rels, (size_t)n);
+  // the rank's fp32 score matrix (idle outside transe_posttrain_rank) rather than one of its
+  // own, which keeps the context's device allocations as they were
+  float* dS = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)n * c->n_ent));
   transe_scores_dev(c, n, dh, dr, dS, c->n_ent);
   KP_HIP(hipMemcpyAsync(out, dS, sizeof(float) * (size_t)n * c->n_ent, hipMemcpyDeviceToHost, c->stream));
   KP_HIP(hipStreamSynchronize(c->stream));

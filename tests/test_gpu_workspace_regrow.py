@@ -1,0 +1,70 @@
+"""A context's named device workspaces across batches of different sizes.
+
+The workspaces grow on demand and are shared by name between the model files and the
+rank path (kp_common.hpp).  Two buffers that alias each other, or a pointer kept across a
+regrowth, would not raise: they would give wrong ranks.  So, per model family, on ONE
+engine and context: a batch of 2 candidates, then one of 12 (every per-slot buffer
+regrows: 12 + 1 slots is more than the 25 % headroom over 2 + 1), then the first 2
+again.  The third result must equal the first bit for bit, and the middle one must equal
+the same 12 candidates on a fresh context.  D = 200 for ComplEx and ConvE (the bf16x3
+attention, the fused ConvE encoder), D = 32 for TransE; 3 epochs."""
+import pytest
+
+from golden_io import seed_all
+
+import kelpie_amd as ka
+
+pytestmark = pytest.mark.gpu
+
+HP = {
+    "ComplEx": {"optimizer_name": "Adagrad", "batch_size": 512, "epochs": 3, "lr": 0.043, "decay1": 0.9,
+                "decay2": 0.999, "regularizer_name": "N3", "regularizer_weight": 0},
+    "TransE": {"batch_size": 2048, "epochs": 3, "lr": 0.01, "margin": 5, "negative_triples_ratio": 5,
+               "regularizer_weight": 1.0},
+    "ConvE": {"batch_size": 512, "label_smoothing": 0.1, "lr": 0.0432, "decay": 0.995, "epochs": 3},
+}
+DIM = {"ComplEx": 200, "TransE": 32, "ConvE": 200}
+
+
+def _model(name, ds, w):
+    if name == "ComplEx":
+        return ka.ComplEx(ds, w["entity_embeddings"], w["relation_embeddings"], init_scale=1e-3)
+    if name == "TransE":
+        return ka.TransE(ds, w["entity_embeddings"], w["relation_embeddings"], norm=2)
+    bn = {i: {"weight": w[f"bn{i}_weight"], "bias": w[f"bn{i}_bias"], "running_mean": w[f"bn{i}_mean"],
+              "running_var": w[f"bn{i}_var"]} for i in (1, 2, 3)}
+    return ka.ConvE(ds, w["entity_embeddings"], w["relation_embeddings"], w["conv_weight"].reshape(32, 3, 3),
+                    w["conv_bias"], w["fc_weight"], w["fc_bias"], bn=bn, hidden_dropout_rate=0.2)
+
+
+def _run(eng, pred, cands):
+    """One batch from a cleared cache and fixed seeds: the relevances and every
+    (post-trained, base) rank and score."""
+    seed_all(42)
+    eng.set_cache()
+    rels = eng.compute_relevance_batch(pred, [[c] for c in cands])
+    return rels, [(pt["target_rank"], pt["target_score"], b["target_rank"], b["target_score"])
+                  for pt, b in eng.last_results]
+
+
+@pytest.mark.parametrize("name", ["ComplEx", "TransE", "ConvE"])
+def test_workspaces_survive_regrowth(name):
+    from kelpie_amd import synth
+    g = synth.make_graph("small", seed=9)
+    ds = ka.Dataset(g.num_entities, g.num_relations, g.train, g.valid, g.test)
+    extra = {"conve_random_bn": True, "trained_scale": 0.5} if name == "ConvE" else {}
+    w = synth.make_weights(name, g.num_entities, g.num_relations, DIM[name], seed=9, **extra)
+    deg = ds.entity_to_degree
+    pred = next(tuple(int(v) for v in t) for t in g.test if 12 <= deg.get(int(t[0]), 0) <= 40)
+    cands = sorted(ds.entity_to_training_triples[pred[0]])[:12]
+    assert len(cands) == 12
+
+    eng = ka.NecessaryPostTrainingEngine(_model(name, ds, w), ds, HP[name])
+    first = _run(eng, pred, cands[:2])
+    middle = _run(eng, pred, cands)
+    again = _run(eng, pred, cands[:2])
+    fresh = _run(ka.NecessaryPostTrainingEngine(_model(name, ds, w), ds, HP[name]), pred, cands)
+
+    assert len(first[1]) == 2 and len(middle[1]) == 12
+    assert again == first, (first, again)
+    assert middle == fresh, (middle, fresh)
