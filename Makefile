@@ -11,7 +11,7 @@ LIB := kelpie_amd/libkelpie_hip.so
 
 all: $(LIB)
 
-build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp include/kelpie_hip.h
+build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn_plan.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp include/kelpie_hip.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -69,4 +69,15 @@ build/san/batch_check_asan: tests/native/batch_check_driver.cpp kelpie_amd/csrc/
 	@mkdir -p build/san
 	$(CXX) -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
 
-.PHONY: asan tsan batch_asan
+# the attention planners (kp_attn_plan.hpp, no HIP) alone in tests/native/attn_plan_driver.cpp,
+# plain and under the host sanitizers; run by tests/test_attn_plan.py (CPU suite)
+attn_plan: build/san/attn_plan
+attn_plan_asan: build/san/attn_plan_asan
+build/san/attn_plan: tests/native/attn_plan_driver.cpp kelpie_amd/csrc/kp_attn_plan.hpp
+	@mkdir -p build/san
+	$(CXX) -O2 -std=c++17 -Wall $< -o $@
+build/san/attn_plan_asan: tests/native/attn_plan_driver.cpp kelpie_amd/csrc/kp_attn_plan.hpp
+	@mkdir -p build/san
+	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
+
+.PHONY: asan tsan batch_asan attn_plan attn_plan_asan

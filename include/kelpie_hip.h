@@ -361,6 +361,22 @@ int kp_rng_conve_masks_enqueue(uint8_t* torch_state, size_t torch_len, int32_t n
 int kp_last_timing(const kp_ctx* ctx, double* device_seconds, double* hot_kernel_seconds,
                    int64_t* hot_kernel_launches, double* hot_work_units);
 
+/* How many batches have their device work in flight at once, this context's next
+ * kp_posttrain_rank among them (n >= 1; 1, the default, is a batch that has the device
+ * to itself).  The reference has no counterpart: PostTrainingEngine runs one post-training
+ * at a time (post_training_engine.py:64-76).  A hint for the attention kernel's work
+ * partition only (ComplEx: with n >= 2 a query tile is cut into fewer key ranges, since
+ * other batches' workgroups fill what a launch leaves idle); results agree to rounding
+ * for every n.  The caller sets it before each kp_posttrain_rank whose neighbours it
+ * knows, and back to 1 afterwards. */
+int kp_ctx_set_inflight(kp_ctx* ctx, int n);
+
+/* The attention plan of the last kp_posttrain_rank's largest launch (ComplEx / ConvE;
+ * zeros otherwise): out[0] = the in-flight hint it was planned with, out[1] = key ranges
+ * per query tile (0: stream-K), out[2] = partial slots per query, out[3] = workgroups,
+ * out[4] = the launch's queries. */
+int kp_last_attn_plan(const kp_ctx* ctx, int32_t out[5]);
+
 /* [start, end] (seconds, on a time base shared by every context of the device) of
  * each dominant-kernel launch of the last kp_posttrain_rank: *n = the launch count,
  * the first min(cap, *n) pairs are written to out[2 i], out[2 i + 1].  With batches

@@ -28,7 +28,8 @@ EXPORTS = ["kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_posttrain_ran
            "kp_rng_transe_calls", "kp_train_epoch", "kp_read_tables", "kp_view_create", "kp_view_destroy",
            "kp_sched_batch_create", "kp_sched_batch_destroy", "kp_sched_add_calls", "kp_sched_pack",
            "kp_gather_i32", "kp_rng_transe_calls_async", "kp_rng_torch_take", "kp_conve_train_begin",
-           "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free"]
+           "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free", "kp_ctx_set_inflight",
+           "kp_last_attn_plan"]
 
 
 class ModelDesc(C.Structure):
@@ -111,6 +112,8 @@ def lib():
         L.kp_rng_conve_masks_enqueue.argtypes = L.kp_rng_conve_masks.argtypes
         L.kp_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+        L.kp_ctx_set_inflight.argtypes = [C.c_void_p, C.c_int]
+        L.kp_last_attn_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.kp_hot_intervals.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
         L.kp_version.restype = C.c_char_p
         L.kp_view_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
@@ -482,6 +485,17 @@ class Context:
         out = np.zeros((max(1, n.value), 2), np.float64)
         check(lib().kp_hot_intervals(self.h, n.value, _ptr(out), C.byref(n)), self.h)
         return out[:n.value]
+
+    def set_inflight(self, n: int):
+        """kp_ctx_set_inflight: batches in flight beside (and including) this context's next one."""
+        check(lib().kp_ctx_set_inflight(self.h, int(n)), self.h)
+
+    def last_attn_plan(self):
+        """kp_last_attn_plan: the attention plan of the last batch's largest launch."""
+        v = (C.c_int32 * 5)()
+        check(lib().kp_last_attn_plan(self.h, v), self.h)
+        return {"attn_inflight": v[0], "attn_ranges": v[1], "attn_parts": v[2], "attn_wg": v[3],
+                "attn_queries": v[4]}
 
     def last_timing(self):
         a, b, n, w = C.c_double(), C.c_double(), C.c_int64(), C.c_double()

@@ -139,6 +139,9 @@ int kp_ctx_create(int device, const kp_model_desc* m, kp_ctx** out) {
     if (const char* a = std::getenv("KP_TE_RANK")) c->te_rank64 = std::strcmp(a, "f32") != 0;
     if (const char* a = std::getenv("KP_ATTN_PART"))
       c->attn_part = std::strcmp(a, "streamk") == 0 ? 1 : std::strcmp(a, "ranges") == 0 ? 2 : 0;
+    // diagnostic: KP_ATTN_RANGES=S cuts every kp_attn3 query tile into S key ranges (1 .. 16,
+    // clamped to the key tiles) with one workgroup per unit, whatever the planner would choose
+    if (const char* a = std::getenv("KP_ATTN_RANGES")) c->attn_ranges = std::max(0, std::min(16, std::atoi(a)));
     KP_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     // the context's own workspaces grow stream-ordered on its stream (DevBuf), from the
     // library's private pool of the device, which keeps what they give back instead of
@@ -400,6 +403,23 @@ int kp_hot_intervals(const kp_ctx* c, int64_t cap, double* out, int64_t* n) {
     out[2 * i] = c->hot_iv[2 * i];
     out[2 * i + 1] = c->hot_iv[2 * i + 1];
   }
+  return KP_OK;
+}
+
+int kp_ctx_set_inflight(kp_ctx* c, int n) {
+  if (!c || n < 1) return KP_EINVAL;
+  c->attn_inflight = n;
+  return KP_OK;
+}
+
+int kp_last_attn_plan(const kp_ctx* c, int32_t out[5]) {
+  if (!c || !out) return KP_EINVAL;
+  const bool any = c->attn_last.nq >= 0;
+  out[0] = any ? c->attn_last.inflight : 0;
+  out[1] = any ? c->attn_last.ranges : 0;
+  out[2] = any ? c->attn_last.n_parts : 0;
+  out[3] = any ? c->attn_last.n_wg : 0;
+  out[4] = any ? c->attn_last.nq : 0;
   return KP_OK;
 }
 

@@ -7,6 +7,7 @@
 #endif
 #include <algorithm>
 
+#include "kp_attn_plan.hpp"
 #include "kp_common.hpp"
 
 namespace kpattn {
@@ -123,20 +124,7 @@ __device__ __forceinline__ float tied(float v) {
 enum { ATT_SOFTMAX_O = 0, ATT_SOFTMAX = 1, ATT_BCE_O = 2 };
 constexpr float kMargin = 40.0f;  // max exponent s - m_ref of a pass-1 weight (e^40 * N * |E| << FLT_MAX)
 
-// Work partition (stream-K style): the (64-query tile, 32-entity key tile) iterations
-// of all query tiles, in query-tile-major order, are cut into equal contiguous
-// ranges of per_wg iterations, one per workgroup, with exactly as many workgroups
-// as the GPU holds at once.  A workgroup's range covers key-tile segments of one or
-// more query tiles; each segment writes a partial (m, l, O) into slot `part` of its
-// query tile, and the owner of a tile's last segment fills the unused slots up to
-// n_parts with empty partials (m = -inf, l = 0, O = 0).  Consumers merge n_parts
-// partials per query exactly as they merged N-split partials.
-struct AttnWork {
-  int ktq;      // key tiles per query tile, ceil(n_ent / 32)
-  int per_wg;   // iterations per workgroup (stream-K)
-  int n_parts;  // partial slots per query
-  int ranges;   // > 0: XCD-grouped aligned key ranges (kp_attn3 only; attn_plan_ranges)
-};
+// The work partition (AttnWork, AttnPlan) and its planners: kp_attn_plan.hpp
 
 template <int DB, int MODE>
 __global__ __launch_bounds__(256, 1) void kp_attn(const float* __restrict__ E, int n_ent,
@@ -413,64 +401,6 @@ __global__ __launch_bounds__(256, 1) void kp_attn(const float* __restrict__ E, i
   }
   it += kt1 - kt0;
   }
-}
-
-// Host: the stream-K partition for nq queries over n_ent keys on `slots` co-resident
-// workgroups.  A workgroup takes at least ktq/15 key tiles, so a query tile is cut
-// into at most 16 partials (the consumers' merge limit).
-struct AttnPlan {
-  AttnWork wk;
-  int n_wg;
-};
-inline AttnPlan attn_plan(int nq, int n_ent, int slots) {
-  const int QT = (nq + 63) / 64, ktq = (n_ent + 31) / 32;
-  const long long total = (long long)QT * ktq;
-  long long per = (total + slots - 1) / slots;
-  per = std::max<long long>(per, (ktq + 14) / 15);
-  per = std::max<long long>(per, 1);
-  AttnPlan p{};
-  p.n_wg = (int)((total + per - 1) / per);
-  p.wk.ktq = ktq;
-  p.wk.per_wg = (int)per;
-  int parts = 1;
-  for (int qt = 0; qt < QT; ++qt) {
-    const long long w0 = ((long long)qt * ktq) / per, w1 = ((long long)(qt + 1) * ktq - 1) / per;
-    parts = std::max(parts, (int)(w1 - w0 + 1));
-  }
-  p.wk.n_parts = parts;
-  return p;
-}
-
-// Host: the XCD-grouped partition of kp_attn3.  The key tiles are cut into S aligned
-// ranges; a unit is (query tile, range), numbered range-major, so consecutive units
-// read the same keys.  Workgroup b (placed on XCD b % 8 by the dispatcher; used for
-// speed only) takes logical id L = (b % 8) * (n_wg / 8) + b / 8 and units L, L + n_wg,
-// ...: the workgroups of one XCD run consecutive units at the same time, so one key
-// range streams into that XCD's L2 once and serves up to 32 query tiles, where the
-// stream-K ranges of different workgroups are unrelated and every query tile re-reads
-// the table from the Infinity Cache.  S minimises rounds x (range length + a per-unit
-// overhead), at most 16 (the consumers' merge limit); every (query, range) partial is
-// written.
-inline AttnPlan attn_plan_ranges(int nq, int n_ent, int slots) {
-  const int QT = (nq + 63) / 64, ktq = (n_ent + 31) / 32;
-  const int n_wg = std::max(8, slots / 8 * 8);
-  int best_s = 1;
-  long long best = -1;
-  for (int S = 1; S <= std::min(16, ktq); ++S) {
-    const long long rounds = ((long long)QT * S + n_wg - 1) / n_wg;
-    const long long cost = rounds * ((ktq + S - 1) / S + 2);
-    if (best < 0 || cost < best) {
-      best = cost;
-      best_s = S;
-    }
-  }
-  AttnPlan p{};
-  p.wk.ktq = ktq;
-  p.wk.per_wg = 0;
-  p.wk.n_parts = best_s;
-  p.wk.ranges = best_s;
-  p.n_wg = (int)std::min<long long>(n_wg, ((long long)QT * best_s + 7) / 8 * 8);
-  return p;
 }
 
 // LDS bytes of kp_attn<DB, *>

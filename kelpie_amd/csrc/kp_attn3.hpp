@@ -1097,26 +1097,29 @@ int attn3_wpc(kp_ctx* c) {
   return slot;
 }
 
-// Host: the partition of the context's attention kernel.  kp_attn3 takes the XCD-grouped
-// aligned ranges unless their quantisation costs more than 40 % over stream-K's
-// balanced split: the L2 reuse they buy (FETCH_SIZE 14x lower, L2 hit rate 2 -> 91 %)
-// outweighs a worse balance.  KP_ATTN_PART=streamk
-// forces stream-K, KP_ATTN_PART=ranges the ranges (parity tests run both).  The fp32
-// kp_attn always uses stream-K.
-inline AttnPlan attn_plan_ctx(const kp_ctx* c, int nq, int n_ent, int slots) {
-  const AttnPlan sk = attn_plan(nq, n_ent, slots);
-  if (c->attn_mode != 1 || c->attn_part == 1) return sk;
-  const AttnPlan r = attn_plan_ranges(nq, n_ent, slots);
-  if (c->attn_part == 2) return r;
-  const long long QT = (nq + 63) / 64, S = r.wk.ranges, ktq = r.wk.ktq;
-  const long long n_wg = std::max(8, slots / 8 * 8);
-  const long long cost_r = (QT * S + n_wg - 1) / n_wg * ((ktq + S - 1) / S + 2);
-  const long long cost_sk = (long long)sk.wk.per_wg + 2;
-  // measured on the interleaved kernel (tools/attn_micro.hip, FB15k-237 ComplEx, nq 800 -
-  // 5,000): the ranges ran 9-21 % faster than stream-K at every size although their
-  // quantisation was up to 25 % worse (profiles/r02o_attn_partition.jsonl)
-  (void)n_ent;
-  return 100 * cost_r <= 140 * cost_sk ? r : sk;
+// A/B switch (make diag): 1 lets the ConvE attention follow the in-flight hint too
+#ifndef KP_CV_ATTN_INFLIGHT
+#define KP_CV_ATTN_INFLIGHT 0
+#endif
+
+// Host: the partition of the context's attention kernel (attn_plan_select, kp_attn_plan.hpp).
+// KP_ATTN_PART=streamk forces stream-K, KP_ATTN_PART=ranges the ranges (parity tests run
+// both), KP_ATTN_RANGES=S that many ranges with one workgroup per unit.  `inflight_ok`:
+// the caller's launches follow the context's in-flight hint (kp_ctx_set_inflight); false
+// keeps the plan of a launch that runs alone.  The fp32 kp_attn always uses stream-K.
+inline AttnPlan attn_plan_ctx(const kp_ctx* c, int nq, int n_ent, int slots, bool inflight_ok) {
+  if (c->attn_mode != 1) return attn_plan(nq, n_ent, slots);
+  return attn_plan_select(c->attn_part, inflight_ok ? c->attn_inflight : 1, c->attn_ranges, nq, n_ent, slots);
+}
+
+// Host: records the plan of a batch's largest hot launch for kp_last_attn_plan.
+inline void attn_plan_note(kp_ctx* c, const AttnPlan& p, int nq, bool inflight_ok) {
+  if (nq < c->attn_last.nq) return;
+  c->attn_last.nq = nq;
+  c->attn_last.inflight = (c->attn_mode == 1 && inflight_ok) ? c->attn_inflight : 1;
+  c->attn_last.ranges = p.wk.ranges;
+  c->attn_last.n_parts = p.wk.n_parts;
+  c->attn_last.n_wg = p.n_wg;
 }
 
 template <int DB, int MODE>

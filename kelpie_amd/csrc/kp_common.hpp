@@ -229,6 +229,11 @@ struct kp_ctx : ImageBufs {
   // attention contraction: 0 = fp32 MFMA (kp_attn.hpp), 1 = bf16x3 MFMA (kp_attn3.hpp)
   int attn_mode = 0;
   int attn_part = 0;  // kp_attn3 partition: 0 chosen per launch, 1 stream-K, 2 XCD-grouped ranges (KP_ATTN_PART)
+  int attn_inflight = 1;  // batches whose attention launches share the device (kp_ctx_set_inflight)
+  int attn_ranges = 0;    // > 0: kp_attn3 runs that many ranges, one workgroup per unit (KP_ATTN_RANGES)
+  struct AttnLast {       // plan of the last batch's largest hot attention launch (kp_last_attn_plan)
+    int nq = -1, inflight = 1, ranges = 0, n_parts = 0, n_wg = 0;
+  } attn_last;
   bool e3_ready = false;     // ImageBufs::e3
   bool e3pre_ready = false;  // e3ts, e3pre
   bool eT_ready = false;

@@ -1007,9 +1007,13 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   }
   std::vector<AttnPlan> step_plan(T);
   size_t o_rows = 1;
+  c->attn_last = {};
   for (int t = 0; t < T; ++t) {
     const int nk = kin_off[t + 1] - kin_off[t];
-    step_plan[t] = attn_plan_ctx(c, std::max(nk, 1), K, attn_slots);
+    // the ConvE attention (ATT_BCE_O, two workgroups per CU) keeps the plan of a launch that
+    // runs alone whatever the context's in-flight hint says
+    step_plan[t] = attn_plan_ctx(c, std::max(nk, 1), K, attn_slots, KP_CV_ATTN_INFLIGHT != 0);
+    if (nk > 0) attn_plan_note(c, step_plan[t], nk, KP_CV_ATTN_INFLIGHT != 0);
     o_rows = std::max(o_rows, (size_t)nk * step_plan[t].wk.n_parts);
   }
   float* dO = reinterpret_cast<float*>(c->cv.o.ensure(sizeof(float) * o_rows * DP));

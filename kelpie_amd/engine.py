@@ -640,6 +640,8 @@ class PostTrainingEngine(RelevanceEngine):
             stats["_score"], stats["_rank"] = np.array(score), np.array(rank)
         if hasattr(ctx, "hot_intervals"):
             stats["hot_iv"] = ctx.hot_intervals()
+        if hasattr(ctx, "last_attn_plan"):
+            stats.update(ctx.last_attn_plan())
         self.last_batch_stats = stats
         return stats
 
@@ -800,7 +802,11 @@ class PostTrainingEngine(RelevanceEngine):
         batches are in flight, each on its own device context
         (``FrozenModel.contexts``: own stream and workspaces over a replica of the
         frozen tables), so one batch's library-side planning, uploads and result
-        download overlap the other's kernels instead of leaving the device idle."""
+        download overlap the other's kernels instead of leaving the device idle.  A batch
+        with a predecessor and a successor in this call tells its context that ``depth``
+        batches share the device (``kp_ctx_set_inflight``: the attention then cuts its query
+        tiles into fewer key ranges); the first and last batch, which run partly alone, and
+        every other path leave the hint at 1."""
         import collections
         import os
         import threading
@@ -878,7 +884,17 @@ class PostTrainingEngine(RelevanceEngine):
                 # this batch's deferred draws (the scheduling thread did not wait for them)
                 _rng_mod.wait_ticket(state.get("ticket"))
                 tr("draws", b)
-                state["stats"] = dict(self._run(state["slots"], ctx=state["ctx"]))
+                # the attention planner's hint (kp_ctx_set_inflight): a batch between two others
+                # of this call shares the device with depth - 1 of them from start to end
+                hint = state.get("inflight", 1)
+                if hint > 1 and hasattr(state["ctx"], "set_inflight"):
+                    state["ctx"].set_inflight(hint)
+                    try:
+                        state["stats"] = dict(self._run(state["slots"], ctx=state["ctx"]))
+                    finally:
+                        state["ctx"].set_inflight(1)
+                else:
+                    state["stats"] = dict(self._run(state["slots"], ctx=state["ctx"]))
                 tr("ran", b)
             except BaseException as e:  # re-raised on the scheduling thread
                 state["error"] = e
@@ -913,6 +929,7 @@ class PostTrainingEngine(RelevanceEngine):
         lookahead = max(0, int(os.environ.get("KELPIE_PIPELINE_LOOKAHEAD", "0")))
         ready = collections.deque()
         todo = iter(enumerate(batches))
+        n_batches = len(batches) if hasattr(batches, "__len__") else None  # unknown: no batch is "between"
         stop = False
 
         def schedule_next():
@@ -952,6 +969,7 @@ class PostTrainingEngine(RelevanceEngine):
                 done = []
             state = ready.popleft()
             state["ctx"] = ctxs[state["b"] % len(ctxs)]
+            state["inflight"] = len(ctxs) if n_batches is not None and 0 < state["b"] < n_batches - 1 else 1
             ci = state["b"] % len(ctxs)
             if not use_workers:  # KELPIE_PIPELINE_WORKERS=0: a thread per batch (A/B)
                 state["thread"] = threading.Thread(target=run, args=(state,), daemon=True)

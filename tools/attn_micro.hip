@@ -3,6 +3,14 @@
 // different defines (tools/attn_micro.sh).  Not part of the product library.
 //
 //   attn_micro <DB 25|13> <mode 0|2> <n_ent> <nq> <iters> [scale] [part 0|1|2]
+//              [--ranges S] [--inflight N] [--streams K]
+//
+// --ranges S: S key ranges per query tile, one workgroup per unit (the library's
+// KP_ATTN_RANGES); --inflight N: the planner's in-flight hint (kp_ctx_set_inflight).
+// --streams K: K contexts, each on its own stream with its own partials, launch the kernel
+// back to back, each launch followed by a short dependent kernel that reads the partials
+// once (it stands in for the merge, its work proportional to the ranges like the merge's);
+// "ms" is then the union time per launch, host time over all launches / (K x iters).
 //
 // Prints one JSON line: per-launch ms (HIP events around `iters` back-to-back launches),
 // fp32-equivalent TF/s (4 D per (query, entity) with O, 2 D without), and the largest
@@ -10,6 +18,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <algorithm>
 #include <chrono>
 #include <random>
@@ -124,8 +133,28 @@ __global__ __launch_bounds__(256, 1) void kp_empty(int* sink) {
   if (threadIdx.x == 1023) sink[blockIdx.x] = lds_e[0];
 }
 
+// --streams: the merge's stand-in, one thread per four dimensions of a query sums the
+// launch's `parts` O partials ([parts][nq][dp]) into out ([nq][dp])
+__global__ void kp_micro_merge(const float* __restrict__ O, long long n4, int parts, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int p = 0; p < parts; ++p) {
+    const float4 v = reinterpret_cast<const float4*>(O)[(size_t)p * n4 + i];
+    a.x += v.x;
+    a.y += v.y;
+    a.z += v.z;
+    a.w += v.w;
+  }
+  reinterpret_cast<float4*>(out)[i] = a;
+}
+
+struct MicroOpt {
+  int ranges = 0, inflight = 1, streams = 0;
+};
+
 template <int DB, int MODE>
-static int run(int n_ent, int nq, int iters, float scale, int part) {
+static int run(int n_ent, int nq, int iters, float scale, int part, MicroOpt opt) {
   constexpr int DP = 16 * DB;
   kp_ctx c;
   KP_HIP(hipStreamCreate(&c.stream));
@@ -136,6 +165,8 @@ static int run(int n_ent, int nq, int iters, float scale, int part) {
   c.dp = DP;
   c.attn_mode = 1;
   c.attn_part = part;
+  c.attn_ranges = opt.ranges;
+  c.attn_inflight = opt.inflight;
   std::mt19937 gen(1234);
   std::normal_distribution<float> nd(0.f, 1.f);
   std::vector<float> E((size_t)n_ent * DP, 0.f), Q((size_t)nq * DP, 0.f), qs(nq);
@@ -161,7 +192,7 @@ static int run(int n_ent, int nq, int iters, float scale, int part) {
   use5 = false;
   const int slots = c.n_cu * attn3_wpc<DB, MODE == ATT_BCE_O ? ATT_BCE_O : ATT_SOFTMAX_O>(&c);
 #endif
-  const AttnPlan plan = attn_plan_ctx(&c, nq, n_ent, slots);
+  const AttnPlan plan = attn_plan_ctx(&c, nq, n_ent, slots, true);
   const int parts = plan.wk.n_parts;
   float *dm, *dl, *dO;
   KP_HIP(hipMalloc(&dm, (size_t)parts * nq * 4));
@@ -305,25 +336,70 @@ static int run(int n_ent, int nq, int iters, float scale, int part) {
   }
   launch();
   KP_HIP(hipStreamSynchronize(c.stream));
-  hipEvent_t e0, e1;
-  KP_HIP(hipEventCreate(&e0));
-  KP_HIP(hipEventCreate(&e1));
-  // >= 1 s of back-to-back launches first: the first ~10 ms of work after the GPU leaves
-  // idle run below the settled clock (profiles/r03zx_attn_warm_vs_spans.jsonl)
-  {
-    const auto w0 = std::chrono::steady_clock::now();
-    while (std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count() < 1.0) {
-      for (int i = 0; i < 20; ++i) launch();
-      KP_HIP(hipStreamSynchronize(c.stream));
-    }
-  }
-  KP_HIP(hipEventRecord(e0, c.stream));
-  for (int i = 0; i < iters; ++i) launch();
-  KP_HIP(hipEventRecord(e1, c.stream));
-  KP_HIP(hipEventSynchronize(e1));
   float ms = 0.f;
-  KP_HIP(hipEventElapsedTime(&ms, e0, e1));
-  ms /= iters;
+  if (opt.streams > 0) {
+    // K contexts as the pipeline has them: own stream, own image of the table, own partials
+    const int K = opt.streams;
+    const long long n4 = (long long)nq * DP / 4;
+    std::vector<kp_ctx> cs(K);
+    std::vector<float*> sm(K), sl(K), sO(K), sout(K);
+    for (int k = 0; k < K; ++k) {
+      KP_HIP(hipStreamCreateWithFlags(&cs[k].stream, hipStreamNonBlocking));
+      cs[k].n_cu = c.n_cu;
+      cs[k].n_ent = n_ent;
+      cs[k].dp = DP;
+      cs[k].attn_mode = 1;
+      cs[k].dE = c.dE;
+      KP_HIP(hipMalloc(&sm[k], (size_t)parts * nq * 4));
+      KP_HIP(hipMalloc(&sl[k], (size_t)parts * nq * 4));
+      KP_HIP(hipMalloc(&sO[k], (size_t)parts * nq * DP * 4));
+      KP_HIP(hipMalloc(&sout[k], (size_t)nq * DP * 4));
+    }
+    auto round = [&]() {
+      for (int k = 0; k < K; ++k) {
+        launch_attn3<DB, MODE>(&cs[k], n_ent, dQ, nq, plan, sm[k], sl[k], sO[k], dqs, ylo);
+        hipLaunchKernelGGL(kp_micro_merge, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, cs[k].stream, sO[k], n4,
+                           parts, sout[k]);
+      }
+    };
+    auto sync_all = [&]() {
+      for (int k = 0; k < K; ++k) KP_HIP(hipStreamSynchronize(cs[k].stream));
+    };
+    {
+      const auto w0 = std::chrono::steady_clock::now();
+      while (std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count() < 1.0) {
+        for (int i = 0; i < 10; ++i) round();
+        sync_all();
+      }
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < iters; ++i) round();
+    sync_all();
+    ms = (float)(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / ((double)iters * K));
+    // the checked and hashed outputs below: stream 0's partials
+    KP_HIP(hipMemcpy(dm, sm[0], (size_t)parts * nq * 4, hipMemcpyDeviceToDevice));
+    KP_HIP(hipMemcpy(dl, sl[0], (size_t)parts * nq * 4, hipMemcpyDeviceToDevice));
+    KP_HIP(hipMemcpy(dO, sO[0], (size_t)parts * nq * DP * 4, hipMemcpyDeviceToDevice));
+  } else {
+    hipEvent_t e0, e1;
+    KP_HIP(hipEventCreate(&e0));
+    KP_HIP(hipEventCreate(&e1));
+    // >= 1 s of back-to-back launches first: the first ~10 ms of work after the GPU leaves
+    // idle run below the settled clock (profiles/r03zx_attn_warm_vs_spans.jsonl)
+    {
+      const auto w0 = std::chrono::steady_clock::now();
+      while (std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count() < 1.0) {
+        for (int i = 0; i < 20; ++i) launch();
+        KP_HIP(hipStreamSynchronize(c.stream));
+      }
+    }
+    KP_HIP(hipEventRecord(e0, c.stream));
+    for (int i = 0; i < iters; ++i) launch();
+    KP_HIP(hipEventRecord(e1, c.stream));
+    KP_HIP(hipEventSynchronize(e1));
+    KP_HIP(hipEventElapsedTime(&ms, e0, e1));
+    ms /= iters;
+  }
   std::vector<float> hm((size_t)parts * nq), hl((size_t)parts * nq), hO((size_t)parts * nq * DP);
   if (MODE != ATT_BCE_O) {
     KP_HIP(hipMemcpy(hm.data(), dm, hm.size() * 4, hipMemcpyDeviceToHost));
@@ -454,24 +530,39 @@ static int run(int n_ent, int nq, int iters, float scale, int part) {
            "\"warm_launches\": %d}\n", med, f.empty() ? 0.0 : f.front(), f.empty() ? 0.0 : f.back(), f.size(), warm);
   }
 #endif
-  printf("{\"kernel\": \"%s\", \"DB\": %d, \"mode\": %d, \"n_ent\": %d, \"nq\": %d, \"parts\": %d, \"ranges\": %d, \"n_wg\": %d, "
+  printf("{\"kernel\": \"%s\", \"DB\": %d, \"mode\": %d, \"n_ent\": %d, \"nq\": %d, \"parts\": %d, \"ranges\": %d, \"n_wg\": %d, \"streams\": %d, "
          "\"ms\": %.5f, \"tflops\": %.2f, \"frac_bf16x6\": %.4f, \"err_l\": %.3e, \"err_o\": %.3e, \"bits\": \"%016llx\"}\n",
-         use5 ? "kp_attn5" : "kp_attn3", DB, MODE, n_ent, nq, parts, plan.wk.ranges, plan.n_wg, ms, flops / ms / 1e9, flops / ms / 1e9 / 419.43,
+         use5 ? "kp_attn5" : "kp_attn3", DB, MODE, n_ent, nq, parts, plan.wk.ranges, plan.n_wg, opt.streams, ms, flops / ms / 1e9, flops / ms / 1e9 / 419.43,
          err_l, err_o, bits);
   return 0;
 }
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    fprintf(stderr, "usage: attn_micro DB mode n_ent nq iters [scale] [part]\n");
+    fprintf(stderr, "usage: attn_micro DB mode n_ent nq iters [scale] [part] [--ranges S] [--inflight N] [--streams K]\n");
     return 2;
   }
   const int DB = atoi(argv[1]), mode = atoi(argv[2]), n_ent = atoi(argv[3]), nq = atoi(argv[4]), iters = atoi(argv[5]);
-  const float scale = argc > 6 ? (float)atof(argv[6]) : 0.05f;
-  const int part = argc > 7 ? atoi(argv[7]) : 0;
+  MicroOpt opt;
+  int npos = argc;
+  for (int i = 6; i < argc; ++i)
+    if (argv[i][0] == '-' && argv[i][1] == '-') {
+      npos = std::min(npos, i);
+      const int v = i + 1 < argc ? atoi(argv[i + 1]) : 0;
+      if (!strcmp(argv[i], "--ranges")) opt.ranges = std::max(0, std::min(16, v));
+      else if (!strcmp(argv[i], "--inflight")) opt.inflight = std::max(1, v);
+      else if (!strcmp(argv[i], "--streams")) opt.streams = std::max(0, std::min(8, v));
+      else {
+        fprintf(stderr, "unknown option %s\n", argv[i]);
+        return 2;
+      }
+      ++i;
+    }
+  const float scale = npos > 6 ? (float)atof(argv[6]) : 0.05f;
+  const int part = npos > 7 ? atoi(argv[7]) : 0;
   try {
-    if (DB == 25 && mode == 0) return run<25, ATT_SOFTMAX_O>(n_ent, nq, iters, scale, part);
-    if (DB == 13 && mode == 2) return run<13, ATT_BCE_O>(n_ent, nq, iters, scale, part);
+    if (DB == 25 && mode == 0) return run<25, ATT_SOFTMAX_O>(n_ent, nq, iters, scale, part, opt);
+    if (DB == 13 && mode == 2) return run<13, ATT_BCE_O>(n_ent, nq, iters, scale, part, opt);
     fprintf(stderr, "unsupported DB/mode\n");
     return 2;
   } catch (const KpError& e) {
