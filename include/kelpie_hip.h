@@ -46,6 +46,12 @@ extern "C" {
 #define KP_MODEL_TRANSE 0
 #define KP_MODEL_COMPLEX 1
 #define KP_MODEL_CONVE 2
+/* DistMult (src/link_prediction/models/distmult.py:38-68; the reference leaves it out of its
+ * registry): plain [d] float rows, score (lhs * rel) . rhs, maximizer, post-trained by the
+ * ComplEx optimizer (multiclass_nll_optimizer.py:57-164).  Rows of at most 400 floats;
+ * kp_posttrain_rank, kp_all_scores, kp_convertible and kp_predict_tails serve it,
+ * kp_train_epoch, kp_dp_relevance and kp_criage_relevance do not. */
+#define KP_MODEL_DISTMULT 3
 
 /* optimizers (multiclass_nll_optimizer.py:41-48; Kelpie TransE / ConvE use Adam) */
 #define KP_OPT_ADAGRAD 0
@@ -61,7 +67,7 @@ typedef struct {
   int32_t model;      /* KP_MODEL_* */
   int32_t n_ent;      /* |E| */
   int32_t n_rel2;     /* 2|R| */
-  int32_t dim;        /* row width: TransE/ConvE d, ComplEx 2d ([Re | Im], complex.py:24-25) */
+  int32_t dim;        /* row width: TransE/ConvE/DistMult d, ComplEx 2d ([Re | Im], complex.py:24-25) */
   const float* entity;   /* [n_ent][dim] */
   const float* relation; /* [n_rel2][dim] */
   /* ConvE frozen layers (conve.py:40-52, frozen copies at :214-237); NULL otherwise */
@@ -85,7 +91,7 @@ typedef struct {
   float lr;              /* ConvE: 1e-3 (KelpieBCEOptimizer ignores hp lr, bce_optimizer.py:165) */
   float beta1, beta2;    /* Adam betas */
   float eps;             /* Adagrad 1e-10, Adam 1e-8 */
-  float reg_weight;      /* ComplEx N3 weight / TransE L2 weight */
+  float reg_weight;      /* ComplEx / DistMult N3 (N2) weight / TransE L2 weight */
   float margin;          /* TransE */
   int32_t neg_ratio;     /* TransE negative_triples_ratio */
   float label_smoothing; /* ConvE */

@@ -7,7 +7,7 @@ inner loop); the arithmetic runs in the gfx950 HIP library libkelpie_hip.so
 """
 from .data import Dataset, KelpieView  # noqa: F401
 from .engine import NecessaryPostTrainingEngine, PostTrainingEngine, SufficientPostTrainingEngine  # noqa: F401
-from .models import MODEL_REGISTRY, ComplEx, ConvE, TransE, from_state_dict  # noqa: F401
+from .models import MODEL_REGISTRY, ComplEx, ConvE, DistMult, TransE, from_state_dict  # noqa: F401
 from .builder import StochasticBuilder  # noqa: F401
 from .prefilters import NoPreFilter, TopologyPreFilter, WeightedTopologyPreFilter  # noqa: F401
 from .baselines import (CriagePreFilter, NecessaryCriageEngine, NecessaryDPEngine, SufficientCriageEngine,  # noqa: F401

@@ -15,7 +15,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KELPIE_HIP_LIB", os.path.join(_HERE, "libkelpie_hip.so"))
 
-KP_MODEL = {"TransE": 0, "ComplEx": 1, "ConvE": 2}
+KP_MODEL = {"TransE": 0, "ComplEx": 1, "ConvE": 2, "DistMult": 3}
 KP_INLINE = 1  # kp_rng_transe_calls_async walked inline (include/kelpie_hip.h)
 KP_OPT = {"Adagrad": 0, "Adam": 1, "SGD": 2}
 

@@ -19,7 +19,7 @@ import numpy as np
 
 from .data import Dataset
 from .engine import NecessaryPostTrainingEngine, SufficientPostTrainingEngine
-from .models import ComplEx, ConvE, TransE
+from .models import ComplEx, ConvE, DistMult, TransE
 
 
 def _np(t):
@@ -38,6 +38,8 @@ def model_from_reference(ref_model, dataset: Dataset, device=0):
     E, R = _np(ref_model.entity_embeddings), _np(ref_model.relation_embeddings)
     if name == "ComplEx":
         return ComplEx(dataset, E, R, init_scale=ref_model.init_scale, device=device)
+    if name == "DistMult":
+        return DistMult(dataset, E, R, init_scale=ref_model.init_scale, device=device)
     if name == "TransE":
         return TransE(dataset, E, R, norm=ref_model.norm, device=device)
     if name == "ConvE":

@@ -96,7 +96,7 @@ int kp_ctx_create(int device, const kp_model_desc* m, kp_ctx** out) {
   int rc = guarded(nullptr, [&] {
     KP_REQUIRE(m->n_ent > 0 && m->n_rel2 > 0 && m->dim > 0, "kp_ctx_create: empty model");
     KP_REQUIRE(m->entity && m->relation, "kp_ctx_create: missing tables");
-    KP_REQUIRE(m->model >= KP_MODEL_TRANSE && m->model <= KP_MODEL_CONVE, "kp_ctx_create: unknown model");
+    KP_REQUIRE(m->model >= KP_MODEL_TRANSE && m->model <= KP_MODEL_DISTMULT, "kp_ctx_create: unknown model");
     c->device = device;
     c->model = m->model;
     c->n_ent = m->n_ent;
@@ -112,6 +112,12 @@ int kp_ctx_create(int device, const kp_model_desc* m, kp_ctx** out) {
       KP_REQUIRE(m->model != KP_MODEL_COMPLEX || m->dim % 2 == 0, "ComplEx: row width must be even ([Re | Im])");
       int db = cx_pick_db(m->dim);
       KP_REQUIRE(db > 0, "row width > 400 not supported yet for ComplEx / ConvE");
+      c->dp = 16 * db;
+    } else if (m->model == KP_MODEL_DISTMULT) {
+      // the ComplEx step on plain rows (kp_complex.hip): the same padded widths; the ConvE
+      // pointers of the descriptor are ignored
+      int db = cx_pick_db(m->dim);
+      if (db <= 0) throw KpError{KP_ENOTSUP, "DistMult: row width > 400 not supported"};
       c->dp = 16 * db;
     } else {
       c->dp = round_up(m->dim, 16);
@@ -206,6 +212,7 @@ int kp_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b) {
     KP_HIP(hipSetDevice(c->device));
     switch (c->model) {
       case KP_MODEL_COMPLEX: complex_posttrain_rank(c, hp, b); break;
+      case KP_MODEL_DISTMULT: distmult_posttrain_rank(c, hp, b); break;
       case KP_MODEL_TRANSE: transe_posttrain_rank(c, hp, b); break;
       case KP_MODEL_CONVE: conve_posttrain_rank(c, hp, b); break;
     }
@@ -221,7 +228,8 @@ int kp_all_scores(kp_ctx* c, int32_t n, const int32_t* heads, const int32_t* rel
       KP_REQUIRE(rels[i] >= 0 && rels[i] < c->n_rel2, "kp_all_scores: relation out of range");
     }
     switch (c->model) {
-      case KP_MODEL_COMPLEX: complex_all_scores(c, n, heads, rels, out); break;
+      case KP_MODEL_COMPLEX:
+      case KP_MODEL_DISTMULT: complex_all_scores(c, n, heads, rels, out); break;
       case KP_MODEL_TRANSE: transe_all_scores(c, n, heads, rels, out); break;
       case KP_MODEL_CONVE: conve_all_scores(c, n, heads, rels, out); break;
     }
@@ -254,7 +262,8 @@ int kp_convertible(kp_ctx* c, int32_t n, const int32_t* heads, int32_t rel, int3
       int32_t* dF = upload(c, bF, filt + filt_off[i0], (size_t)std::max(1, fo[m]));
       uint8_t* dK = reinterpret_cast<uint8_t*>(bK.ensure((size_t)m));
       switch (c->model) {
-        case KP_MODEL_COMPLEX: complex_scores_dev(c, m, dH, dR, dS, ld); break;
+        case KP_MODEL_COMPLEX:
+        case KP_MODEL_DISTMULT: complex_scores_dev(c, m, dH, dR, dS, ld); break;
         case KP_MODEL_TRANSE: transe_scores_dev(c, m, dH, dR, dS, ld); break;
         case KP_MODEL_CONVE: conve_scores_dev(c, m, dH, dR, dS, ld); break;
       }
@@ -356,7 +365,8 @@ int kp_predict_tails(kp_ctx* c, int32_t n, const int32_t* triples, const int32_t
       float* dT = reinterpret_cast<float*>(bT.ensure(sizeof(float) * (size_t)m));
       int64_t* dK = reinterpret_cast<int64_t*>(bK.ensure(sizeof(int64_t) * (size_t)m));
       switch (c->model) {
-        case KP_MODEL_COMPLEX: complex_scores_dev(c, m, dH, dR, dS, ld); break;
+        case KP_MODEL_COMPLEX:
+        case KP_MODEL_DISTMULT: complex_scores_dev(c, m, dH, dR, dS, ld); break;
         case KP_MODEL_TRANSE: transe_scores_dev(c, m, dH, dR, dS, ld); break;
         case KP_MODEL_CONVE: conve_scores_dev(c, m, dH, dR, dS, ld); break;
       }

@@ -314,8 +314,10 @@ __device__ __forceinline__ float wave_max(float v) {
 // entry points implemented per model family
 // ----------------------------------------------------------------------------
 void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b);
+void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b);  // kp_complex.hip, product policy
 void complex_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rels, float* out);
 // scores of n (head, rel) pairs over the frozen entities into a device buffer [n][ld]
+// (complex_*: ComplEx and DistMult contexts, by the context's product)
 void complex_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* d_rels, float* d_out, int ld);
 void transe_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* d_rels, float* d_out, int ld);
 void conve_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* d_rels, float* d_out, int ld);

@@ -23,6 +23,10 @@
 //   When R <= batch_size (one step per epoch) the permutation only reorders
 //   the batch, so every epoch reuses one plan; otherwise each (epoch, step)
 //   gets its own plan from the permutation.
+//
+// DistMult (src/link_prediction/models/distmult.py:38-68, same optimizer) is the same step
+// with the real product q = x * r on plain [d] rows: the kernels and the host function are
+// written over a product policy (CxProd / DmProd below), and only the policy differs.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -46,8 +50,78 @@ struct CxTail {
   int pair, c;
 };
 
+// the ComplEx product from exact fp64 products of the fp32 operands (kp_cx_rankq64)
+__device__ __forceinline__ double cx_q64(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
+                                         int half) {
+  if (d < half) return (double)lhs[d] * (double)rel[d] - (double)lhs[d + half] * (double)rel[d + half];
+  if (d < 2 * half) {
+    const int i = d - half;
+    return (double)lhs[i] * (double)rel[d] + (double)lhs[d] * (double)rel[i];
+  }
+  return 0.0;
+}
+
+// ----------------------------------------------------------------------------
+// Product policies.  The kernels below are written once over the model's product
+// q = lhs o rel; a policy holds its fp32 and fp64 forms, the Jacobian J_rel^T applied in
+// the contribution, and the regulariser modulus.  `w` is the policy's extent of a row:
+// the complex width d / 2 for ComplEx (rows [Re | Im]), the row width d for DistMult.
+// A row is G runs of w coordinates; coordinate i of run h is element i + h * w, and the
+// G elements of one i form one regulariser factor.
+// ----------------------------------------------------------------------------
+struct CxProd {  // ComplEx (complex.py:59-112)
+  static constexpr int G = 2;
+  static constexpr const char* name = "ComplEx";
+  static int extent(int dim) { return dim / 2; }
+  static __device__ __forceinline__ float q(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
+                                            int w) {
+    return cx_q(lhs, rel, d, w);
+  }
+  static __device__ __forceinline__ double q64(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
+                                               int w) {
+    return cx_q64(lhs, rel, d, w);
+  }
+  // the factor of one (re, im) pair: the complex modulus (complex.py:80-84)
+  static __device__ __forceinline__ float mod(const float* xv) { return sqrtf(xv[0] * xv[0] + xv[1] * xv[1]); }
+  static __device__ __forceinline__ double mod64(const float* xv) {
+    return sqrt((double)xv[0] * xv[0] + (double)xv[1] * xv[1]);
+  }
+  // out = J_r^T dv + cf q at coordinate i:  J_r^T (u, v) = (u c + v e, -u e + v c)
+  static __device__ __forceinline__ void emit(float* __restrict__ out, int i, int w, const double* xv,
+                                              const double* rv, const double* dv, double cf) {
+    const double a = xv[0], b = xv[1], cc = rv[0], ee = rv[1];
+    const double dre = dv[0], dim_ = dv[1];
+    const double qre = a * cc - b * ee, qim = a * ee + b * cc;
+    out[i] = (float)(dre * cc + dim_ * ee + cf * qre);
+    out[i + w] = (float)(-dre * ee + dim_ * cc + cf * qim);
+  }
+};
+
+struct DmProd {  // DistMult (distmult.py:38-68): plain [d] rows, q = lhs * rel
+  static constexpr int G = 1;
+  static constexpr const char* name = "DistMult";
+  static int extent(int dim) { return dim; }
+  static __device__ __forceinline__ float q(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
+                                            int w) {
+    return d < w ? __fmul_rn(lhs[d], rel[d]) : 0.f;
+  }
+  static __device__ __forceinline__ double q64(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
+                                               int w) {
+    return d < w ? (double)lhs[d] * (double)rel[d] : 0.0;
+  }
+  // the factor of one coordinate: |x_i| (distmult.py:66, sqrt(x_i^2))
+  static __device__ __forceinline__ float mod(const float* xv) { return fabsf(xv[0]); }
+  static __device__ __forceinline__ double mod64(const float* xv) { return fabs((double)xv[0]); }
+  // J_r^T v = r * v
+  static __device__ __forceinline__ void emit(float* __restrict__ out, int i, int w, const double* xv,
+                                              const double* rv, const double* dv, double cf) {
+    const double q = xv[0] * rv[0];
+    out[i] = (float)(dv[0] * rv[0] + cf * q);
+  }
+};
 
 // qpair[p] = E[h] o R[r] for the frozen-head rows
+template <class Prod>
 __global__ void kp_cx_qpair(const float* __restrict__ E, const float* __restrict__ R, int dp, int half,
                             const int2* __restrict__ pairs, int n_pairs, float* __restrict__ out) {
   int p = blockIdx.x;
@@ -55,7 +129,7 @@ __global__ void kp_cx_qpair(const float* __restrict__ E, const float* __restrict
   int2 hr = pairs[p];
   const float* lhs = E + (size_t)hr.x * dp;
   const float* rel = R + (size_t)hr.y * dp;
-  for (int d = threadIdx.x; d < dp; d += blockDim.x) out[(size_t)p * dp + d] = cx_q(lhs, rel, d, half);
+  for (int d = threadIdx.x; d < dp; d += blockDim.x) out[(size_t)p * dp + d] = Prod::q(lhs, rel, d, half);
 }
 
 // lsef[p] = the frozen-head pair's log-sum-exp over the frozen entities, merged from the
@@ -110,7 +184,8 @@ struct CxOpt {
 //     J_r^T (c <E> - Tsum - ck x) + (c p_k - ck) q,   <E> = softmax-weighted entity
 //     (frozen part sum_sp w_sp O_sp merged with the kelpie column p_k x)
 //   frozen-head row pair (count c, target = kelpie):  c (p_k - 1) q_pair
-template <int DP>
+// (`half` is the policy's extent w: d / 2 for ComplEx, d for DistMult)
+template <int DP, class Prod>
 __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __restrict__ stepq, int nq,
                                                      const int4* __restrict__ stept, int nt,
                                                      const CxQuery* __restrict__ pq, const float* __restrict__ X,
@@ -129,7 +204,7 @@ __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __res
     const float* rel = R + (size_t)sq.y * DP;
     const CxQuery Q = pq[sq.z];
     float z = 0.f;
-    for (int d = lane; d < 2 * half; d += 64) z += cx_q(x, rel, d, half) * x[d];
+    for (int d = lane; d < Prod::G * half; d += 64) z += Prod::q(x, rel, d, half) * x[d];
     z = wave_sum(z);
     // The softmax normalisation in fp64 with correctly rounded exp / log.  <E> below is
     // ~5e-4 per coordinate at the reference init and the row contributions cancel to a
@@ -157,10 +232,13 @@ __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __res
     // one leaves 104 of the 512 registers per lane free; with two splits' loads in flight
     // this kernel took 94 and still fitted, the round-4 forms with 150 did not and ran
     // only on the CUs no attention workgroup held: 92 -> 192 us per launch under overlap)
-    constexpr int NI = (DP / 2 + 63) / 64;
-    double ore_k[NI], oim_k[NI];
+    constexpr int G = Prod::G;
+    constexpr int NI = (DP / G + 63) / 64;
+    double o_k[NI][G];
 #pragma unroll
-    for (int k = 0; k < NI; ++k) ore_k[k] = oim_k[k] = 0.0;
+    for (int k = 0; k < NI; ++k)
+#pragma unroll
+      for (int h = 0; h < G; ++h) o_k[k][h] = 0.0;
     for (int sp = 0; sp < n_split; ++sp) {
       const double w0 = __shfl(wv_l, sp, 64);
       const float* O0 = att_O + ((size_t)sp * nq + item) * DP;
@@ -168,9 +246,11 @@ __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __res
       for (int k = 0; k < NI; ++k) {
         const int i = lane + 64 * k;
         const bool in = i < half;
-        const float a0 = in ? O0[i] : 0.f, b0 = in ? O0[i + half] : 0.f;
-        ore_k[k] += w0 * (double)a0;
-        oim_k[k] += w0 * (double)b0;
+        float o0[G];
+#pragma unroll
+        for (int h = 0; h < G; ++h) o0[h] = in ? O0[i + h * half] : 0.f;
+#pragma unroll
+        for (int h = 0; h < G; ++h) o_k[k][h] += w0 * (double)o0[h];
       }
     }
     const double fc = (double)Q.c, fck = (double)Q.ck;
@@ -180,27 +260,30 @@ __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __res
     for (int k = 0; k < NI; ++k) {
       const int i = lane + 64 * k;
       if (i >= half) continue;
-      const double a = x[i], b = x[i + half];
-      const double cc = rel[i], ee = rel[i + half];
-      const double ere = ore_k[k] + pk * a, eim = oim_k[k] + pk * b;
-      const double dre = fc * ere - (double)ts[i] - fck * a;
-      const double dim_ = fc * eim - (double)ts[i + half] - fck * b;
-      const double qre = a * cc - b * ee, qim = a * ee + b * cc;
-      out[i] = (float)(dre * cc + dim_ * ee + cf * qre);
-      out[i + half] = (float)(-dre * ee + dim_ * cc + cf * qim);
+      double xv[G], rv[G], dv[G];
+#pragma unroll
+      for (int h = 0; h < G; ++h) xv[h] = x[i + h * half];
+#pragma unroll
+      for (int h = 0; h < G; ++h) rv[h] = rel[i + h * half];
+#pragma unroll
+      for (int h = 0; h < G; ++h) {
+        const double e = o_k[k][h] + pk * xv[h];  // <E>: the frozen part and the kelpie column
+        dv[h] = fc * e - (double)ts[i + h * half] - fck * xv[h];
+      }
+      Prod::emit(out, i, half, xv, rv, dv, cf);
     }
   } else {
     const int4 st = stept[item - nq];  // slot, pair, count
     const float* x = X + (size_t)st.x * DP;
     const float* qp = Qpair + (size_t)st.y * DP;
     float z = 0.f;
-    for (int d = lane; d < 2 * half; d += 64) z += qp[d] * x[d];
+    for (int d = lane; d < Prod::G * half; d += 64) z += qp[d] * x[d];
     z = wave_sum(z);
     const double lf = lsef[st.y];
     const double hi = fmax(lf, (double)z), lo = fmin(lf, (double)z);
     const double lse = hi + log1p(exp(lo - hi));
     const double coef = (double)st.z * (exp((double)z - lse) - 1.0);
-    for (int d = lane; d < 2 * half; d += 64) out[d] = (float)(coef * (double)qp[d]);
+    for (int d = lane; d < Prod::G * half; d += 64) out[d] = (float)(coef * (double)qp[d]);
   }
 }
 
@@ -208,11 +291,13 @@ __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __res
 #define KP_CX_UPD64 0
 #endif
 // Sum a slot's contributions, add the N3 term, apply the optimizer (torch op order).
-template <int DP>
+// (`half` is the policy's extent w, as in kp_cx_contrib)
+template <int DP, class Prod>
 __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __restrict__ act,
                                                     const CxPlan* __restrict__ plans, int nq,
                                                     const float* __restrict__ contrib, float* __restrict__ X,
                                                     float* __restrict__ S1, float* __restrict__ S2, CxOpt opt) {
+  constexpr int G = Prod::G;
   const int tid = threadIdx.x;
   const int4 a4 = act[blockIdx.x];  // slot, plan, qoff, toff
   const int slot = a4.x;
@@ -243,7 +328,7 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
     for (int k = 0; k < (DP + 63) / 64; ++k) {
       const int d = lane + 64 * k;
       part[k] = 0.0;
-      if (d >= 2 * half) continue;
+      if (d >= G * half) continue;
       double acc[4] = {0.0, 0.0, 0.0, 0.0};
       int j = w;
       for (; j + 12 < nc; j += 16) {
@@ -261,7 +346,7 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
 #pragma unroll
       for (int k = 0; k < (DP + 63) / 64; ++k) {
         const int d = lane + 64 * k;
-        if (d < 2 * half) red[w][d] = part[k] + red[w][d];
+        if (d < G * half) red[w][d] = part[k] + red[w][d];
       }
     __syncthreads();
   }
@@ -270,7 +355,7 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
   __shared__ float red[4][DP];
   if (nc > UPD_WIDE) {
     const int w = tid >> 6, lane = tid & 63;
-    for (int d = lane; d < 2 * half; d += 64) {
+    for (int d = lane; d < G * half; d += 64) {
       float acc[4] = {0.f, 0.f, 0.f, 0.f};
       int j = w;
       for (; j + 12 < nc; j += 16) {
@@ -286,15 +371,18 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
   }
 #endif
   // N2 (regularizers.py:25-35): the factor of each batch row holding the kelpie entity
-  // is ||f||^3 with f_i = |x_i| (complex modulus, complex.py:80-84), so its gradient is
-  // 3 w / B * ||f|| * x per such row; ||f|| over the whole row, before the update
+  // is ||f||^3 with f_i the policy's modulus (complex.py:80-84: |x_i| complex; distmult.py:66:
+  // |x_i| real), so its gradient is 3 w / B * ||f|| * x per such row; ||f|| over the whole
+  // row, before the update
   float n2 = 0.f;
   if (opt.reg_w != 0.f && opt.reg_n2) {
     __shared__ float n2red[4];
     float ps = 0.f;
     for (int i = tid; i < half; i += 256) {
-      const float a = x[i], b = x[i + half];
-      const float f = sqrtf(a * a + b * b);
+      float xv[G];
+#pragma unroll
+      for (int h = 0; h < G; ++h) xv[h] = x[i + h * half];
+      const float f = Prod::mod(xv);
       ps += f * f;
     }
     ps = wave_sum(ps);
@@ -303,49 +391,56 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
     n2 = sqrtf((n2red[0] + n2red[1]) + (n2red[2] + n2red[3]));
   }
 #pragma unroll
-  for (int u = 0; u < (DP / 2 + 255) / 256; ++u) {
+  for (int u = 0; u < (DP / G + 255) / 256; ++u) {
     const int i = tid + 256 * u;
     if (i >= half) continue;
-    acc_t gv[2] = {0.f, 0.f};
+    acc_t gv[G];
+#pragma unroll
+    for (int h = 0; h < G; ++h) gv[h] = 0.f;
     if (nc > UPD_WIDE) {
+#pragma unroll
+      for (int h = 0; h < G; ++h) {
+        const int d = i + h * half;
 #if KP_CX_UPD64
-      gv[0] = red[0][i] + red[1][i];
-      gv[1] = red[0][i + half] + red[1][i + half];
+        gv[h] = red[0][d] + red[1][d];
 #else
-      gv[0] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-      gv[1] = (red[0][i + half] + red[1][i + half]) + (red[2][i + half] + red[3][i + half]);
+        gv[h] = (red[0][d] + red[1][d]) + (red[2][d] + red[3][d]);
 #endif
+      }
     } else {
       for (int j = 0; j < nc; ++j) {
         const float* c = crow(j);
-        gv[0] += c[i];
-        gv[1] += c[i + half];
+#pragma unroll
+        for (int h = 0; h < G; ++h) gv[h] += c[i + h * half];
       }
     }
+#pragma unroll
+    for (int h = 0; h < G; ++h) {
 #if KP_CX_UPD64
-    gv[0] /= (double)P.b;
-    gv[1] /= (double)P.b;
+      gv[h] /= (double)P.b;
 #else
-    gv[0] *= inv_b;
-    gv[1] *= inv_b;
+      gv[h] *= inv_b;
 #endif
-    const float a = x[i], b = x[i + half];
+    }
+    float xv[G];
+#pragma unroll
+    for (int h = 0; h < G; ++h) xv[h] = x[i + h * half];
     if (opt.reg_w != 0.f) {
 #if KP_CX_UPD64
-      const double mod = opt.reg_n2 ? (double)n2 : sqrt((double)a * a + (double)b * b);
+      const double mod = opt.reg_n2 ? (double)n2 : Prod::mod64(xv);
       const double k3 = 3.0 * (double)opt.reg_w / (double)P.b * (double)(P.cnt_l + P.cnt_r) * mod;
 #else
-      const float mod = opt.reg_n2 ? n2 : sqrtf(a * a + b * b);
+      const float mod = opt.reg_n2 ? n2 : Prod::mod(xv);
       const float k3 = 3.0f * opt.reg_w * inv_b * (float)(P.cnt_l + P.cnt_r) * mod;
 #endif
-      gv[0] += k3 * a;
-      gv[1] += k3 * b;
+#pragma unroll
+      for (int h = 0; h < G; ++h) gv[h] += k3 * xv[h];
     }
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < G; ++h) {
       const int d = i + h * half;
       const float gd = (float)gv[h];
-      float xd = h ? b : a;
+      float xd = xv[h];
       const size_t o = (size_t)slot * DP + d;
       if (opt.kind == KP_OPT_ADAGRAD) {
         float s1 = S1[o];
@@ -373,17 +468,7 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
 // fp64 ranking queries (launch_rank_f64): q_s = x_s o R[p_s] from exact fp64 products of
 // the fp32 operands; the target score q_s . E_o and the kelpie column q_s . x_s as one
 // sequential fp64 FMA chain over d (the order kp_rank_f64_count scores every entity in)
-__device__ __forceinline__ double cx_q64(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
-                                         int half) {
-  if (d < half) return (double)lhs[d] * (double)rel[d] - (double)lhs[d + half] * (double)rel[d + half];
-  if (d < 2 * half) {
-    const int i = d - half;
-    return (double)lhs[i] * (double)rel[d] + (double)lhs[d] * (double)rel[i];
-  }
-  return 0.0;
-}
-
-template <int DP>
+template <int DP, class Prod>
 __global__ void kp_cx_rankq64(const float* __restrict__ X, const float* __restrict__ R, const float* __restrict__ E,
                               int n_ent, int half, const int32_t* __restrict__ pred, int n_slots,
                               double* __restrict__ Q, double* __restrict__ t64, double* __restrict__ kcol64) {
@@ -392,7 +477,7 @@ __global__ void kp_cx_rankq64(const float* __restrict__ X, const float* __restri
   const float* x = X + (size_t)s * DP;
   const float* rel = R + (size_t)pred[3 * s + 1] * DP;
   double* q = Q + (size_t)s * DP;
-  for (int d = threadIdx.x; d < DP; d += blockDim.x) q[d] = cx_q64(x, rel, d, half);
+  for (int d = threadIdx.x; d < DP; d += blockDim.x) q[d] = Prod::q64(x, rel, d, half);
   __syncthreads();
   if (threadIdx.x == 0) {
     const int o = pred[3 * s + 2];
@@ -409,6 +494,7 @@ __global__ void kp_cx_rankq64(const float* __restrict__ X, const float* __restri
   }
 }
 
+template <class Prod>
 __global__ void kp_cx_scoreq(const float* __restrict__ E, const float* __restrict__ R, int dp, int half,
                              const int32_t* __restrict__ heads, const int32_t* __restrict__ rels, int n,
                              float* __restrict__ Q) {
@@ -416,14 +502,14 @@ __global__ void kp_cx_scoreq(const float* __restrict__ E, const float* __restric
   if (s >= n) return;
   const float* lhs = E + (size_t)heads[s] * dp;
   const float* rel = R + (size_t)rels[s] * dp;
-  for (int d = threadIdx.x; d < dp; d += blockDim.x) Q[(size_t)s * dp + d] = cx_q(lhs, rel, d, half);
+  for (int d = threadIdx.x; d < dp; d += blockDim.x) Q[(size_t)s * dp + d] = Prod::q(lhs, rel, d, half);
 }
 
 // ----------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------
 // step queries q_j = x_slot o R_rel (complex.py:65-72), one row per step query
-template <int DP>
+template <int DP, class Prod>
 __global__ void kp_cx_stepq(const float* __restrict__ X, const float* __restrict__ R, int half,
                             const int4* __restrict__ stepq, int nq, float* __restrict__ Q) {
   const int j = blockIdx.x;
@@ -431,13 +517,14 @@ __global__ void kp_cx_stepq(const float* __restrict__ X, const float* __restrict
   const int4 sq = stepq[j];
   const float* x = X + (size_t)sq.x * DP;
   const float* rel = R + (size_t)sq.y * DP;
-  for (int d = threadIdx.x; d < DP; d += blockDim.x) Q[(size_t)j * DP + d] = cx_q(x, rel, d, half);
+  for (int d = threadIdx.x; d < DP; d += blockDim.x) Q[(size_t)j * DP + d] = Prod::q(x, rel, d, half);
 }
 
-template <int DB>
+template <int DB, class Prod>
 void launch_stepq(kp_ctx* c, const int4* stepq, const float* X, int nq, float* Q) {
   if (nq <= 0) return;
-  hipLaunchKernelGGL((kp_cx_stepq<16 * DB>), dim3(nq), dim3(64), 0, c->stream, X, c->dR, c->dim / 2, stepq, nq, Q);
+  hipLaunchKernelGGL((kp_cx_stepq<16 * DB, Prod>), dim3(nq), dim3(64), 0, c->stream, X, c->dR, Prod::extent(c->dim), stepq,
+                     nq, Q);
   KP_HIP(hipGetLastError());
 }
 
@@ -471,29 +558,29 @@ void launch_attn(kp_ctx* c, bool with_o, const float* Q, int nq, const AttnPlan&
   KP_HIP(hipGetLastError());
 }
 
-template <int DB>
+template <int DB, class Prod>
 void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, const CxQuery* pq,
                    const int4* stepq, int nq, const int4* stept, int nt, const float* tsum, const float* qpair,
                    const float* lsef, const float* am, const float* al, const float* aO, int n_split, float* contrib,
                    float* X, float* S1, float* S2, const CxOpt& opt) {
   if (n_act <= 0) return;
-  const int half = c->dim / 2;
+  const int half = Prod::extent(c->dim);
   KP_REQUIRE(n_split >= 1 && n_split <= 64, "cx contrib: one attention split per lane");
   if (nq + nt > 0) {
-    hipLaunchKernelGGL((kp_cx_contrib<16 * DB>), dim3((nq + nt + 3) / 4), dim3(256), 0, c->stream, half, stepq, nq,
+    hipLaunchKernelGGL((kp_cx_contrib<16 * DB, Prod>), dim3((nq + nt + 3) / 4), dim3(256), 0, c->stream, half, stepq, nq,
                        stept, nt, pq, X, c->dR, tsum, qpair, lsef, am, al, aO, n_split, contrib);
     KP_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL((kp_cx_update<16 * DB>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq, contrib, X,
+  hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq, contrib, X,
                      S1, S2, opt);
   KP_HIP(hipGetLastError());
 }
 
-template <int DB>
+template <int DB, class Prod>
 void launch_rankq64(kp_ctx* c, const float* X, const int32_t* pred, int n, double* Q, double* t64, double* kcol64) {
   if (n <= 0) return;
-  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB>), dim3(n), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
-                     c->dim / 2, pred, n, Q, t64, kcol64);
+  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod>), dim3(n), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
+                     Prod::extent(c->dim), pred, n, Q, t64, kcol64);
   KP_HIP(hipGetLastError());
 }
 
@@ -506,31 +593,27 @@ void launch_rankq64(kp_ctx* c, const float* X, const int32_t* pred, int n, doubl
     case 13: { constexpr int DB = 13; __VA_ARGS__; } break; \
     case 16: { constexpr int DB = 16; __VA_ARGS__; } break; \
     case 25: { constexpr int DB = 25; __VA_ARGS__; } break; \
-    default: throw KpError{KP_ENOTSUP, "ComplEx: unsupported padded dimension"}; \
+    default: throw KpError{KP_ENOTSUP, "ComplEx / DistMult: unsupported padded dimension"}; \
   }
 
-}  // namespace
-
-int cx_pick_db(int dim) {
-  static const int dbs[] = {1, 2, 4, 8, 13, 16, 25};
-  for (int db : dbs)
-    if (16 * db >= dim) return db;
-  return -1;
-}
-
+// The batched post-training and rank of a model whose step is a 1-vs-all softmax over
+// q = lhs o rel (product policy Prod): planning, workspaces, attention planning and timing
+// are the model's only through Prod.
 // KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time before the first upload (checks
 // and planning), up to the last launch enqueued, and waiting for the device
-void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
+template <class Prod>
+void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
+  const std::string who = Prod::name;
   const double t_in = g_host_times ? host_ms() : 0.0;
   const int DBV = c->dp / 16;
   const int K = c->n_ent;  // kelpie id
   const int ns = bt->n_slots;
   const int hpbs = hp->batch_size;
-  KP_REQUIRE(hpbs > 0 && hp->epochs >= 0, "ComplEx: bad batch_size/epochs");
+  KP_REQUIRE(hpbs > 0 && hp->epochs >= 0, who + ": bad batch_size/epochs");
   const int E = hp->epochs;
   // every id is checked before it indexes a host vector or a device table, as in every
   // model family (kp_batch_check.hpp)
-  require_batch(c, bt, "ComplEx");
+  require_batch(c, bt, Prod::name);
 
   std::vector<CxPlan> plans;
   std::vector<CxQuery> pqs;
@@ -572,7 +655,7 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
           qtg_count[rel_slot[r]] += 1;
         }
       } else {
-        KP_REQUIRE(t == K, "ComplEx: a training row does not involve the kelpie entity");
+        KP_REQUIRE(t == K, who + ": a training row does not involve the kelpie entity");
         P.cnt_r += 1;
         const int64_t key = (int64_t)h * c->n_rel2 + r;
         auto it = pair_id.find(key);
@@ -631,10 +714,10 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
       make_plan(rows, nullptr, R);
     } else {
       const int64_t g0 = bt->rng_off[s], g1 = bt->rng_off[s + 1];
-      KP_REQUIRE(g1 - g0 >= (int64_t)E * R, "ComplEx: missing randperm draws for a multi-step slot");
+      KP_REQUIRE(g1 - g0 >= (int64_t)E * R, who + ": missing randperm draws for a multi-step slot");
       for (int e = 0; e < E; ++e) {
         const int32_t* perm = bt->rng + g0 + (int64_t)e * R;
-        for (int j = 0; j < R; ++j) KP_REQUIRE(perm[j] >= 0 && perm[j] < R, "ComplEx: randperm value out of range");
+        for (int j = 0; j < R; ++j) KP_REQUIRE(perm[j] >= 0 && perm[j] < R, who + ": randperm value out of range");
         for (int j = 0; j < nst; ++j) {
           const int st = j * hpbs;
           const int n = std::min(bs, R - st);
@@ -703,7 +786,7 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   int32_t* dPred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
   const RankDev rk = upload_rank_inputs(c, bt);
 
-  const int half = c->dim / 2;
+  const int half = Prod::extent(c->dim);
   KP_HIP(hipEventRecord(c->ev0, c->stream));
   if (npq > 0) {
     hipLaunchKernelGGL(kp_cx_tsum, dim3(npq), dim3(128), 0, c->stream, c->dE, DP, dPq, npq, dTg, dTsum);
@@ -728,7 +811,7 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   float* dAO = reinterpret_cast<float*>(c->cx.ao.ensure(sizeof(float) * att_rows * DP));
   float* dQs = reinterpret_cast<float*>(c->cx.qs.ensure(sizeof(float) * (size_t)std::max(max_nq, 1) * DP));
   if (npairs > 0) {
-    hipLaunchKernelGGL(kp_cx_qpair, dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP, half, dPairs, npairs,
+    hipLaunchKernelGGL(kp_cx_qpair<Prod>, dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP, half, dPairs, npairs,
                        dQpair);
     KP_HIP(hipGetLastError());
     CX_DISPATCH(DBV, launch_attn<DB>(c, false, dQpair, npairs, plan_pairs, dAm, dAl, nullptr));
@@ -748,7 +831,7 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   opt.one_minus_b1 = (float)(1.0 - (double)hp->beta1);
   opt.one_minus_b2 = (float)(1.0 - (double)hp->beta2);
   opt.reg_w = hp->reg_weight;
-  KP_REQUIRE(hp->reg_kind == KP_REG_N3 || hp->reg_kind == KP_REG_N2, "ComplEx: unknown regulariser");
+  KP_REQUIRE(hp->reg_kind == KP_REG_N3 || hp->reg_kind == KP_REG_N2, who + ": unknown regulariser");
   opt.reg_n2 = hp->reg_kind == KP_REG_N2;
   // loop-interval events, destroyed on every exit path (a KP_HIP / KP_REQUIRE below throws)
   struct LoopEvents {
@@ -776,7 +859,7 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
       ea = c->event(2 * hot_launches);
       eb = c->event(2 * hot_launches + 1);
     }
-    CX_DISPATCH(DBV, launch_stepq<DB>(c, dStepQ + q_off[t], dX, nq, dQs));
+    CX_DISPATCH(DBV, launch_stepq<DB, Prod>(c, dStepQ + q_off[t], dX, nq, dQs));
     if (nq > 0 && c->time_hot) KP_HIP(hipEventRecord(ea, c->stream));
     CX_DISPATCH(DBV, launch_attn<DB>(c, true, dQs, nq, step_plan[t], dAm, dAl, dAO));
     if (nq > 0) {
@@ -789,7 +872,7 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
     const double step = (double)(t + 1);
     opt.step_size = (float)((double)hp->lr / (1.0 - std::pow((double)hp->beta1, step)));
     opt.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)hp->beta2, step));
-    CX_DISPATCH(DBV, launch_update<DB>(c, na, dActs + act_off[t], dPlans, dPq, dStepQ + q_off[t], nq,
+    CX_DISPATCH(DBV, launch_update<DB, Prod>(c, na, dActs + act_off[t], dPlans, dPq, dStepQ + q_off[t], nq,
                                        dStepT + t_off[t], t_off[t + 1] - t_off[t], dTsum, dQpair, dLsef, dAm, dAl, dAO,
                                        sp, dContrib, dX, dS1, dS2, opt));
     if (g_host_times) {
@@ -803,7 +886,7 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
 
   // ---- ranking: scores of (kelpie, p, .) over E plus the kelpie column, in fp64
   // (launch_rank_f64: at the reference init the target's neighbours are ~1e-5 relative away)
-  CX_DISPATCH(DBV, launch_rankq64<DB>(c, dX, dPred, ns, r64.q, r64.t, r64.kcol));
+  CX_DISPATCH(DBV, launch_rankq64<DB, Prod>(c, dX, dPred, ns, r64.q, r64.t, r64.kcol));
   launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
 
@@ -818,11 +901,29 @@ void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   record_hot_timing(c, hot_launches, h0, h1);
 }
 
+}  // namespace
+
+int cx_pick_db(int dim) {
+  static const int dbs[] = {1, 2, 4, 8, 13, 16, 25};
+  for (int db : dbs)
+    if (16 * db >= dim) return db;
+  return -1;
+}
+
+void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) { posttrain_rank<CxProd>(c, hp, bt); }
+void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) { posttrain_rank<DmProd>(c, hp, bt); }
+
+// scores of (head, relation) pairs against every entity; ComplEx and DistMult contexts
 void complex_scores_dev(kp_ctx* c, int n, const int32_t* dh, const int32_t* dr, float* dS, int ld) {
   if (n <= 0) return;
   const int DP = c->dp;
   float* dQ = reinterpret_cast<float*>(c->cx.score_q.ensure(sizeof(float) * (size_t)n * DP));
-  hipLaunchKernelGGL(kp_cx_scoreq, dim3(n), dim3(128), 0, c->stream, c->dE, c->dR, DP, c->dim / 2, dh, dr, n, dQ);
+  if (c->model == KP_MODEL_DISTMULT)
+    hipLaunchKernelGGL(kp_cx_scoreq<DmProd>, dim3(n), dim3(128), 0, c->stream, c->dE, c->dR, DP,
+                       DmProd::extent(c->dim), dh, dr, n, dQ);
+  else
+    hipLaunchKernelGGL(kp_cx_scoreq<CxProd>, dim3(n), dim3(128), 0, c->stream, c->dE, c->dR, DP,
+                       CxProd::extent(c->dim), dh, dr, n, dQ);
   KP_HIP(hipGetLastError());
   launch_score_gemm(c, dQ, n, dS, ld, 0);
 }

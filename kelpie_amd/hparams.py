@@ -9,7 +9,8 @@ The reference turns its hp dicts into Pydantic models before it uses them:
   ``BCEOptimizerHyperParams`` (``bce_optimizer.py:17-22``, ConvE);
 * model params, when the model is built (``explain.py:169-172``):
   ``TransEHyperParams`` (``transe.py:12-14``), ``ComplExHyperParams`` (``complex.py:12-14``),
-  ``ConvEHyperParams`` (``conve.py:15-20``).
+  ``ConvEHyperParams`` (``conve.py:15-20``), ``DistMultHyperParams`` (``distmult.py:12-14``;
+  the reference trains DistMult with ComplEx's ``MultiClassNLLOptimizer``).
 
 The same classes here give the same behaviour: a missing field or a value of the wrong
 type raises ``pydantic.ValidationError`` (a ``ValueError``) naming the field, values are
@@ -61,6 +62,11 @@ class ComplExHyperParams(BaseModel):
     init_scale: float
 
 
+class DistMultHyperParams(BaseModel):
+    dimension: int
+    init_scale: float
+
+
 class ConvEHyperParams(BaseModel):
     dimension: int
     input_dropout_rate: float
@@ -71,8 +77,9 @@ class ConvEHyperParams(BaseModel):
 
 # MODEL_REGISTRY[name]["optimizer"].get_hyperparams_class() (link_prediction/__init__.py)
 OPTIMIZER_HP = {"ComplEx": MultiClassNLLOptimizerHyperParams, "TransE": PairwiseRankingOptimizerHyperParams,
-                "ConvE": BCEOptimizerHyperParams}
-MODEL_HP = {"ComplEx": ComplExHyperParams, "TransE": TransEHyperParams, "ConvE": ConvEHyperParams}
+                "ConvE": BCEOptimizerHyperParams, "DistMult": MultiClassNLLOptimizerHyperParams}
+MODEL_HP = {"ComplEx": ComplExHyperParams, "TransE": TransEHyperParams, "ConvE": ConvEHyperParams,
+            "DistMult": DistMultHyperParams}
 
 
 def optimizer_hp(model_name: str, hp: dict) -> dict:

@@ -112,15 +112,13 @@ class FrozenModel:
         self.posttrain_draws(rows, hp, rng)
 
 
-class ComplEx(FrozenModel):
-    """ComplEx (complex.py:17-142): rows [Re | Im], maximizer."""
-
-    name = "ComplEx"
+class MultiClassNLLModel(FrozenModel):
+    """What ComplEx and DistMult share: a kelpie row initialised as ``init * init_scale``
+    and post-trained by ``KelpieMultiClassNLLOptimizer`` (multiclass_nll_optimizer.py:57-164),
+    which draws one ``randperm`` per epoch and nothing at construction."""
 
     def __init__(self, dataset, entity_embeddings, relation_embeddings, init_scale=1e-3, device=0):
         super().__init__(dataset, entity_embeddings, relation_embeddings, device)
-        assert self.dimension % 2 == 0
-        self.real_dimension = self.dimension // 2
         self.init_scale = float(init_scale)
 
     def kelpie_init(self, init, rng):
@@ -149,6 +147,26 @@ class ComplEx(FrozenModel):
 
     def posttrain_skip(self, rows, n_rows, hp, rng):
         rng.complex_epochs(int(n_rows), int(hp["epochs"]), int(hp["batch_size"]), want=False)
+
+
+class ComplEx(MultiClassNLLModel):
+    """ComplEx (complex.py:17-142): rows [Re | Im], maximizer."""
+
+    name = "ComplEx"
+
+    def __init__(self, dataset, entity_embeddings, relation_embeddings, init_scale=1e-3, device=0):
+        super().__init__(dataset, entity_embeddings, relation_embeddings, init_scale, device)
+        assert self.dimension % 2 == 0
+        self.real_dimension = self.dimension // 2
+
+
+class DistMult(MultiClassNLLModel):
+    """DistMult (distmult.py:17-71): plain [d] rows, score (lhs * rel) . rhs, maximizer;
+    ``dimension`` is d.  The reference trains it with ComplEx's optimizer; its
+    KelpieDistMult (distmult.py:74-94) cannot be constructed, and the evident intent of
+    :85-90 is the row initialisation ``init * init_scale`` of complex.py:155-157."""
+
+    name = "DistMult"
 
 
 class TransE(FrozenModel):
@@ -272,7 +290,7 @@ class ConvE(FrozenModel):
             rng.discard(2 * per_pair * int(sum(steps)))
 
 
-MODEL_REGISTRY = {"ComplEx": ComplEx, "TransE": TransE, "ConvE": ConvE}
+MODEL_REGISTRY = {"ComplEx": ComplEx, "TransE": TransE, "ConvE": ConvE, "DistMult": DistMult}
 
 
 def from_state_dict(name, dataset, state, model_params, device=0):
@@ -289,6 +307,8 @@ def from_state_dict(name, dataset, state, model_params, device=0):
     E, R = arr("entity_embeddings"), arr("relation_embeddings")
     if name == "ComplEx":
         return ComplEx(dataset, E, R, init_scale=model_params.get("init_scale", 1e-3), device=device)
+    if name == "DistMult":
+        return DistMult(dataset, E, R, init_scale=model_params.get("init_scale", 1e-3), device=device)
     if name == "TransE":
         return TransE(dataset, E, R, norm=model_params.get("norm", 2), device=device)
     if name == "ConvE":

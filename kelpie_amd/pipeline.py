@@ -104,6 +104,7 @@ def reference_construction_draws(model_name, num_entities, num_relations, model_
     * TransE (transe.py:27-32): ``torch.rand(|E|, d)``, ``torch.rand(2|R|, d)``, then
       ``xavier_normal_`` on both;
     * ComplEx (complex.py:27-31): ``torch.rand(|E|, 2d)``, ``torch.rand(2|R|, 2d)``;
+    * DistMult (distmult.py:29-31): ``torch.rand(|E|, d)``, ``torch.rand(2|R|, d)``;
     * ConvE (conve.py:44-61): the ``Conv2d(1, 32, 3x3)`` and ``Linear(hidden, d)``
       ``reset_parameters`` draws, then as TransE.
 
@@ -117,6 +118,10 @@ def reference_construction_draws(model_name, num_entities, num_relations, model_
         torch.rand(n_rel2, d)
         return
     d = int(model_params["dimension"])
+    if model_name == "DistMult":
+        torch.rand(int(num_entities), d)
+        torch.rand(n_rel2, d)
+        return
     if model_name == "ConvE":
         torch.nn.Conv2d(1, 32, (3, 3), 1, 0, bias=True)
         torch.nn.Linear(int(model_params["hidden_layer_size"]), d)

@@ -7,7 +7,7 @@ from published dataset statistics (SURVEY.md §8(d) "Synthetic inputs"):
 Zipf-like entity popularity ``p_i ∝ i^-0.8``, uniform relations, deduplicated,
 then split train / valid / test.  Weights follow the reference initialisers
 (TransE / ConvE ``xavier_normal_``: ``transe.py:30-35``, ``conve.py:54-59``;
-ComplEx ``U[0,1)·init_scale``: ``complex.py:27-35``).
+ComplEx / DistMult ``U[0,1)·init_scale``: ``complex.py:27-35``, ``distmult.py:29-35``).
 """
 from __future__ import annotations
 
@@ -116,6 +116,12 @@ def make_weights(model: str, n_ent: int, n_rel: int, dim: int, seed: int = 0,
         D = 2 * dim
         return {"entity_embeddings": (rng.random((n_ent, D)) * init_scale).astype(np.float32),
                 "relation_embeddings": (rng.random((R2, D)) * init_scale).astype(np.float32)}
+    if model == "DistMult":  # distmult.py:29-35: U[0,1) * init_scale on plain [d] rows
+        if trained_scale:
+            return {"entity_embeddings": (rng.standard_normal((n_ent, dim)) * trained_scale).astype(np.float32),
+                    "relation_embeddings": (rng.standard_normal((R2, dim)) * trained_scale).astype(np.float32)}
+        return {"entity_embeddings": (rng.random((n_ent, dim)) * init_scale).astype(np.float32),
+                "relation_embeddings": (rng.random((R2, dim)) * init_scale).astype(np.float32)}
     if model == "ConvE":
         if trained_scale:
             w = {"entity_embeddings": (rng.standard_normal((n_ent, dim)) * trained_scale).astype(np.float32),
