@@ -515,6 +515,8 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   const int DP = c->dp;
   const bool l1 = c->te_norm == 1;
   require_batch(c, bt, "TransE");
+  // before the first upload: the buffers below are sized by DP, the kernels hold DP / 256 float4 per lane
+  KP_REQUIRE(DP <= 512, "TransE: dimension > 512 not supported");
   KP_REQUIRE(hp->neg_ratio >= 1 && hp->batch_size >= 1 && hp->epochs >= 0, "TransE: bad hyper-parameters");
   std::vector<TeSlot> slots(ns);
   for (int s = 0; s < ns; ++s) {
@@ -549,7 +551,6 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   for (int s = 0; s < ns; ++s) order[s] = s;
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return slots[a].R > slots[b].R; });
   int32_t* dOrder = upload(c, c->te.order, order.data(), order.size());
-  KP_REQUIRE(DP <= 512, "TransE: dimension > 512 not supported");
   int max_r = 0;
   for (int s = 0; s < ns; ++s) max_r = std::max(max_r, slots[s].R);
   // one 1024-thread workgroup per CU: a long slot is bound by the row gathers one CU keeps
