@@ -165,6 +165,26 @@ int kp_host_free(void* p);
  * (post_training_engine.py:101-125). */
 int kp_posttrain_rank(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch);
 
+/* kp_posttrain_rank, plus what each slot's post-trained row would predict instead: the k
+ * best tails of (kelpie, p, .) among the columns 0 .. n_ent (column n_ent = the kelpie
+ * entity), taken from the values the rank compares (the reference keeps only the target's
+ * score and rank of get_triple_results' masked row, post_training_engine.py:101-125).
+ *   masking     as the rank: every filtered column is left out, the target o too when it is
+ *               filtered (ComplEx, ConvE, DistMult); TransE restores its filtered o; the
+ *               kelpie column takes part unless filtered
+ *   order       better value first (TransE: the smaller distance), equal values by column
+ *               id; ConvE orders on its fp64 logits (two saturated sigmoids, a tie for the
+ *               rank, stay in logit order)
+ *   out_ids     [n_slots][k] column ids, -1 past the last unmasked column
+ *   out_scores  [n_slots][k] the columns' scores, converted as out_score is; 0 past the end
+ * If o is unmasked and out_rank <= k, o is among the first out_rank ids of its slot.
+ * out_x, out_score and out_rank are bit for bit those of kp_posttrain_rank.
+ * k in [1, 32]; k == 0 with NULL outputs is kp_posttrain_rank.  KP_EINVAL (after the batch
+ * check, before any device work) for k < 0, k > 32 or k > 0 with a NULL output;
+ * KP_ENOTSUP for k > 0 when the context ranks in fp32 (KP_TE_RANK=f32, KP_CV_RANK=f32). */
+int kp_posttrain_rank_topk(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
+                           float* out_scores);
+
 /* Model.all_scores (model.py:19; transe.py:48-65, complex.py:88-112,
  * conve.py:133-158) for n (head, relation) pairs over the frozen entities:
  * out[n][n_ent].  The RelevanceEngine.select_entities_to_convert sweep

@@ -29,7 +29,7 @@ EXPORTS = ["kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_posttrain_ran
            "kp_sched_batch_create", "kp_sched_batch_destroy", "kp_sched_add_calls", "kp_sched_pack",
            "kp_gather_i32", "kp_rng_transe_calls_async", "kp_rng_torch_take", "kp_conve_train_begin",
            "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free", "kp_ctx_set_inflight",
-           "kp_last_attn_plan"]
+           "kp_last_attn_plan", "kp_posttrain_rank_topk"]
 
 
 class ModelDesc(C.Structure):
@@ -77,6 +77,8 @@ def lib():
         L.kp_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
         L.kp_host_free.argtypes = [C.c_void_p]
         L.kp_posttrain_rank.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch)]
+        L.kp_posttrain_rank_topk.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
+                                             C.c_void_p]
         L.kp_all_scores.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kp_convertible.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
@@ -369,7 +371,13 @@ class Context:
         except Exception:
             pass
 
-    def posttrain_rank(self, hp: HP, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False):
+    def posttrain_rank(self, hp: HP, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False, topk=0):
+        """kp_posttrain_rank: (target scores, ranks, final rows or None).  With ``topk`` > 0
+        (kp_posttrain_rank_topk) a fourth element: (ids int32 [n][topk], scores float32
+        [n][topk]), the slots' best unmasked tails, -1 / 0 past the last one."""
+        topk = int(topk)
+        if not 0 <= topk <= 32:
+            raise ValueError(f"topk must be in [0, 32], got {topk}")
         n = len(row_off) - 1
         x0 = np.ascontiguousarray(x0, dtype=np.float32)
         row_off = np.ascontiguousarray(row_off, dtype=np.int32)
@@ -384,8 +392,13 @@ class Context:
         out_r = np.zeros(n, np.int64)
         b = Batch(n, _ptr(x0), _ptr(row_off), _ptr(rows), _ptr(rng_off), _ptr(rng), _ptr(pred), _ptr(filt_off),
                   _ptr(filt), _ptr(out_x), _ptr(out_s), _ptr(out_r))
-        check(lib().kp_posttrain_rank(self.h, C.byref(hp), C.byref(b)), self.h)
-        return out_s, out_r, out_x
+        if topk == 0:
+            check(lib().kp_posttrain_rank(self.h, C.byref(hp), C.byref(b)), self.h)
+            return out_s, out_r, out_x
+        ids = np.full((n, topk), -1, np.int32)
+        top = np.zeros((n, topk), np.float32)
+        check(lib().kp_posttrain_rank_topk(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top)), self.h)
+        return out_s, out_r, out_x, (ids, top)
 
     def all_scores(self, heads, rels):
         heads = np.ascontiguousarray(heads, dtype=np.int32)

@@ -35,6 +35,13 @@ probability the replay has reached (1 - average / best of the sliding window),
 between ``AUTO_MIN`` and ``AUTO_MAX`` rules.  Either way the results, the draws and
 ``#relevances`` are those of the sequential reference; only the device work spent
 past a stop (``stats["wasted"]``) and the number of engine batches change.
+
+With ``top_k`` > 0 the engine also reports, for every post-training, the k tails the
+post-trained row would predict (``engine.top_k``), and each record gains
+``"counterfactuals"``, aligned with ``rule_to_relevance``: per rule the ``base`` and
+``post`` lists of [label, score] pairs (the sufficient engine: one such pair of lists per
+conversion entity, with its label); the kelpie entity is printed as ``kelpie:`` plus the
+label of the entity it clones.  The lists come with the batches the search runs anyway.
 """
 from __future__ import annotations
 
@@ -47,7 +54,7 @@ class StochasticBuilder:
     AUTO_MIN, AUTO_MAX = 4, 32
 
     def __init__(self, xsi, engine, summarization: str = None, max_explanation_length: int = 4, window=32,
-                 pipelined=False):
+                 pipelined=False, top_k=0):
         if summarization is not None:
             raise NotImplementedError("summarisation (simulation / bisimulation) is out of scope")
         self.xsi = xsi
@@ -59,6 +66,10 @@ class StochasticBuilder:
         self.pipelined = bool(pipelined) and hasattr(engine, "submit_batch")
         self.spec_window = self.AUTO_MAX if self.auto else max(1, int(window))
         self.summarization = None
+        self.top_k = int(top_k)
+        if self.top_k:
+            engine.top_k = self.top_k  # validates the range
+        self._details = {}  # rule -> the engine's (post-trained, base) results of its evaluation
         self.stats = {"batches": 0, "evaluated": 0, "wasted": 0, "batch_s": 0.0, "schedule_s": 0.0, "pack_s": 0.0,
                       "lib_s": 0.0}
 
@@ -73,6 +84,7 @@ class StochasticBuilder:
     def build_explanations(self, pred, candidate_triples: list, k: int = 10):
         start = time.time()
         candidate_triples = [tuple(int(v) for v in t) for t in candidate_triples]
+        self._details = {}
         triple_to_rel = self.explore_singleton_rules(pred, candidate_triples)
         srt = sorted(triple_to_rel.items(), key=lambda x: x[1], reverse=True)
         rule_to_rel = [((t,), rel) for (t, rel) in srt]
@@ -92,8 +104,34 @@ class StochasticBuilder:
                     break
         rule_to_rel = sorted(rule_to_rel, key=lambda x: (x[1], 1 / len(x[0])), reverse=True)[:k]
         mapped = [(self.dataset.labels_triples(rule), rel) for rule, rel in rule_to_rel]
-        return {"triple": self.dataset.labels_triple(tuple(pred)), "rule_to_relevance": mapped,
-                "#relevances": rels_num, "execution_time": time.time() - start}
+        out = {"triple": self.dataset.labels_triple(tuple(pred)), "rule_to_relevance": mapped,
+               "#relevances": rels_num, "execution_time": time.time() - start}
+        if self.top_k:
+            out["counterfactuals"] = [self._counterfactual(pred, self._details[rule]) for rule, _ in rule_to_rel]
+        return out
+
+    def _keep_details(self, rules, n):
+        """The engine's per-rule results of its last batch, for the first ``n`` of ``rules``."""
+        if self.top_k:
+            for rule, det in zip(rules[:n], self.engine.last_results):
+                self._details[tuple(rule)] = det
+
+    def _labelled(self, res, cloned):
+        """A result's list as [label, score] pairs; None when it was cached without one."""
+        if res.get("top_ids") is None:
+            return None
+        ds, k = self.dataset, self.top_k
+        return [["kelpie:" + ds.id_to_entity[cloned] if e == ds.num_entities else ds.id_to_entity[e], float(v)]
+                for e, v in zip(res["top_ids"][:k], res["top_scores"][:k])]
+
+    def _counterfactual(self, pred, det):
+        if isinstance(det, tuple):  # necessary: (post-trained, base) of the prediction's subject
+            pt, base = det
+            s = int(pred[0])
+            return {"base": self._labelled(base, s), "post": self._labelled(pt, s)}
+        # sufficient: one pair per conversion entity
+        return [{"entity": self.dataset.id_to_entity[e], "base": self._labelled(base, e), "post": self._labelled(pt, e)}
+                for e, (pt, base) in zip(self.engine.entities_to_convert, det)]
 
     def explore_singleton_rules(self, pred, triples: list):
         # one engine batch for every singleton; a duplicated candidate is evaluated
@@ -101,6 +139,7 @@ class StochasticBuilder:
         t0 = time.perf_counter()
         rels = self.engine.compute_relevance_batch(pred, [[t] for t in triples])
         self._account(t0)
+        self._keep_details([(t,) for t in triples], len(triples))
         self.stats["batches"] += 1
         self.stats["evaluated"] += len(triples)
         out = {}
@@ -163,6 +202,7 @@ class StochasticBuilder:
                 t0 = time.perf_counter()
                 rels = eng.compute_relevance_batch(pred, [list(r) for r in chunk], checkpoints=cps)
                 self._account(t0)
+            self._keep_details(chunk, len(rels))
             self.stats["batches"] += 1
             self.stats["evaluated"] += len(chunk)
             stop_at = None

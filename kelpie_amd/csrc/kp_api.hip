@@ -202,21 +202,37 @@ int kp_ctx_destroy(kp_ctx* c) {
   return KP_OK;
 }
 
-int kp_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b) {
+// kp_posttrain_rank and kp_posttrain_rank_topk (tk.k == 0: no lists).  The model's function
+// checks k and the list outputs itself, after the batch check and before its first upload.
+static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk) {
   if (!c || !hp || !b) return KP_EINVAL;
   return guarded(c, [&] {
     KP_REQUIRE(b->n_slots >= 0, "kp_posttrain_rank: negative n_slots");
-    if (b->n_slots == 0) return;
+    if (b->n_slots == 0) {
+      KP_REQUIRE(tk.k >= 0 && tk.k <= 32, "kp_posttrain_rank_topk: k must be in [0, 32]");
+      return;
+    }
     KP_REQUIRE(b->x0 && b->row_off && b->pred && b->filt_off && b->out_score && b->out_rank,
                "kp_posttrain_rank: missing buffer");
     KP_HIP(hipSetDevice(c->device));
     switch (c->model) {
-      case KP_MODEL_COMPLEX: complex_posttrain_rank(c, hp, b); break;
-      case KP_MODEL_DISTMULT: distmult_posttrain_rank(c, hp, b); break;
-      case KP_MODEL_TRANSE: transe_posttrain_rank(c, hp, b); break;
-      case KP_MODEL_CONVE: conve_posttrain_rank(c, hp, b); break;
+      case KP_MODEL_COMPLEX: complex_posttrain_rank(c, hp, b, tk); break;
+      case KP_MODEL_DISTMULT: distmult_posttrain_rank(c, hp, b, tk); break;
+      case KP_MODEL_TRANSE: transe_posttrain_rank(c, hp, b, tk); break;
+      case KP_MODEL_CONVE: conve_posttrain_rank(c, hp, b, tk); break;
     }
   });
+}
+
+int kp_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b) { return posttrain_rank_call(c, hp, b, {}); }
+
+int kp_posttrain_rank_topk(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k, int32_t* out_ids,
+                           float* out_scores) {
+  TopkOut tk;
+  tk.k = k;
+  tk.ids = out_ids;
+  tk.scores = out_scores;
+  return posttrain_rank_call(c, hp, b, tk);
 }
 
 int kp_all_scores(kp_ctx* c, int32_t n, const int32_t* heads, const int32_t* rels, float* out) {

@@ -125,7 +125,15 @@ struct RankWs {
   DevBuf q64, t64;        // fp64 ranking queries [ns][dp]; target | kelpie column scores [2][ns]
   DevBuf scores;          // fp32 score matrix [ns][ld] (KP_TE_RANK / KP_CV_RANK = f32)
   DevBuf bits;            // launch_rank_f64's filter bitmap (kp_rank.hip owns it)
-  auto all() { return std::array{&pred, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &scores, &bits}; }
+  // kp_posttrain_rank_topk (kp_rank.hip owns the first two): the waves' candidate lists
+  // [chunk slots][4 column blocks][k] (sort keys, columns) of one chunk of slots, and the
+  // final lists [ns][k]
+  DevBuf cand_key, cand_col;
+  DevBuf top_ids, top_scores;
+  auto all() {
+    return std::array{&pred, &po,   &filt_off, &filt,     &target,   &rank,    &q64,
+                      &t64,  &scores, &bits,   &cand_key, &cand_col, &top_ids, &top_scores};
+  }
 };
 KP_WS_COMPLETE(RankWs);
 
@@ -313,8 +321,16 @@ __device__ __forceinline__ float wave_max(float v) {
 // ----------------------------------------------------------------------------
 // entry points implemented per model family
 // ----------------------------------------------------------------------------
-void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b);
-void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b);  // kp_complex.hip, product policy
+// kp_posttrain_rank_topk's request: the k best unmasked columns of every slot into the
+// caller's ids / scores [n_slots][k]; k == 0 (no lists) is kp_posttrain_rank
+struct TopkOut {
+  int k = 0;
+  int32_t* ids = nullptr;
+  float* scores = nullptr;
+};
+void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
+// kp_complex.hip, product policy
+void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
 void complex_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rels, float* out);
 // scores of n (head, rel) pairs over the frozen entities into a device buffer [n][ld]
 // (complex_*: ComplEx and DistMult contexts, by the context's product)
@@ -323,9 +339,9 @@ void transe_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* 
 void conve_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* d_rels, float* d_out, int ld);
 void launch_convertible_reduce(kp_ctx* c, int n, const float* d_scores, int ld, int obj, const int32_t* d_fo,
                                const int32_t* d_f, int minimizer, uint8_t* d_keep);
-void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b);
+void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
 void transe_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rels, float* out);
-void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b);
+void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
 void conve_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rels, float* out);
 // ConvE encoder output (eval mode) of n (lhs, rel) pairs -> [n][dp] (criage_first_step, conve.py:102-124)
 void conve_encode_dev(kp_ctx* c, int n, const int2* d_src, float* d_out);
@@ -360,11 +376,15 @@ enum { RANK_TRIPLE_RESULTS = 0, RANK_PREDICT_TAILS = 1, RANK_SORT_POSITION = 2 }
 // kcol64 [n] the kelpie column scores q . x; rank = #{e not filtered : score_e >= target}
 // over the frozen entities (scores q . E_e summed in fp64, sequentially over d) plus the
 // kelpie column.  The target itself counts unless filtered.
+// topk > 0: also the topk best unmasked columns of every slot (better value first, equal
+// values by column), ids and converted scores into d_top_ids / d_top_scores [n][topk]
+// (device), -1 / 0 past the last unmasked column; the ranks are those of topk == 0
 // launch_rank_f64's score kinds
 enum { RANK64_DOT = 0, RANK64_SIGMOID = 1, RANK64_DIST = 2, RANK64_DIST1 = 3 };
 void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* d_t64, const double* d_kcol64,
                      const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt, float* d_target,
-                     int64_t* d_rank, int act = 0);
+                     int64_t* d_rank, int act = 0, int topk = 0, int32_t* d_top_ids = nullptr,
+                     float* d_top_scores = nullptr);
 void launch_rank_count(kp_ctx* c, int n_slots, const float* d_scores, int ld, int n_cols,
                        const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt,
                        int minimizer, float* d_target, int64_t* d_rank,

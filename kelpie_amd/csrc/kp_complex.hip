@@ -602,7 +602,7 @@ void launch_rankq64(kp_ctx* c, const float* X, const int32_t* pred, int n, doubl
 // KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time before the first upload (checks
 // and planning), up to the last launch enqueued, and waiting for the device
 template <class Prod>
-void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
+void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
   const std::string who = Prod::name;
   const double t_in = g_host_times ? host_ms() : 0.0;
   const int DBV = c->dp / 16;
@@ -614,6 +614,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   // every id is checked before it indexes a host vector or a device table, as in every
   // model family (kp_batch_check.hpp)
   require_batch(c, bt, Prod::name);
+  require_topk(tk, true, Prod::name);
 
   std::vector<CxPlan> plans;
   std::vector<CxQuery> pqs;
@@ -771,8 +772,9 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   int32_t* dTg = upload(c, c->cx.targets, targets.data(), targets.size());
   int2* dPairs = upload(c, c->cx.pairs, pairs.data(), pairs.size());
   int4* dActs = upload(c, c->cx.acts, acts.data(), acts.size());
-  int4* dStepQ = upload(c, c->cx.stepq, stepq.data(), std::max<size_t>(1, stepq.size()));
-  int4* dStepT = upload(c, c->cx.stept, stept.data(), std::max<size_t>(1, stept.size()));
+  // (empty without a step, epochs == 0: upload() then only sizes the buffer)
+  int4* dStepQ = upload(c, c->cx.stepq, stepq.data(), stepq.size());
+  int4* dStepT = upload(c, c->cx.stept, stept.data(), stept.size());
   float* dContrib = reinterpret_cast<float*>(c->cx.contrib.ensure(sizeof(float) * (size_t)std::max(1, max_items) * DP));
   const int npq = (int)pqs.size(), npairs = (int)pairs.size();
   float* dTsum = reinterpret_cast<float*>(c->cx.tsum.ensure(sizeof(float) * (size_t)std::max(npq, 1) * DP));
@@ -784,7 +786,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   // were enqueued only then (a host round trip per batch with the context idle)
   const Rank64Dev r64 = rank64_buffers(c, ns);
   int32_t* dPred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
-  const RankDev rk = upload_rank_inputs(c, bt);
+  const RankDev rk = upload_rank_inputs(c, bt, tk);
 
   const int half = Prod::extent(c->dim);
   KP_HIP(hipEventRecord(c->ev0, c->stream));
@@ -887,10 +889,11 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   // ---- ranking: scores of (kelpie, p, .) over E plus the kelpie column, in fp64
   // (launch_rank_f64: at the reference init the target's neighbours are ~1e-5 relative away)
   CX_DISPATCH(DBV, launch_rankq64<DB, Prod>(c, dX, dPred, ns, r64.q, r64.t, r64.kcol));
-  launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank);
+  launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_DOT, tk.k,
+                  rk.top_ids, rk.top_scores);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
 
-  const double t_enq = download_results(c, bt, dX, rk, xp);
+  const double t_enq = download_results(c, bt, dX, rk, xp, tk);
   const double t_done = g_host_times ? host_ms() : 0.0;
   if (g_host_times)
     std::fprintf(stderr,
@@ -910,8 +913,12 @@ int cx_pick_db(int dim) {
   return -1;
 }
 
-void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) { posttrain_rank<CxProd>(c, hp, bt); }
-void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) { posttrain_rank<DmProd>(c, hp, bt); }
+void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
+  posttrain_rank<CxProd>(c, hp, bt, tk);
+}
+void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
+  posttrain_rank<DmProd>(c, hp, bt, tk);
+}
 
 // scores of (head, relation) pairs against every entity; ComplEx and DistMult contexts
 void complex_scores_dev(kp_ctx* c, int n, const int32_t* dh, const int32_t* dr, float* dS, int ld) {

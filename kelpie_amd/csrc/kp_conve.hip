@@ -681,9 +681,10 @@ void conve_encode_dev(kp_ctx* c, int n, const int2* d_src, float* d_out) { encod
 
 // KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time of the planning, the uploads,
 // enqueueing the step loop, and the rank with the final wait
-void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
+void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
   const double t_in = g_host_times ? host_ms() : 0.0;
   require_batch(c, bt, "ConvE");
+  require_topk(tk, c->cv_rank64 != 0, "ConvE");
   const int ns = bt->n_slots;
   const int K = c->n_ent;
   const int DP = c->dp;
@@ -1194,13 +1195,14 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   int2* dRsrc = upload(c, c->cv.rank_src, rsrc.data(), rsrc.size());
   float* dQr = reinterpret_cast<float*>(c->cv.q.ensure(sizeof(float) * (size_t)std::max(ns, mk) * DP));
   encode_eval(c, ns, dRsrc, dX, dQr);
-  const RankDev rk = upload_rank_inputs(c, bt);
+  const RankDev rk = upload_rank_inputs(c, bt, tk);
   if (c->cv_rank64) {
     const Rank64Dev r64 = rank64_buffers(c, ns);
     hipLaunchKernelGGL(kp_cv_rankq64, dim3(ns), dim3(64), 0, c->stream, dQr, dX, c->dE, K, DP, rk.po, ns, r64.q, r64.t,
                        r64.kcol);
     KP_HIP(hipGetLastError());
-    launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_SIGMOID);
+    launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_SIGMOID,
+                    tk.k, rk.top_ids, rk.top_scores);
   } else {
     const int ld = round_up(K + 1, 4);
     float* dScores = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)ns * ld));
@@ -1210,7 +1212,7 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
     launch_rank_count(c, ns, dScores, ld, K + 1, rk.po, rk.filt_off, rk.filt, 0, rk.target, rk.rank);
   }
   KP_HIP(hipEventRecord(c->ev1, c->stream));
-  download_results(c, bt, dX, rk, xp);
+  download_results(c, bt, dX, rk, xp, tk);
   if (g_host_times)
     std::fprintf(stderr, "[kp_cv] slots %d steps %d pairs %zu: plan %.2f ms, uploads %.2f ms, loop enqueue %.2f ms, "
                  "rank + wait %.2f ms\n", ns, T, kinst.size(), t_plan - t_in, t_up - t_plan, t_loop - t_up,

@@ -25,6 +25,16 @@ inline void require_batch(const kp_ctx* c, const kp_batch* bt, const char* model
     throw KpError{KP_EINVAL, std::string(model) + ": " + why};
 }
 
+// kp_posttrain_rank_topk's k and outputs, checked right after the batch and before the first
+// upload.  `rank64`: the call ranks on launch_rank_f64's fp64 operands; the fp32 diagnostic
+// rank (KP_TE_RANK / KP_CV_RANK = f32) has none to select from
+inline void require_topk(const TopkOut& tk, bool rank64, const char* model) {
+  if (tk.k < 0 || tk.k > 32) throw KpError{KP_EINVAL, std::string(model) + ": top-k: k must be in [0, 32]"};
+  if (tk.k > 0 && (!tk.ids || !tk.scores)) throw KpError{KP_EINVAL, std::string(model) + ": top-k: missing output"};
+  if (tk.k > 0 && !rank64)
+    throw KpError{KP_ENOTSUP, std::string(model) + ": top-k needs the fp64 rank (the fp32 rank switch is set)"};
+}
+
 // x0 [ns][dim] zero-padded to [ns][dp] in `xp` (kept by the caller for download_results)
 // and uploaded into `b`
 inline float* upload_x0(kp_ctx* c, DevBuf& b, const kp_batch* bt, std::vector<float>& xp) {
@@ -42,11 +52,13 @@ struct RankDev {
   int32_t* filt;
   float* target;  // [ns]
   int64_t* rank;  // [ns]
+  int32_t* top_ids = nullptr;   // [ns][k] (kp_posttrain_rank_topk, k > 0)
+  float* top_scores = nullptr;  // [ns][k]
 };
 
 // upload the ranked objects and the filter CSR, size the result buffers.  The caller
 // chooses where in its call this happens: an upload's position decides what it overlaps.
-inline RankDev upload_rank_inputs(kp_ctx* c, const kp_batch* bt) {
+inline RankDev upload_rank_inputs(kp_ctx* c, const kp_batch* bt, const TopkOut& tk = {}) {
   const int ns = bt->n_slots;
   std::vector<int32_t> po(ns);
   for (int s = 0; s < ns; ++s) po[s] = bt->pred[3 * s + 2];
@@ -56,6 +68,10 @@ inline RankDev upload_rank_inputs(kp_ctx* c, const kp_batch* bt) {
   r.filt = upload(c, c->rank.filt, bt->filt, (size_t)bt->filt_off[ns]);
   r.target = reinterpret_cast<float*>(c->rank.target.ensure(sizeof(float) * (size_t)ns));
   r.rank = reinterpret_cast<int64_t*>(c->rank.rank.ensure(sizeof(int64_t) * (size_t)ns));
+  if (tk.k > 0) {
+    r.top_ids = reinterpret_cast<int32_t*>(c->rank.top_ids.ensure(sizeof(int32_t) * (size_t)ns * tk.k));
+    r.top_scores = reinterpret_cast<float*>(c->rank.top_scores.ensure(sizeof(float) * (size_t)ns * tk.k));
+  }
   return r;
 }
 
@@ -73,14 +89,20 @@ inline Rank64Dev rank64_buffers(kp_ctx* c, int ns) {
 }
 
 // the tail of a call: enqueue the downloads of the kelpie rows (when out_x is set), the
-// target scores and the ranks, wait for the stream once, unpad the rows into out_x.
+// target scores, the ranks and the top-k lists (when asked for), wait for the stream once,
+// unpad the rows into out_x.
 // Returns the host time at which the wait began (0 unless KP_HOST_TIMES).
 inline double download_results(kp_ctx* c, const kp_batch* bt, const float* dX, const RankDev& r,
-                               std::vector<float>& xp) {
+                               std::vector<float>& xp, const TopkOut& tk = {}) {
   const int ns = bt->n_slots;
   if (bt->out_x) KP_HIP(hipMemcpyAsync(xp.data(), dX, sizeof(float) * xp.size(), hipMemcpyDeviceToHost, c->stream));
   KP_HIP(hipMemcpyAsync(bt->out_score, r.target, sizeof(float) * ns, hipMemcpyDeviceToHost, c->stream));
   KP_HIP(hipMemcpyAsync(bt->out_rank, r.rank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
+  if (tk.k > 0) {
+    const size_t n = (size_t)ns * tk.k;
+    KP_HIP(hipMemcpyAsync(tk.ids, r.top_ids, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    KP_HIP(hipMemcpyAsync(tk.scores, r.top_scores, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+  }
   const double t_wait = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipStreamSynchronize(c->stream));
   if (bt->out_x)

@@ -246,14 +246,51 @@ __global__ void kp_rank_f64_kelpie(int n_slots, int n_ent, int nwords, const uin
                                         : (float)t64[s];  // DOT, DIST1
 }
 
+// ----------------------------------------------------------------------------
+// top-k tails (kp_posttrain_rank_topk): the k best unmasked columns of every slot, from the
+// values the rank compares.  A column's sort key is its fp64 value mapped to an unsigned
+// integer whose order is the value's (reversed for maximizers), so a smaller key is a
+// better column for every kind; keys tie only on equal values, and the lower column wins.
+// Masked or absent entries carry column -1 (as unsigned the largest: they sort last).
+// ----------------------------------------------------------------------------
+constexpr int TOPK_MAX = 32;
+__device__ __forceinline__ unsigned long long topk_key(double v, bool minimizer) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v + 0.0);  // -0 -> +0
+  const unsigned long long asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  return minimizer ? asc : ~asc;
+}
+__device__ __forceinline__ double topk_value(unsigned long long key, bool minimizer) {
+  const unsigned long long asc = minimizer ? key : ~key;
+  const unsigned long long u = (asc >> 63) ? (asc & 0x7fffffffffffffffull) : ~asc;
+  return __longlong_as_double((long long)u);
+}
+// (key, column) order: a before b
+__device__ __forceinline__ bool topk_before(unsigned long long ka, uint32_t ca, unsigned long long kb, uint32_t cb) {
+  return ka < kb || (ka == kb && ca < cb);
+}
+
 // MODE: RANK64_DOT (dot products, maximizer), RANK64_SIGMOID (dot products = logits, with
-// the saturated float32 sigmoid ties), RANK64_DIST (squared L2), RANK64_DIST1 (L1)
-template <int MODE>
+// the saturated float32 sigmoid ties), RANK64_DIST (squared L2), RANK64_DIST1 (L1).
+// TOPK: after the count, every wave sorts its 64 columns of each slot by (key, column)
+// across its lanes (a bitonic network of shuffles: no atomics, no LDS) and its first k
+// lanes write the wave's list [k] into top.cand_key / cand_col [slot][4 gridDim.x][k].  The
+// target's column carries t64, the value the count compares the others with.  Without TOPK
+// `top` is empty and the kernel is the count alone.
+template <bool TOPK>
+struct TopkArgs {};
+template <>
+struct TopkArgs<true> {
+  int k;
+  unsigned long long* cand_key;
+  int32_t* cand_col;
+};
+
+template <int MODE, bool TOPK = false>
 __global__ __launch_bounds__(256) void kp_rank_f64_count(int n_slots, int n_ent, int dp, const double* __restrict__ Q,
                                                          const double* __restrict__ t64,
                                                          const int32_t* __restrict__ pred_o, const float* __restrict__ ET,
                                                          int ldt, int nwords, const uint32_t* __restrict__ bits,
-                                                         unsigned long long* __restrict__ rank) {
+                                                         unsigned long long* __restrict__ rank, TopkArgs<TOPK> top) {
   __shared__ int part[4][RQ];
   const int s0 = blockIdx.y * RQ;
   const int e = blockIdx.x * 256 + threadIdx.x;  // < ldt: ET is zero-padded
@@ -304,11 +341,148 @@ __global__ __launch_bounds__(256) void kp_rank_f64_count(int n_slots, int n_ent,
     const int tot = part[0][j] + part[1][j] + part[2][j] + part[3][j];
     if (tot) atomicAdd(&rank[s0 + j], (unsigned long long)tot);
   }
+  if constexpr (TOPK) {
+    constexpr bool MINI = MODE == RANK64_DIST || MODE == RANK64_DIST1;
+    const size_t lists = (size_t)4 * gridDim.x;
+#pragma unroll
+    for (int j = 0; j < RQ; ++j) {
+      if (j < ns) {  // block-uniform
+        const int s = s0 + j;
+        unsigned long long key = ~0ull;
+        uint32_t col = 0xffffffffu;
+        if (e < n_ent) {
+          const bool filtered = (bits[(size_t)s * nwords + (e >> 5)] >> (e & 31)) & 1u;
+          const bool is_o = e == pred_o[s];
+          if (!filtered || (MINI && is_o)) {  // a minimizer's filtered target is restored
+            key = topk_key(is_o ? t64[s] : acc[j], MINI);
+            col = (uint32_t)e;
+          }
+        }
+        // ascending bitonic sort of the wave's 64 (key, column) pairs over its lanes
+#pragma unroll
+        for (int size = 2; size <= 64; size <<= 1) {
+#pragma unroll
+          for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const unsigned long long pk = __shfl_xor(key, stride, 64);
+            const uint32_t pc = __shfl_xor(col, stride, 64);
+            const bool want_min = ((lane & stride) == 0) == ((lane & size) == 0);
+            // distinct pairs: exactly one is before the other; equal pairs (absent entries) swap freely
+            const bool take = topk_before(pk, pc, key, col) == want_min;
+            key = take ? pk : key;
+            col = take ? pc : col;
+          }
+        }
+        if (lane < top.k) {
+          const size_t at = ((size_t)s * lists + (size_t)4 * blockIdx.x + w) * top.k + lane;
+          top.cand_key[at] = key;
+          top.cand_col[at] = (int32_t)col;
+        }
+      }
+    }
+  }
 }
+
+// merge of a slot's `lists` sorted wave lists [lists][k] plus the kelpie column into its final
+// list, one workgroup per slot.  The k best heads (first entries) name the only lists that
+// can hold one of the k best columns (a list whose head is not among the k best heads has k
+// better columns before any of its own), so: pick the k best heads, load those lists (at
+// most k * k entries), pick the k best of them.  Each pick is the block's minimum of
+// (key, column) after the previous pick: comparisons only, the same result on every run.
+__device__ __forceinline__ void topk_block_min(unsigned long long& key, uint32_t& col, uint32_t& pay,
+                                               unsigned long long* sk, uint32_t* sc, uint32_t* sp) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long pk = __shfl_xor(key, o, 64);
+    const uint32_t pc = __shfl_xor(col, o, 64);
+    const uint32_t pp = __shfl_xor(pay, o, 64);
+    if (topk_before(pk, pc, key, col)) key = pk, col = pc, pay = pp;
+  }
+  __syncthreads();  // the previous round's readers are done with sk / sc / sp
+  if (lane == 0) sk[w] = key, sc[w] = col, sp[w] = pay;
+  __syncthreads();
+  key = sk[0], col = sc[0], pay = sp[0];
+#pragma unroll
+  for (int i = 1; i < 4; ++i)
+    if (topk_before(sk[i], sc[i], key, col)) key = sk[i], col = sc[i], pay = sp[i];
+}
+
+__global__ __launch_bounds__(256) void kp_rank_topk_merge(int n_ent, int nwords, int lists, int k, int act,
+                                                          const unsigned long long* __restrict__ cand_key,
+                                                          const int32_t* __restrict__ cand_col,
+                                                          const uint32_t* __restrict__ bits,
+                                                          const int32_t* __restrict__ pred_o,
+                                                          const double* __restrict__ t64,
+                                                          const double* __restrict__ kcol64, int32_t* __restrict__ out_ids,
+                                                          float* __restrict__ out_scores) {
+  __shared__ unsigned long long sk[4];
+  __shared__ uint32_t sc[4], sp[4];
+  __shared__ int pick[TOPK_MAX];                          // the chosen lists (-1: none)
+  __shared__ unsigned long long lk[TOPK_MAX * TOPK_MAX];  // their entries
+  __shared__ uint32_t lc[TOPK_MAX * TOPK_MAX];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const bool mini = act == RANK64_DIST || act == RANK64_DIST1;
+  const unsigned long long* ck = cand_key + (size_t)s * lists * k;
+  const int32_t* cc = cand_col + (size_t)s * lists * k;
+  // phase 1: the k best heads
+  unsigned long long last_k = 0;
+  uint32_t last_c = 0;
+  for (int r = 0; r < k; ++r) {
+    unsigned long long bk = ~0ull;
+    uint32_t bc = 0xffffffffu, bl = 0xffffffffu;
+    for (int l = tid; l < lists; l += 256) {
+      const unsigned long long hk = ck[(size_t)l * k];
+      const uint32_t hc = (uint32_t)cc[(size_t)l * k];
+      if (hc != 0xffffffffu && (r == 0 || topk_before(last_k, last_c, hk, hc)) && topk_before(hk, hc, bk, bc))
+        bk = hk, bc = hc, bl = (uint32_t)l;
+    }
+    topk_block_min(bk, bc, bl, sk, sc, sp);
+    if (tid == 0) pick[r] = bc == 0xffffffffu ? -1 : (int)bl;
+    last_k = bk, last_c = bc;
+    // once the heads run out every later pick is empty too (bc stays -1: nothing is after it)
+  }
+  __syncthreads();
+  // phase 2: the chosen lists' entries, and the kelpie column as one more entry
+  for (int i = tid; i < k * k; i += 256) {
+    const int l = pick[i / k];
+    lk[i] = l < 0 ? ~0ull : ck[(size_t)l * k + i % k];
+    lc[i] = l < 0 ? 0xffffffffu : (uint32_t)cc[(size_t)l * k + i % k];
+  }
+  const bool kfilt = (bits[(size_t)s * nwords + (n_ent >> 5)] >> (n_ent & 31)) & 1u;
+  const bool k_is_o = pred_o[s] == n_ent;
+  const bool k_in = !kfilt || (mini && k_is_o);
+  const unsigned long long kk = k_in ? topk_key(k_is_o ? t64[s] : kcol64[s], mini) : ~0ull;
+  const uint32_t kc = k_in ? (uint32_t)n_ent : 0xffffffffu;
+  __syncthreads();
+  for (int r = 0; r < k; ++r) {
+    unsigned long long bk = ~0ull;
+    uint32_t bc = 0xffffffffu, bp = 0;
+    for (int i = tid; i <= k * k; i += 256) {
+      const unsigned long long ek = i < k * k ? lk[i] : kk;
+      const uint32_t ec = i < k * k ? lc[i] : kc;
+      if (ec != 0xffffffffu && (r == 0 || topk_before(last_k, last_c, ek, ec)) && topk_before(ek, ec, bk, bc))
+        bk = ek, bc = ec;
+    }
+    topk_block_min(bk, bc, bp, sk, sc, sp);
+    if (tid == 0) {
+      float sc32 = 0.f;
+      if (bc != 0xffffffffu) {
+        const double v = topk_value(bk, mini);
+        sc32 = act == RANK64_SIGMOID ? sigmoid_f32(v) : act == RANK64_DIST ? (float)sqrt(v) : (float)v;
+      }
+      out_ids[(size_t)s * k + r] = (int32_t)bc;
+      out_scores[(size_t)s * k + r] = sc32;
+    }
+    last_k = bk, last_c = bc;
+  }
+}
+
+// bytes of candidate workspace a launch may hold: the slots run in chunks of whole slot rows
+constexpr size_t TOPK_WS_BYTES = (size_t)64 << 20;
 
 void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* d_t64, const double* d_kcol64,
                      const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt, float* d_target,
-                     int64_t* d_rank, int act) {
+                     int64_t* d_rank, int act, int topk, int32_t* d_top_ids, float* d_top_scores) {
   if (n_slots <= 0) return;
   const int ldt = (c->n_ent + 255) / 256 * 256;
   if (!c->eT_ready) {
@@ -328,19 +502,54 @@ void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* 
   hipLaunchKernelGGL(kp_rank_f64_kelpie, dim3((n_slots + 63) / 64), dim3(64), 0, c->stream, n_slots, c->n_ent, nwords,
                      bits, d_pred_o, d_t64, d_kcol64, act, d_target, rank);
   KP_HIP(hipGetLastError());
+  if (topk > 0) {
+    // every wave of the scoring grid leaves a list of k candidates per slot (12 bytes each):
+    // the slots run in chunks of whole slot rows that keep the lists within TOPK_WS_BYTES
+    const int lists = 4 * (ldt / 256);
+    const size_t per_slot = (size_t)lists * topk;  // candidates
+    const int rows_fit = (int)std::max<size_t>(1, TOPK_WS_BYTES / (per_slot * 12 * RQ));
+    const int chunk = std::min(n_slots, rows_fit * RQ);
+    unsigned long long* ck =
+        reinterpret_cast<unsigned long long*>(c->rank.cand_key.ensure(sizeof(unsigned long long) * per_slot * chunk));
+    int32_t* cc = reinterpret_cast<int32_t*>(c->rank.cand_col.ensure(sizeof(int32_t) * per_slot * chunk));
+    for (int s0 = 0; s0 < n_slots; s0 += chunk) {
+      const int m = std::min(chunk, n_slots - s0);
+      const dim3 grid(ldt / 256, (m + RQ - 1) / RQ);
+      const double* q = d_q64 + (size_t)s0 * c->dp;
+      const uint32_t* b = bits + (size_t)s0 * nwords;
+#define KP_TOPK_LAUNCH(MODE)                                                                                       \
+  hipLaunchKernelGGL((kp_rank_f64_count<MODE, true>), grid, dim3(256), 0, c->stream, m, c->n_ent, c->dp, q,        \
+                     d_t64 + s0, d_pred_o + s0, c->eT.as<float>(), ldt, nwords, b, rank + s0, TopkArgs<true>{topk, ck, cc})
+      if (act == RANK64_DIST)
+        KP_TOPK_LAUNCH(RANK64_DIST);
+      else if (act == RANK64_DIST1)
+        KP_TOPK_LAUNCH(RANK64_DIST1);
+      else if (act == RANK64_SIGMOID)
+        KP_TOPK_LAUNCH(RANK64_SIGMOID);
+      else
+        KP_TOPK_LAUNCH(RANK64_DOT);
+#undef KP_TOPK_LAUNCH
+      KP_HIP(hipGetLastError());
+      hipLaunchKernelGGL(kp_rank_topk_merge, dim3(m), dim3(256), 0, c->stream, c->n_ent, nwords, lists, topk, act, ck,
+                         cc, b, d_pred_o + s0, d_t64 + s0, d_kcol64 + s0, d_top_ids + (size_t)s0 * topk,
+                         d_top_scores + (size_t)s0 * topk);
+      KP_HIP(hipGetLastError());
+    }
+    return;
+  }
   const dim3 grid(ldt / 256, (n_slots + RQ - 1) / RQ);
   if (act == RANK64_DIST)
     hipLaunchKernelGGL(kp_rank_f64_count<RANK64_DIST>, grid, dim3(256), 0, c->stream, n_slots, c->n_ent, c->dp, d_q64,
-                       d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank);
+                       d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank, TopkArgs<false>{});
   else if (act == RANK64_DIST1)
     hipLaunchKernelGGL(kp_rank_f64_count<RANK64_DIST1>, grid, dim3(256), 0, c->stream, n_slots, c->n_ent, c->dp, d_q64,
-                       d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank);
+                       d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank, TopkArgs<false>{});
   else if (act == RANK64_SIGMOID)
     hipLaunchKernelGGL(kp_rank_f64_count<RANK64_SIGMOID>, grid, dim3(256), 0, c->stream, n_slots, c->n_ent, c->dp,
-                       d_q64, d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank);
+                       d_q64, d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank, TopkArgs<false>{});
   else
     hipLaunchKernelGGL(kp_rank_f64_count<RANK64_DOT>, grid, dim3(256), 0, c->stream, n_slots, c->n_ent, c->dp, d_q64,
-                       d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank);
+                       d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank, TopkArgs<false>{});
   KP_HIP(hipGetLastError());
 }
 

@@ -510,11 +510,12 @@ __global__ void kp_te_rankq64(const float* __restrict__ X, const float* __restri
 
 }  // namespace
 
-void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
+void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
   const int ns = bt->n_slots;
   const int DP = c->dp;
   const bool l1 = c->te_norm == 1;
   require_batch(c, bt, "TransE");
+  require_topk(tk, c->te_rank64 != 0, "TransE");
   // before the first upload: the buffers below are sized by DP, the kernels hold DP / 256 float4 per lane
   KP_REQUIRE(DP <= 512, "TransE: dimension > 512 not supported");
   KP_REQUIRE(hp->neg_ratio >= 1 && hp->batch_size >= 1 && hp->epochs >= 0, "TransE: bad hyper-parameters");
@@ -601,7 +602,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
   for (int s = 0; s < ns; ++s) rels[s] = bt->pred[3 * s + 1];
   int32_t* dH = upload(c, c->te.heads, heads.data(), heads.size());
   int32_t* dRl = upload(c, c->te.rels, rels.data(), rels.size());
-  const RankDev rk = upload_rank_inputs(c, bt);
+  const RankDev rk = upload_rank_inputs(c, bt, tk);
   if (c->te_rank64) {
     int32_t* dPred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
     const Rank64Dev r64 = rank64_buffers(c, ns);
@@ -609,14 +610,14 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt) {
                        r64.q, r64.t, r64.kcol, l1 ? 1 : 0);
     KP_HIP(hipGetLastError());
     launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank,
-                    l1 ? RANK64_DIST1 : RANK64_DIST);
+                    l1 ? RANK64_DIST1 : RANK64_DIST, tk.k, rk.top_ids, rk.top_scores);
   } else {
     float* dScores = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)ns * ld));
     launch_te_scores(c, ns, dH, dRl, dX, dScores, ld, c->n_ent);
     launch_rank_count(c, ns, dScores, ld, c->n_ent + 1, rk.po, rk.filt_off, rk.filt, 1, rk.target, rk.rank);
   }
   KP_HIP(hipEventRecord(c->ev1, c->stream));
-  download_results(c, bt, dX, rk, xp);
+  download_results(c, bt, dX, rk, xp, tk);
   float ms_all = 0.f, ms_hot = 0.f;
   KP_HIP(hipEventElapsedTime(&ms_all, c->ev0, c->ev1));
   KP_HIP(hipEventElapsedTime(&ms_hot, ea, eb));

@@ -172,6 +172,28 @@ class PostTrainingEngine(RelevanceEngine):
             raise Exception("Already a post-trainable KelpieModel.")
         self.set_cache()
         self.last_batch_stats = {}
+        self._top_k = 0
+
+    TOP_K_MAX = 32  # kp_posttrain_rank_topk's largest k
+    _top_k = 0
+
+    @property
+    def top_k(self):
+        """How many of each post-training's best tails the device also reports (0: none, the
+        default; at most ``TOP_K_MAX``).  With ``top_k`` > 0 every slot's result gains
+        ``top_ids`` / ``top_scores``: what the post-trained row would predict for
+        (kelpie, p, .), best first, filtered entities left out as the rank leaves them out;
+        id ``num_entities`` is the kelpie entity itself.  The relevances, the draws and the
+        batches are those of ``top_k`` = 0."""
+        return self._top_k
+
+    @top_k.setter
+    def top_k(self, k):
+        if isinstance(k, bool) or int(k) != k:
+            raise TypeError(f"top_k must be an integer, got {k!r}")
+        if not 0 <= int(k) <= self.TOP_K_MAX:
+            raise ValueError(f"top_k must be in [0, {self.TOP_K_MAX}], got {k}")
+        self._top_k = int(k)
 
     def set_cache(self):
         self.base_pt_results = {}
@@ -451,6 +473,9 @@ class PostTrainingEngine(RelevanceEngine):
 
     def _schedule_all(self, items, checkpoints):
         """_schedule_multi, with every queued TransE call's draws made before it returns or raises."""
+        if self._top_k and self._sharded():
+            # before any draw: the gather's records hold a score and a rank per slot
+            raise NotImplementedError("top_k > 0 with a slot sharding: the lists are not gathered across ranks")
         self._sched = None  # this batch's natively assembled slots (TransE), made on first use
         if self._sharded():
             # ComplEx / ConvE: every rank owns one contiguous run of the batch's slots, so it
@@ -629,11 +654,23 @@ class PostTrainingEngine(RelevanceEngine):
         if gate is not None and not gate():
             return None
         t_lib = time.perf_counter()
-        score, rank, _ = ctx.posttrain_rank(self._kp_hp, *packed)
+        k = self._top_k
+        if k:
+            score, rank, _, (top_ids, top_scores) = ctx.posttrain_rank(self._kp_hp, *packed, topk=k)
+        else:
+            score, rank, _ = ctx.posttrain_rank(self._kp_hp, *packed)
         t_end = time.perf_counter()
         if fill:
             for i, s in enumerate(slots):
                 s.result = {"target_score": float(score[i]), "target_rank": int(rank[i])}
+            if k:
+                top_ids, top_scores = np.asarray(top_ids), np.asarray(top_scores)
+                # a list ends at its first -1 (fewer than k unmasked columns)
+                short = top_ids < 0
+                n_top = np.where(short.any(1), short.argmax(1), top_ids.shape[1])
+                for i, s in enumerate(slots):
+                    s.result["top_ids"] = top_ids[i, :n_top[i]].tolist()
+                    s.result["top_scores"] = top_scores[i, :n_top[i]].tolist()
         stats = {"slots": n, "rows": int(packed[1][-1]), "pack_s": t_lib - t_run, "lib_s": t_end - t_lib,
                  **ctx.last_timing()}
         if not fill:
@@ -658,6 +695,38 @@ class PostTrainingEngine(RelevanceEngine):
 
     def compute_relevance_batch(self, pred, rules, checkpoints: list | None = None):
         raise NotImplementedError
+
+    @staticmethod
+    def _cf_side(res, k):
+        """One post-training of a counterfactual: its target score and rank and its ``top``
+        list [(entity id, score)], None when the result was cached without one."""
+        ids = res.get("top_ids")
+        top = None if ids is None else list(zip(ids[:k], res["top_scores"][:k]))
+        return {"score": res["target_score"], "rank": res["target_rank"], "top": top}
+
+    def _cf_rule(self, relevance, detail, k):
+        raise NotImplementedError
+
+    def compute_counterfactuals(self, pred, rules, k: int):
+        """``compute_relevance_batch(pred, rules)`` -- the same schedule, draws, batches and
+        relevances, the generators left where it leaves them -- that also reports what the
+        model predicts instead: per rule ``{"relevance", "base", "post"}`` (the sufficient
+        engine: ``{"relevance", "conversions": [{"entity", "base", "post"}, ...]}``, one per
+        conversion entity), ``base`` / ``post`` = ``{"score", "rank", "top"}`` of the
+        post-training without / with the rule's edit, ``top`` the k best tails
+        [(entity id, score)] (``num_entities``: the kelpie entity).  No post-training runs for
+        the sake of a list: a base result cached while ``top_k`` was 0 reports ``"top": None``."""
+        if isinstance(k, bool) or int(k) != k:
+            raise TypeError(f"k must be an integer, got {k!r}")
+        if not 1 <= int(k) <= self.TOP_K_MAX:
+            raise ValueError(f"k must be in [1, {self.TOP_K_MAX}], got {k}")
+        old = self._top_k
+        self._top_k = max(old, int(k))
+        try:
+            rels = self.compute_relevance_batch(pred, rules)
+        finally:
+            self._top_k = old
+        return [self._cf_rule(rel, det, int(k)) for rel, det in zip(rels, self.last_results)]
 
     def _schedule_multi(self, items, checkpoints):
         raise NotImplementedError
@@ -1098,8 +1167,19 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
         return outs
 
 
+    def _cf_rule(self, relevance, detail, k):
+        pt, base = detail
+        return {"relevance": relevance, "base": self._cf_side(base, k), "post": self._cf_side(pt, k)}
+
+
 class SufficientPostTrainingEngine(PostTrainingEngine):
     """post_training_engine.py:160-207."""
+
+    def _cf_rule(self, relevance, detail, k):
+        # one (post-trained, base) pair per conversion entity, in entities_to_convert's order
+        return {"relevance": relevance,
+                "conversions": [{"entity": int(e), "base": self._cf_side(base, k), "post": self._cf_side(pt, k)}
+                                for e, (pt, base) in zip(self.entities_to_convert, detail)]}
 
     def __init__(self, model, dataset, hp, rng=None):
         super().__init__(model, dataset, hp, rng)

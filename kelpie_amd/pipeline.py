@@ -9,7 +9,8 @@ Mirrors the reference's callers of the relevance engine:
 * ``explain_preds`` / ``write_explanations`` (explain.py:190-203): the
   ``output.json`` list of ``{"triple", "rule_to_relevance", "#relevances",
   "execution_time"[, "entities_to_convert"]}`` records, rewritten after every
-  prediction as the reference does.
+  prediction as the reference does.  With ``top_k`` > 0 every record also holds
+  ``"counterfactuals"`` (kelpie_amd/builder.py): what the model predicts instead.
 
 The DP / CRIAGE baselines and summarisation are out of scope.
 """
@@ -52,7 +53,7 @@ class SufficientPipeline(Pipeline):
 
 
 def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="auto", entity_classes=None,
-                   pipelined=False):
+                   pipelined=False, top_k=0):
     """explain.py:49-89 for the post-training engines (baseline=None, no summarisation)."""
     if prefilter == TYPE_PREFILTER:
         raise NotImplementedError("type_based prefilter: out of scope (kelpie_amd/prefilters.py)")
@@ -61,11 +62,13 @@ def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="a
     if mode == "necessary":
         xsi = 5 if xsi is None else xsi
         engine = NecessaryPostTrainingEngine(model, dataset, hp)
-        return NecessaryPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined))
+        return NecessaryPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
+                                                                  top_k=top_k))
     if mode == "sufficient":
         xsi = 0.9 if xsi is None else xsi
         engine = SufficientPostTrainingEngine(model, dataset, hp)
-        return SufficientPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined))
+        return SufficientPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
+                                                                  top_k=top_k))
     raise ValueError(f"unknown mode {mode!r}")
 
 
@@ -134,7 +137,7 @@ def reference_construction_draws(model_name, num_entities, num_relations, model_
 
 
 def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefilter=None, prefilter_k=20,
-                xsi=None, skip=-1, output_path=None, device=0):
+                xsi=None, skip=-1, output_path=None, device=0, top_k=0):
     """explain.py main() (explain.py:143-203) without the CLI: seeds 42 (explain.py:144),
     the reference model construction's random draws (:171-172), the checkpoint state dict
     (``torch.load(path, weights_only=True)``, :174) as a frozen model on the MI355X, the
@@ -150,5 +153,5 @@ def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefi
     torch.manual_seed(42)
     reference_construction_draws(model_name, dataset.num_entities, dataset.num_relations, model_params)
     model = from_state_dict(model_name, dataset, state, model_params, device=device)
-    pipe = build_pipeline(model, dataset, hp, mode, prefilter=prefilter, xsi=xsi)
+    pipe = build_pipeline(model, dataset, hp, mode, prefilter=prefilter, xsi=xsi, top_k=top_k)
     return explain_preds(pipe, dataset, preds, prefilter_k=prefilter_k, skip=skip, output_path=output_path)
