@@ -11,7 +11,7 @@ LIB := kelpie_amd/libkelpie_hip.so
 
 all: $(LIB)
 
-build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn_plan.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp include/kelpie_hip.h
+build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn_plan.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp kelpie_amd/csrc/kp_cx_plan.hpp kelpie_amd/csrc/kp_cv_plan.hpp include/kelpie_hip.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -80,4 +80,17 @@ build/san/attn_plan_asan: tests/native/attn_plan_driver.cpp kelpie_amd/csrc/kp_a
 	@mkdir -p build/san
 	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
 
-.PHONY: asan tsan batch_asan attn_plan attn_plan_asan
+# the post-training step planners (kp_cx_plan.hpp, kp_cv_plan.hpp, no HIP) alone in
+# tests/native/step_plan_driver.cpp, plain and under the host sanitizers; run by
+# tests/test_step_plan.py (CPU suite)
+STEP_PLAN_DEP := tests/native/step_plan_driver.cpp kelpie_amd/csrc/kp_cx_plan.hpp kelpie_amd/csrc/kp_cv_plan.hpp include/kelpie_hip.h
+step_plan: build/san/step_plan
+step_plan_asan: build/san/step_plan_asan
+build/san/step_plan: $(STEP_PLAN_DEP)
+	@mkdir -p build/san
+	$(CXX) -O2 -std=c++17 -Wall $< -o $@
+build/san/step_plan_asan: $(STEP_PLAN_DEP)
+	@mkdir -p build/san
+	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
+
+.PHONY: asan tsan batch_asan attn_plan attn_plan_asan step_plan step_plan_asan

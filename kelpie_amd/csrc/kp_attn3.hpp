@@ -1097,6 +1097,29 @@ int attn3_wpc(kp_ctx* c) {
   return slot;
 }
 
+// Host: runs the statements with `DB` the compile-time constant of the padded row width
+// DBV = dp / 16, over the compiled widths (cx_pick_db's list).  DB_MIN: the narrowest width
+// the caller compiles (ComplEx / DistMult 1, ConvE 4); any other DBV throws KP_ENOTSUP
+// with MSG.
+#define KP_DB_CASE(N, DB_MIN, ...)   \
+  case N:                            \
+    if constexpr (N >= (DB_MIN)) {   \
+      constexpr int DB = N;          \
+      __VA_ARGS__;                   \
+    }                                \
+    break;
+#define KP_DB_DISPATCH(DBV, DB_MIN, MSG, ...)      \
+  switch ((DBV) >= (DB_MIN) ? (DBV) : -1) {        \
+    KP_DB_CASE(1, DB_MIN, __VA_ARGS__)             \
+    KP_DB_CASE(2, DB_MIN, __VA_ARGS__)             \
+    KP_DB_CASE(4, DB_MIN, __VA_ARGS__)             \
+    KP_DB_CASE(8, DB_MIN, __VA_ARGS__)             \
+    KP_DB_CASE(13, DB_MIN, __VA_ARGS__)            \
+    KP_DB_CASE(16, DB_MIN, __VA_ARGS__)            \
+    KP_DB_CASE(25, DB_MIN, __VA_ARGS__)            \
+    default: throw KpError{KP_ENOTSUP, MSG};       \
+  }
+
 // A/B switch (make diag): 1 lets the ConvE attention follow the in-flight hint too
 #ifndef KP_CV_ATTN_INFLIGHT
 #define KP_CV_ATTN_INFLIGHT 0

@@ -31,24 +31,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
-#include <unordered_map>
 
 #include "kp_attn.hpp"
 #include "kp_attn3.hpp"
+#include "kp_cx_plan.hpp"
 #include "kp_posttrain.hpp"
 
 namespace {
 using namespace kpattn;
-
-struct CxPlan {
-  int b, q_begin, q_count, t_begin, t_count, cnt_l, cnt_r, pad;
-};
-struct CxQuery {
-  int rel, c, ck, tg_begin, tg_count, pad0, pad1, pad2;
-};
-struct CxTail {
-  int pair, c;
-};
 
 // the ComplEx product from exact fp64 products of the fp32 operands (kp_cx_rankq64)
 __device__ __forceinline__ double cx_q64(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
@@ -584,246 +574,11 @@ void launch_rankq64(kp_ctx* c, const float* X, const int32_t* pred, int n, doubl
   KP_HIP(hipGetLastError());
 }
 
-#define CX_DISPATCH(DBV, ...)   \
-  switch (DBV) {                 \
-    case 1: { constexpr int DB = 1; __VA_ARGS__; } break;   \
-    case 2: { constexpr int DB = 2; __VA_ARGS__; } break;   \
-    case 4: { constexpr int DB = 4; __VA_ARGS__; } break;   \
-    case 8: { constexpr int DB = 8; __VA_ARGS__; } break;   \
-    case 13: { constexpr int DB = 13; __VA_ARGS__; } break; \
-    case 16: { constexpr int DB = 16; __VA_ARGS__; } break; \
-    case 25: { constexpr int DB = 25; __VA_ARGS__; } break; \
-    default: throw KpError{KP_ENOTSUP, "ComplEx / DistMult: unsupported padded dimension"}; \
-  }
+#define CX_DISPATCH(DBV, ...) \
+  KP_DB_DISPATCH(DBV, 1, "ComplEx / DistMult: unsupported padded dimension", __VA_ARGS__)
 
-// The batched post-training and rank of a model whose step is a 1-vs-all softmax over
-// q = lhs o rel (product policy Prod): planning, workspaces, attention planning and timing
-// are the model's only through Prod.
-// KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time before the first upload (checks
-// and planning), up to the last launch enqueued, and waiting for the device
-template <class Prod>
-void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
-  const std::string who = Prod::name;
-  const double t_in = g_host_times ? host_ms() : 0.0;
-  const int DBV = c->dp / 16;
-  const int K = c->n_ent;  // kelpie id
-  const int ns = bt->n_slots;
-  const int hpbs = hp->batch_size;
-  KP_REQUIRE(hpbs > 0 && hp->epochs >= 0, who + ": bad batch_size/epochs");
-  const int E = hp->epochs;
-  // every id is checked before it indexes a host vector or a device table, as in every
-  // model family (kp_batch_check.hpp)
-  require_batch(c, bt, Prod::name);
-  require_topk(tk, true, Prod::name);
-
-  std::vector<CxPlan> plans;
-  std::vector<CxQuery> pqs;
-  std::vector<CxTail> pts;
-  std::vector<int32_t> targets;
-  std::vector<int2> pairs;
-  std::unordered_map<int64_t, int> pair_id;
-  std::vector<int> plan_base(ns, 0), nsteps(ns, 0);
-
-  std::vector<int> rel_slot(c->n_rel2, -1);
-  std::vector<int> rel_cnt, rel_ck, rel_first;
-  std::unordered_map<int, int> tail_slot;
-  auto make_plan = [&](const int32_t* rows, const int32_t* idx, int n) {
-    CxPlan P{};
-    P.b = n;
-    P.q_begin = (int)pqs.size();
-    P.t_begin = (int)pts.size();
-    std::vector<int> rels;
-    tail_slot.clear();
-    // pass 1: group
-    std::vector<int> qtg_count;
-    for (int k = 0; k < n; ++k) {
-      const int32_t* rw = rows + 3 * (size_t)(idx ? idx[k] : k);
-      const int h = rw[0], r = rw[1], t = rw[2];
-      if (h == K) {
-        if (rel_slot[r] < 0) {
-          rel_slot[r] = (int)rels.size();
-          rels.push_back(r);
-          qtg_count.push_back(0);
-          pqs.push_back(CxQuery{r, 0, 0, 0, 0, 0, 0, 0});
-        }
-        CxQuery& Q = pqs[P.q_begin + rel_slot[r]];
-        Q.c += 1;
-        P.cnt_l += 1;
-        if (t == K) {
-          Q.ck += 1;
-          P.cnt_r += 1;
-        } else {
-          qtg_count[rel_slot[r]] += 1;
-        }
-      } else {
-        KP_REQUIRE(t == K, who + ": a training row does not involve the kelpie entity");
-        P.cnt_r += 1;
-        const int64_t key = (int64_t)h * c->n_rel2 + r;
-        auto it = pair_id.find(key);
-        int pid;
-        if (it == pair_id.end()) {
-          pid = (int)pairs.size();
-          pair_id.emplace(key, pid);
-          pairs.push_back(make_int2(h, r));
-        } else {
-          pid = it->second;
-        }
-        auto jt = tail_slot.find(pid);
-        if (jt == tail_slot.end()) {
-          tail_slot.emplace(pid, (int)pts.size());
-          pts.push_back(CxTail{pid, 1});
-        } else {
-          pts[jt->second].c += 1;
-        }
-      }
-    }
-    // pass 2: frozen targets grouped per query
-    int base = (int)targets.size();
-    for (size_t j = 0; j < rels.size(); ++j) {
-      pqs[P.q_begin + j].tg_begin = base;
-      pqs[P.q_begin + j].tg_count = 0;
-      base += qtg_count[j];
-    }
-    targets.resize(base);
-    for (int k = 0; k < n; ++k) {
-      const int32_t* rw = rows + 3 * (size_t)(idx ? idx[k] : k);
-      if (rw[0] == K && rw[2] != K) {
-        CxQuery& Q = pqs[P.q_begin + rel_slot[rw[1]]];
-        targets[Q.tg_begin + Q.tg_count++] = rw[2];
-      }
-    }
-    for (int r : rels) rel_slot[r] = -1;
-    P.q_count = (int)rels.size();
-    P.t_count = (int)pts.size() - P.t_begin;
-    plans.push_back(P);
-  };
-
-  int T = 0;
-  for (int s = 0; s < ns; ++s) {
-    const int r0 = bt->row_off[s], r1 = bt->row_off[s + 1];
-    const int R = r1 - r0;
-    const int32_t* rows = bt->rows + 3 * (size_t)r0;
-    plan_base[s] = (int)plans.size();
-    if (R == 0 || E == 0) {
-      nsteps[s] = 0;
-      continue;
-    }
-    const int nst = (R + hpbs - 1) / hpbs;
-    const int bs = std::min(hpbs, R);
-    nsteps[s] = nst;
-    if (nst == 1) {
-      make_plan(rows, nullptr, R);
-    } else {
-      const int64_t g0 = bt->rng_off[s], g1 = bt->rng_off[s + 1];
-      KP_REQUIRE(g1 - g0 >= (int64_t)E * R, who + ": missing randperm draws for a multi-step slot");
-      for (int e = 0; e < E; ++e) {
-        const int32_t* perm = bt->rng + g0 + (int64_t)e * R;
-        for (int j = 0; j < R; ++j) KP_REQUIRE(perm[j] >= 0 && perm[j] < R, who + ": randperm value out of range");
-        for (int j = 0; j < nst; ++j) {
-          const int st = j * hpbs;
-          const int n = std::min(bs, R - st);
-          make_plan(rows, perm + st, n);
-        }
-      }
-    }
-    T = std::max(T, E * nst);
-  }
-
-  // per-step active lists
-  std::vector<int> act_off(T + 1, 0), q_off(T + 1, 0), t_off(T + 1, 0);
-  std::vector<int4> acts;
-  std::vector<int4> stepq, stept;
-  int max_nq = 0, max_items = 0;
-  for (int t = 0; t < T; ++t) {
-    act_off[t] = (int)acts.size();
-    q_off[t] = (int)stepq.size();
-    t_off[t] = (int)stept.size();
-    int qo = 0, to = 0;
-    for (int s = 0; s < ns; ++s) {
-      const int nst = nsteps[s];
-      if (nst == 0 || t >= E * nst) continue;
-      const int plan = plan_base[s] + (nst == 1 ? 0 : t);
-      acts.push_back(make_int4(s, plan, qo, to));
-      const CxPlan& P = plans[plan];
-      for (int j = 0; j < P.q_count; ++j)
-        stepq.push_back(make_int4(s, pqs[P.q_begin + j].rel, P.q_begin + j, 0));
-      for (int j = 0; j < P.t_count; ++j) stept.push_back(make_int4(s, pts[P.t_begin + j].pair, pts[P.t_begin + j].c, 0));
-      qo += P.q_count;
-      to += P.t_count;
-    }
-    max_nq = std::max(max_nq, qo);
-    max_items = std::max(max_items, qo + to);
-  }
-  act_off[T] = (int)acts.size();
-  q_off[T] = (int)stepq.size();
-  t_off[T] = (int)stept.size();
-
-  const int DP = c->dp;
-  const double t_plan = g_host_times ? host_ms() : 0.0;
-  // ---- uploads
-  std::vector<float> xp;
-  float* dX = upload_x0(c, c->cx.x, bt, xp);
-  float* dS1 = reinterpret_cast<float*>(c->cx.s1.ensure(sizeof(float) * (size_t)ns * DP));
-  float* dS2 = reinterpret_cast<float*>(c->cx.s2.ensure(sizeof(float) * (size_t)ns * DP));
-  KP_HIP(hipMemsetAsync(dS1, 0, sizeof(float) * (size_t)ns * DP, c->stream));
-  KP_HIP(hipMemsetAsync(dS2, 0, sizeof(float) * (size_t)ns * DP, c->stream));
-  CxPlan* dPlans = upload(c, c->cx.plans, plans.data(), plans.size());
-  CxQuery* dPq = upload(c, c->cx.queries, pqs.data(), pqs.size());
-  int32_t* dTg = upload(c, c->cx.targets, targets.data(), targets.size());
-  int2* dPairs = upload(c, c->cx.pairs, pairs.data(), pairs.size());
-  int4* dActs = upload(c, c->cx.acts, acts.data(), acts.size());
-  // (empty without a step, epochs == 0: upload() then only sizes the buffer)
-  int4* dStepQ = upload(c, c->cx.stepq, stepq.data(), stepq.size());
-  int4* dStepT = upload(c, c->cx.stept, stept.data(), stept.size());
-  float* dContrib = reinterpret_cast<float*>(c->cx.contrib.ensure(sizeof(float) * (size_t)std::max(1, max_items) * DP));
-  const int npq = (int)pqs.size(), npairs = (int)pairs.size();
-  float* dTsum = reinterpret_cast<float*>(c->cx.tsum.ensure(sizeof(float) * (size_t)std::max(npq, 1) * DP));
-  float* dQpair = reinterpret_cast<float*>(c->cx.qpair.ensure(sizeof(float) * (size_t)std::max(npairs, 1) * DP));
-  float* dLsef = reinterpret_cast<float*>(c->cx.lsef.ensure(sizeof(float) * (size_t)std::max(npairs, 1)));
-
-  // the ranking's inputs and buffers now, ahead of the step loop: an upload from pageable
-  // memory after the loop waited for the whole loop on the device, so the rank kernels
-  // were enqueued only then (a host round trip per batch with the context idle)
-  const Rank64Dev r64 = rank64_buffers(c, ns);
-  int32_t* dPred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
-  const RankDev rk = upload_rank_inputs(c, bt, tk);
-
-  const int half = Prod::extent(c->dim);
-  KP_HIP(hipEventRecord(c->ev0, c->stream));
-  if (npq > 0) {
-    hipLaunchKernelGGL(kp_cx_tsum, dim3(npq), dim3(128), 0, c->stream, c->dE, DP, dPq, npq, dTg, dTsum);
-    KP_HIP(hipGetLastError());
-  }
-  // frozen-head pairs: q and frozen log-sum-exp
-  int slots_attn = 0;
-  CX_DISPATCH(DBV, slots_attn = attn_slots_db<DB>(c));
-  const AttnPlan plan_pairs = attn_plan_ctx(c, std::max(npairs, 1), c->n_ent, slots_attn, true);
-  const int split_pairs = plan_pairs.wk.n_parts;
-  size_t att_rows = (size_t)std::max(npairs, 1) * split_pairs;
-  std::vector<AttnPlan> step_plan(T);
-  c->attn_last = {};
-  for (int t = 0; t < T; ++t) {
-    const int nq = q_off[t + 1] - q_off[t];
-    step_plan[t] = attn_plan_ctx(c, std::max(nq, 1), c->n_ent, slots_attn, true);
-    if (nq > 0) attn_plan_note(c, step_plan[t], nq, true);
-    att_rows = std::max(att_rows, (size_t)nq * step_plan[t].wk.n_parts);
-  }
-  float* dAm = reinterpret_cast<float*>(c->cx.am.ensure(sizeof(float) * att_rows));
-  float* dAl = reinterpret_cast<float*>(c->cx.al.ensure(sizeof(float) * att_rows));
-  float* dAO = reinterpret_cast<float*>(c->cx.ao.ensure(sizeof(float) * att_rows * DP));
-  float* dQs = reinterpret_cast<float*>(c->cx.qs.ensure(sizeof(float) * (size_t)std::max(max_nq, 1) * DP));
-  if (npairs > 0) {
-    hipLaunchKernelGGL(kp_cx_qpair<Prod>, dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP, half, dPairs, npairs,
-                       dQpair);
-    KP_HIP(hipGetLastError());
-    CX_DISPATCH(DBV, launch_attn<DB>(c, false, dQpair, npairs, plan_pairs, dAm, dAl, nullptr));
-    // combine the splits into lsef on the device (no host round trip inside the batch)
-    hipLaunchKernelGGL(kp_cx_lse_merge, dim3((npairs + 255) / 256), dim3(256), 0, c->stream, npairs, split_pairs, dAm,
-                       dAl, dLsef);
-    KP_HIP(hipGetLastError());
-  }
-
-  // ---- the epoch/step loop
+// the optimizer's constants of a call (step_size and bc2_sqrt follow per step)
+CxOpt make_opt(const kp_hp* hp, const std::string& who) {
   CxOpt opt{};
   opt.kind = hp->optimizer;
   opt.lr = hp->lr;
@@ -835,6 +590,173 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   opt.reg_w = hp->reg_weight;
   KP_REQUIRE(hp->reg_kind == KP_REG_N3 || hp->reg_kind == KP_REG_N2, who + ": unknown regulariser");
   opt.reg_n2 = hp->reg_kind == KP_REG_N2;
+  return opt;
+}
+
+// the device side of one call: the plan's uploads and the workspaces (c->cx, c->rank)
+struct CxDev {
+  float *X, *S1, *S2;  // kelpie rows and optimizer state [ns][dp]
+  CxPlan* plans;
+  CxQuery* pq;
+  int32_t* tg;
+  int2* pairs;
+  int4 *acts, *stepq, *stept;
+  float *contrib, *tsum, *qpair, *lsef;
+  Rank64Dev r64;
+  int32_t* pred;
+  RankDev rk;
+  // the attention's: sized and planned by cx_preloop
+  float *am = nullptr, *al = nullptr, *ao = nullptr, *qs = nullptr;
+  std::vector<AttnPlan> step_plan;  // [T]
+};
+
+// the plan's element types are the HIP vector types' layout: their arrays are uploaded as such
+static_assert(sizeof(CxI2) == sizeof(int2) && alignof(CxI2) == alignof(int2), "CxI2 is int2");
+static_assert(sizeof(CxI4) == sizeof(int4) && alignof(CxI4) == alignof(int4), "CxI4 is int4");
+inline const int2* as_dev(const CxI2* p) { return reinterpret_cast<const int2*>(p); }
+inline const int4* as_dev(const CxI4* p) { return reinterpret_cast<const int4*>(p); }
+
+CxDev cx_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, const CxStepPlan& sp, std::vector<float>& xp) {
+  const int ns = bt->n_slots, DP = c->dp;
+  CxDev d;
+  d.X = upload_x0(c, c->cx.x, bt, xp);
+  d.S1 = reinterpret_cast<float*>(c->cx.s1.ensure(sizeof(float) * (size_t)ns * DP));
+  d.S2 = reinterpret_cast<float*>(c->cx.s2.ensure(sizeof(float) * (size_t)ns * DP));
+  KP_HIP(hipMemsetAsync(d.S1, 0, sizeof(float) * (size_t)ns * DP, c->stream));
+  KP_HIP(hipMemsetAsync(d.S2, 0, sizeof(float) * (size_t)ns * DP, c->stream));
+  d.plans = upload(c, c->cx.plans, sp.plans.data(), sp.plans.size());
+  d.pq = upload(c, c->cx.queries, sp.pqs.data(), sp.pqs.size());
+  d.tg = upload(c, c->cx.targets, sp.targets.data(), sp.targets.size());
+  d.pairs = upload(c, c->cx.pairs, as_dev(sp.pairs.data()), sp.pairs.size());
+  d.acts = upload(c, c->cx.acts, as_dev(sp.acts.data()), sp.acts.size());
+  // (empty without a step, epochs == 0: upload() then only sizes the buffer)
+  d.stepq = upload(c, c->cx.stepq, as_dev(sp.stepq.data()), sp.stepq.size());
+  d.stept = upload(c, c->cx.stept, as_dev(sp.stept.data()), sp.stept.size());
+  d.contrib = reinterpret_cast<float*>(c->cx.contrib.ensure(sizeof(float) * (size_t)std::max(1, sp.max_items) * DP));
+  const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
+  d.tsum = reinterpret_cast<float*>(c->cx.tsum.ensure(sizeof(float) * (size_t)std::max(npq, 1) * DP));
+  d.qpair = reinterpret_cast<float*>(c->cx.qpair.ensure(sizeof(float) * (size_t)std::max(npairs, 1) * DP));
+  d.lsef = reinterpret_cast<float*>(c->cx.lsef.ensure(sizeof(float) * (size_t)std::max(npairs, 1)));
+
+  // the ranking's inputs and buffers now, ahead of the step loop: an upload from pageable
+  // memory after the loop waited for the whole loop on the device, so the rank kernels
+  // were enqueued only then (a host round trip per batch with the context idle)
+  d.r64 = rank64_buffers(c, ns);
+  d.pred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
+  d.rk = upload_rank_inputs(c, bt, tk);
+  return d;
+}
+
+// before the loop: the queries' frozen-target sums, the attention plans and workspaces of
+// every step, and the frozen-head pairs' q and frozen log-sum-exp
+template <class Prod>
+void cx_preloop(kp_ctx* c, const CxStepPlan& sp, CxDev& d) {
+  const int DP = c->dp, DBV = DP / 16;
+  const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
+  KP_HIP(hipEventRecord(c->ev0, c->stream));
+  if (npq > 0) {
+    hipLaunchKernelGGL(kp_cx_tsum, dim3(npq), dim3(128), 0, c->stream, c->dE, DP, d.pq, npq, d.tg, d.tsum);
+    KP_HIP(hipGetLastError());
+  }
+  int slots_attn = 0;
+  CX_DISPATCH(DBV, slots_attn = attn_slots_db<DB>(c));
+  const AttnPlan plan_pairs = attn_plan_ctx(c, std::max(npairs, 1), c->n_ent, slots_attn, true);
+  const int split_pairs = plan_pairs.wk.n_parts;
+  size_t att_rows = (size_t)std::max(npairs, 1) * split_pairs;
+  d.step_plan.resize(sp.T);
+  c->attn_last = {};
+  for (int t = 0; t < sp.T; ++t) {
+    const int nq = sp.q_off[t + 1] - sp.q_off[t];
+    d.step_plan[t] = attn_plan_ctx(c, std::max(nq, 1), c->n_ent, slots_attn, true);
+    if (nq > 0) attn_plan_note(c, d.step_plan[t], nq, true);
+    att_rows = std::max(att_rows, (size_t)nq * d.step_plan[t].wk.n_parts);
+  }
+  d.am = reinterpret_cast<float*>(c->cx.am.ensure(sizeof(float) * att_rows));
+  d.al = reinterpret_cast<float*>(c->cx.al.ensure(sizeof(float) * att_rows));
+  d.ao = reinterpret_cast<float*>(c->cx.ao.ensure(sizeof(float) * att_rows * DP));
+  d.qs = reinterpret_cast<float*>(c->cx.qs.ensure(sizeof(float) * (size_t)std::max(sp.max_nq, 1) * DP));
+  if (npairs > 0) {
+    hipLaunchKernelGGL(kp_cx_qpair<Prod>, dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP, Prod::extent(c->dim),
+                       d.pairs, npairs, d.qpair);
+    KP_HIP(hipGetLastError());
+    CX_DISPATCH(DBV, launch_attn<DB>(c, false, d.qpair, npairs, plan_pairs, d.am, d.al, nullptr));
+    // combine the splits into lsef on the device (no host round trip inside the batch)
+    hipLaunchKernelGGL(kp_cx_lse_merge, dim3((npairs + 255) / 256), dim3(256), 0, c->stream, npairs, split_pairs, d.am,
+                       d.al, d.lsef);
+    KP_HIP(hipGetLastError());
+  }
+}
+
+// the epoch/step loop: per step the queries, their attention over the frozen entities and
+// the update of every active slot.  Returns the hot (attention) launches; t_steps: the host
+// time after enqueueing steps 0, 1, T/2, T-1 (KP_HOST_TIMES)
+template <class Prod>
+int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxDev& d, CxOpt opt, double* t_steps) {
+  const int DBV = c->dp / 16, T = sp.T;
+  int64_t hot_launches = 0;
+  c->hot_pairs.clear();
+  c->hot_iv.clear();
+  for (int t = 0; t < T; ++t) {
+    const int nq = sp.q_off[t + 1] - sp.q_off[t];
+    const int na = sp.act_off[t + 1] - sp.act_off[t];
+    const int sp_n = d.step_plan[t].wk.n_parts;
+    hipEvent_t ea = nullptr, eb = nullptr;
+    if (nq > 0 && c->time_hot) {
+      ea = c->event(2 * hot_launches);
+      eb = c->event(2 * hot_launches + 1);
+    }
+    CX_DISPATCH(DBV, launch_stepq<DB, Prod>(c, d.stepq + sp.q_off[t], d.X, nq, d.qs));
+    if (nq > 0 && c->time_hot) KP_HIP(hipEventRecord(ea, c->stream));
+    CX_DISPATCH(DBV, launch_attn<DB>(c, true, d.qs, nq, d.step_plan[t], d.am, d.al, d.ao));
+    if (nq > 0) {
+      if (c->time_hot) {
+        KP_HIP(hipEventRecord(eb, c->stream));
+        c->hot_pairs.push_back({(double)nq, 0.0});
+      }
+      ++hot_launches;
+    }
+    const AdamStep as = adam_step(hp, t);
+    opt.step_size = as.step_size;
+    opt.bc2_sqrt = as.bc2_sqrt;
+    CX_DISPATCH(DBV, launch_update<DB, Prod>(c, na, d.acts + sp.act_off[t], d.plans, d.pq, d.stepq + sp.q_off[t], nq,
+                                             d.stept + sp.t_off[t], sp.t_off[t + 1] - sp.t_off[t], d.tsum, d.qpair,
+                                             d.lsef, d.am, d.al, d.ao, sp_n, d.contrib, d.X, d.S1, d.S2, opt));
+    if (g_host_times) {
+      if (t == 0) t_steps[0] = host_ms();
+      if (t == 1) t_steps[1] = host_ms();
+      if (t == T / 2) t_steps[2] = host_ms();
+      if (t == T - 1) t_steps[3] = host_ms();
+    }
+  }
+  return hot_launches;
+}
+
+// The batched post-training and rank of a model whose step is a 1-vs-all softmax over
+// q = lhs o rel (product policy Prod): planning (kp_cx_plan.hpp), workspaces, attention
+// planning and timing are the model's only through Prod.
+// KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time before the first upload (checks
+// and planning), up to the last launch enqueued, and waiting for the device
+template <class Prod>
+void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
+  const std::string who = Prod::name;
+  const double t_in = g_host_times ? host_ms() : 0.0;
+  const int ns = bt->n_slots;
+  KP_REQUIRE(hp->batch_size > 0 && hp->epochs >= 0, who + ": bad batch_size/epochs");
+  // every id is checked before it indexes a host vector or a device table, as in every
+  // model family (kp_batch_check.hpp)
+  require_batch(c, bt, Prod::name);
+  require_topk(tk, true, Prod::name);
+  const CxOpt opt = make_opt(hp, who);
+
+  CxStepPlan sp;
+  if (const char* why = cx_step_plan(c->n_ent, c->n_rel2, hp->batch_size, hp->epochs, bt, sp))
+    throw KpError{KP_EINVAL, who + ": " + why};
+  const double t_plan = g_host_times ? host_ms() : 0.0;
+
+  std::vector<float> xp;
+  CxDev d = cx_workspaces(c, bt, tk, sp, xp);
+  cx_preloop<Prod>(c, sp, d);
+
   // loop-interval events, destroyed on every exit path (a KP_HIP / KP_REQUIRE below throws)
   struct LoopEvents {
     hipEvent_t a = nullptr, b = nullptr;
@@ -845,63 +767,28 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   } lev;
   KP_HIP(hipEventCreate(&lev.a));
   KP_HIP(hipEventCreate(&lev.b));
-  hipEvent_t h0 = lev.a, h1 = lev.b;
-  KP_HIP(hipEventRecord(h0, c->stream));
+  KP_HIP(hipEventRecord(lev.a, c->stream));
   const double t_loop0 = g_host_times ? host_ms() : 0.0;
-  double t_steps[4] = {0, 0, 0, 0};  // host time after enqueueing steps 0, 1, T/2, T-1
-  int64_t hot_launches = 0;
-  c->hot_pairs.clear();
-  c->hot_iv.clear();
-  for (int t = 0; t < T; ++t) {
-    const int nq = q_off[t + 1] - q_off[t];
-    const int na = act_off[t + 1] - act_off[t];
-    const int sp = step_plan[t].wk.n_parts;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (nq > 0 && c->time_hot) {
-      ea = c->event(2 * hot_launches);
-      eb = c->event(2 * hot_launches + 1);
-    }
-    CX_DISPATCH(DBV, launch_stepq<DB, Prod>(c, dStepQ + q_off[t], dX, nq, dQs));
-    if (nq > 0 && c->time_hot) KP_HIP(hipEventRecord(ea, c->stream));
-    CX_DISPATCH(DBV, launch_attn<DB>(c, true, dQs, nq, step_plan[t], dAm, dAl, dAO));
-    if (nq > 0) {
-      if (c->time_hot) {
-        KP_HIP(hipEventRecord(eb, c->stream));
-        c->hot_pairs.push_back({(double)nq, 0.0});
-      }
-      ++hot_launches;
-    }
-    const double step = (double)(t + 1);
-    opt.step_size = (float)((double)hp->lr / (1.0 - std::pow((double)hp->beta1, step)));
-    opt.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)hp->beta2, step));
-    CX_DISPATCH(DBV, launch_update<DB, Prod>(c, na, dActs + act_off[t], dPlans, dPq, dStepQ + q_off[t], nq,
-                                       dStepT + t_off[t], t_off[t + 1] - t_off[t], dTsum, dQpair, dLsef, dAm, dAl, dAO,
-                                       sp, dContrib, dX, dS1, dS2, opt));
-    if (g_host_times) {
-      if (t == 0) t_steps[0] = host_ms();
-      if (t == 1) t_steps[1] = host_ms();
-      if (t == T / 2) t_steps[2] = host_ms();
-      if (t == T - 1) t_steps[3] = host_ms();
-    }
-  }
-  KP_HIP(hipEventRecord(h1, c->stream));
+  double t_steps[4] = {0, 0, 0, 0};
+  const int64_t hot_launches = cx_step_loop<Prod>(c, hp, sp, d, opt, t_steps);
+  KP_HIP(hipEventRecord(lev.b, c->stream));
 
   // ---- ranking: scores of (kelpie, p, .) over E plus the kelpie column, in fp64
   // (launch_rank_f64: at the reference init the target's neighbours are ~1e-5 relative away)
-  CX_DISPATCH(DBV, launch_rankq64<DB, Prod>(c, dX, dPred, ns, r64.q, r64.t, r64.kcol));
-  launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_DOT, tk.k,
-                  rk.top_ids, rk.top_scores);
+  CX_DISPATCH(c->dp / 16, launch_rankq64<DB, Prod>(c, d.X, d.pred, ns, d.r64.q, d.r64.t, d.r64.kcol));
+  launch_rank_f64(c, ns, d.r64.q, d.r64.t, d.r64.kcol, d.rk.po, d.rk.filt_off, d.rk.filt, d.rk.target, d.rk.rank,
+                  RANK64_DOT, tk.k, d.rk.top_ids, d.rk.top_scores);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
 
-  const double t_enq = download_results(c, bt, dX, rk, xp, tk);
+  const double t_enq = download_results(c, bt, d.X, d.rk, xp, tk);
   const double t_done = g_host_times ? host_ms() : 0.0;
   if (g_host_times)
     std::fprintf(stderr,
                  "[kp_cx] slots %d steps %d: plan %.2f ms, enqueue %.2f ms (uploads+pairs %.2f, step 0 %.2f, step 1 "
                  "%.2f, to T/2 %.2f, to T-1 %.2f), wait %.2f ms\n",
-                 ns, T, t_plan - t_in, t_enq - t_plan, t_loop0 - t_plan, t_steps[0] - t_loop0, t_steps[1] - t_steps[0],
-                 t_steps[2] - t_steps[1], t_steps[3] - t_steps[2], t_done - t_enq);
-  record_hot_timing(c, hot_launches, h0, h1);
+                 ns, sp.T, t_plan - t_in, t_enq - t_plan, t_loop0 - t_plan, t_steps[0] - t_loop0,
+                 t_steps[1] - t_steps[0], t_steps[2] - t_steps[1], t_steps[3] - t_steps[2], t_done - t_enq);
+  record_hot_timing(c, hot_launches, lev.a, lev.b);
 }
 
 }  // namespace

@@ -23,11 +23,11 @@
 //   pairs with a frozen head reuse their precomputed FC output) -> Adam.
 #include <cstdio>
 #include <cmath>
-#include <unordered_map>
 
 #include "kp_attn.hpp"
 #include "kp_attn3.hpp"
 #include "kp_cv_fused.hpp"
+#include "kp_cv_plan.hpp"
 #include "kp_posttrain.hpp"
 
 int cx_pick_db(int dim);
@@ -35,19 +35,6 @@ int cx_pick_db(int dim);
 namespace {
 using namespace kpattn;
 
-using kpcvf::CvBits;
-struct CvInst {  // one kelpie pair in one step
-  int slot, rel, b, pos;
-  CvBits mb;
-  int tail_begin, tail_count;
-};
-struct CvFInst {  // one frozen-head pair in one step
-  int slot, fp, b, pos;  // fp: its FC row (per batch), or its encoded row in the step's Q (fr_step)
-  CvBits mb;
-};
-struct CvAct {
-  int slot, k_begin, k_count, f_begin, f_count, pad0, pad1, pad2;
-};
 struct CvConst {
   int n_ent, dim, dp, H, hid;
   float scale;  // hidden dropout: 1/(1-p) as float32 (the noise value of a kept element)
@@ -419,7 +406,6 @@ struct CvOpt {
 // column's BCE gradient G * x_fc, in chunks of up to FCH pairs of one slot, one workgroup per
 // chunk (a hub slot's hundreds of pairs no longer run as one workgroup's serial loop);
 // ch = (slot's act index in the step, first pair, pair count); fpart[chunk][d]
-constexpr int FCH = 16;
 __global__ __launch_bounds__(256) void kp_cv_fgrad(CvConst k, const int4* __restrict__ chunks,
                                                    const CvAct* __restrict__ act, const CvFInst* __restrict__ fi,
                                                    const float* __restrict__ fcf, const int32_t* __restrict__ bits,
@@ -677,355 +663,403 @@ static void conve_fused_images(kp_ctx* c, const __bf16** fw, const __bf16** bw) 
   *bw = c->cvf_bw3.as<__bf16>();
 }
 
+// the shared-encoder split's frozen terms (kp_cv_fused.hpp), once per context: the FC
+// weight's map-row slices and the relations' FC terms (map rows 20-37, the relation half
+// only, no bias) summed over NB_L bands.  dX / dBits: any valid kelpie rows / keep bits,
+// the relation sources read neither
+static void conve_shared_setup(kp_ctx* c, const __bf16* cvf_fw, const float* dX, const int32_t* dBits) {
+  if (c->cv_shared_ready) return;
+  constexpr int NB_L = 24;
+  float* wtm = reinterpret_cast<float*>(c->cv_wtm.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NMID));
+  hipLaunchKernelGGL(kpcvf::kp_cv_mid_wt, dim3((c->dim * kpcvf::NMID + 255) / 256), dim3(256), 0, c->stream,
+                     c->d_fc_w, c->dim, wtm);
+  KP_HIP(hipGetLastError());
+  float* wtl = reinterpret_cast<float*>(c->cv_wtl.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NLHS));
+  float* wlc = reinterpret_cast<float*>(c->cv_wlc.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NLHS));
+  float* wfm = reinterpret_cast<float*>(c->cv_wfm.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NMID));
+  const int nw = (kpcvf::NLHS + kpcvf::NMID) * c->dim;
+  hipLaunchKernelGGL(kpcvf::kp_cv_lhs_wt, dim3((nw + 255) / 256), dim3(256), 0, c->stream, c->d_fc_w, c->dim, wlc,
+                     wtl, wfm);
+  KP_HIP(hipGetLastError());
+  const int nr = c->n_rel2;
+  std::vector<int2> rs(nr);
+  for (int r = 0; r < nr; ++r) rs[r] = make_int2(0, r);
+  DevBuf bs, bo;
+  int2* dRs = upload(c, bs, rs.data(), rs.size());
+  float* sl = reinterpret_cast<float*>(bo.ensure(sizeof(float) * (size_t)NB_L * nr * c->dim));
+  const int g = NB_L * ((nr + kpcvf::MT - 1) / kpcvf::MT);
+  hipLaunchKernelGGL(kpcvf::kp_cv_fwd_fused<false>, dim3(g), dim3(512), kpcvf::FWD_LDS, c->stream, nr, dRs, c->dE,
+                     dX, c->dR, c->dp, c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, cvf_fw, nullptr, c->dim,
+                     nullptr, dBits, 1.0f, 1.0f, sl, nullptr, 8 * (kpcvf::MID_Y + 2),
+                     8 * (kpcvf::FR - kpcvf::MID_Y - 2), NB_L, 2);
+  KP_HIP(hipGetLastError());
+  float* tr = reinterpret_cast<float*>(c->cv_trel.ensure(sizeof(float) * (size_t)nr * c->dim));
+  hipLaunchKernelGGL(kpcvf::kp_cv_slab_sum, dim3((nr * c->dim + 255) / 256), dim3(256), 0, c->stream, nr, NB_L,
+                     c->dim, sl, tr);
+  KP_HIP(hipGetLastError());
+  KP_HIP(hipStreamSynchronize(c->stream));
+  bs.release();
+  bo.release();
+  c->cv_shared_ready = true;
+}
+
 void conve_encode_dev(kp_ctx* c, int n, const int2* d_src, float* d_out) { encode_eval(c, n, d_src, nullptr, d_out); }
 
-// KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time of the planning, the uploads,
-// enqueueing the step loop, and the rank with the final wait
-void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
-  const double t_in = g_host_times ? host_ms() : 0.0;
-  require_batch(c, bt, "ConvE");
-  require_topk(tk, c->cv_rank64 != 0, "ConvE");
-  const int ns = bt->n_slots;
-  const int K = c->n_ent;
-  const int DP = c->dp;
-  const int DBV = DP / 16;
-  KP_REQUIRE(hp->batch_size >= 1 && hp->epochs >= 0, "ConvE: bad hyper-parameters");
-  CvConst kc = make_const(c, hp);
-  const int E_ = hp->epochs;
+namespace {
 
-  // ---------------- host planning: er_vocab per slot (bce_optimizer.py:92-96)
-  struct Pair {
-    int h, r;
-    std::vector<int> tails;
-    int tail_begin = -1, tail_count = 0;  // kelpie pair: its distinct tails in `tails`; frozen: its FC row
-  };
-  std::vector<int2> fpairs;                // frozen (h, r) -> fc precompute
-  std::unordered_map<long long, int> fp_id;
-  std::vector<int32_t> tails;
-  std::vector<CvInst> kinst;
-  std::vector<CvFInst> finst;
-  std::vector<CvAct> acts;
-  // per slot: batches (pair ranges) and mask word offsets per step
-  struct SlotPlan {
-    std::vector<Pair> pairs;
-    int nb = 0;
-  };
-  std::vector<SlotPlan> plan(ns);
-  int T = 0;
-  for (int s = 0; s < ns; ++s) {
-    const int r0 = bt->row_off[s], r1 = bt->row_off[s + 1];
-    std::unordered_map<long long, int> idx;
-    auto& P = plan[s].pairs;
-    for (int j = r0; j < r1; ++j) {
-      const int h = bt->rows[3 * j], r = bt->rows[3 * j + 1], t = bt->rows[3 * j + 2];
-      const long long key = (long long)h * c->n_rel2 + r;
-      auto it = idx.find(key);
-      if (it == idx.end()) {
-        idx.emplace(key, (int)P.size());
-        P.push_back(Pair{h, r, {t}});
-      } else {
-        P[it->second].tails.push_back(t);
-      }
-    }
-    plan[s].nb = P.empty() ? 0 : (int)((P.size() + hp->batch_size - 1) / hp->batch_size);
-    T = std::max(T, E_ * plan[s].nb);
-    for (auto& pr : P)
-      if (pr.h != K) {
-        for (int tt : pr.tails) KP_REQUIRE(tt == K, "ConvE: a training row does not involve the kelpie entity");
-        const long long key = (long long)pr.h * c->n_rel2 + pr.r;
-        if (!fp_id.count(key)) {
-          fp_id.emplace(key, (int)fpairs.size());
-          fpairs.push_back(make_int2(pr.h, pr.r));
-        }
-      }
-  }
-  // keep-bit offsets: per slot, steps in order; per step one word-aligned run per drawn
-  // dropout, in the forward's order (input b x 2d, feature map b x 32, hidden b x d)
-  struct StepBits {
-    long long in, fm, hid;  // word offsets (-1: not drawn)
-  };
-  std::vector<std::vector<StepBits>> moff(ns);
-  for (int s = 0; s < ns; ++s) {
-    const int nb = plan[s].nb;
-    const int P = (int)plan[s].pairs.size();
-    long long off = bt->rng_off[s];
-    for (int t = 0; t < E_ * nb; ++t) {
-      const int j = t % nb;
-      const long long b = std::min(hp->batch_size, P - j * hp->batch_size);
-      StepBits sb{-1, -1, -1};
-      if (kc.has_in) { sb.in = off; off += (b * 2 * c->dim + 31) / 32; }
-      if (kc.has_fm) { sb.fm = off; off += (b * 32 + 31) / 32; }
-      if (kc.has_mask) { sb.hid = off; off += (b * c->dim + 31) / 32; }
-      moff[s].push_back(sb);
-    }
-    KP_REQUIRE(off <= bt->rng_off[s + 1], "ConvE: missing dropout keep bits");
-  }
-  auto pair_bits = [&](const StepBits& sb, int pos) {
-    return CvBits{sb.in < 0 ? -1 : 32 * sb.in + (long long)pos * 2 * c->dim,
-                  sb.fm < 0 ? -1 : 32 * sb.fm + (long long)pos * 32,
-                  sb.hid < 0 ? -1 : 32 * sb.hid + (long long)pos * c->dim};
-  };
-  // per-step instance lists; the step's encoder rows (kelpie pairs, then with fr_step the
-  // frozen-head pairs) with their keep-bit offsets
-  std::vector<int> kin_off(T + 1, 0), fin_off(T + 1, 0), act_o(T + 1, 0), enc_off(T + 1, 0);
-  std::vector<int2> enc_src;
-  std::vector<CvBits> enc_bits;
-  // the shared-encoder path's kelpie rows per step (one per slot with a kelpie pair in the
-  // step: its source and its pairs' range in the step's list), and per kelpie pair (its
-  // kelpie row, first pair of that row)
-  std::vector<int> sr_off(T + 1, 0);
-  // the frozen-head pairs' chunks per step (kp_cv_fgrad)
-  std::vector<int> fch_off(T + 1, 0);
-  std::vector<int4> fchunks;
-  int max_fch = 0;
-  std::vector<int2> sr_src, sr_rng, psr;
-  int max_k = 0, max_enc = 0, max_sr = 0;
-  for (int t = 0; t < T; ++t) {
-    kin_off[t] = (int)kinst.size();
-    fin_off[t] = (int)finst.size();
-    act_o[t] = (int)acts.size();
-    enc_off[t] = (int)enc_src.size();
-    std::vector<int2> fr_hr;  // the step's frozen-head (h, r), with fr_step
-    int local_k = 0;
-    sr_off[t] = (int)sr_src.size();
-    fch_off[t] = (int)fchunks.size();
-    for (int s = 0; s < ns; ++s) {
-      const int nb = plan[s].nb;
-      if (nb == 0 || t >= E_ * nb) continue;
-      const int j = t % nb;
-      auto& P = plan[s].pairs;
-      const int p0 = j * hp->batch_size, p1 = std::min((int)P.size(), p0 + hp->batch_size);
-      const int b = p1 - p0;
-      CvAct A{};
-      A.slot = s;
-      A.k_begin = local_k;
-      A.f_begin = (int)finst.size() - fin_off[t];
-      int my_sr = -1;
-      for (int q = p0; q < p1; ++q) {
-        auto& pr = P[q];
-        if (pr.h == K) {
-          const bool first = my_sr < 0;
-          if (first) {
-            my_sr = (int)sr_src.size() - sr_off[t];
-            sr_src.push_back(make_int2(-s - 1, 0));
-          }
-          psr.push_back(make_int2(my_sr, first ? 1 : 0));
-          CvInst I{};
-          I.slot = s;
-          I.rel = pr.r;
-          I.b = b;
-          I.pos = q - p0;
-          I.mb = pair_bits(moff[s][t], I.pos);
-          if (pr.tail_begin < 0) {  // the pair's distinct tails, stored once for every step
-            pr.tail_begin = (int)tails.size();
-            for (int tt : pr.tails)
-              if (std::find(tails.begin() + pr.tail_begin, tails.end(), tt) == tails.end()) tails.push_back(tt);
-            pr.tail_count = (int)tails.size() - pr.tail_begin;
-          }
-          I.tail_begin = pr.tail_begin;
-          I.tail_count = pr.tail_count;
-          kinst.push_back(I);
-          ++local_k;
-        } else {
-          CvFInst F{};
-          F.slot = s;
-          if (!kc.fr_step && pr.tail_begin < 0) pr.tail_begin = fp_id.at((long long)pr.h * c->n_rel2 + pr.r);
-          F.fp = kc.fr_step ? (int)finst.size() - fin_off[t] : pr.tail_begin;  // (frozen pair: its FC row)
-          F.b = b;
-          F.pos = q - p0;
-          F.mb = pair_bits(moff[s][t], F.pos);
-          finst.push_back(F);
-          if (kc.fr_step) fr_hr.push_back(make_int2(pr.h, pr.r));
-        }
-      }
-      A.k_count = local_k - A.k_begin;
-      A.f_count = (int)finst.size() - fin_off[t] - A.f_begin;
-      A.pad0 = (int)fchunks.size() - fch_off[t];
-      A.pad1 = (A.f_count + FCH - 1) / FCH;
-      for (int f = 0; f < A.f_count; f += FCH)
-        fchunks.push_back(make_int4((int)acts.size() - act_o[t], f, std::min(FCH, A.f_count - f), 0));
-      acts.push_back(A);
-      if (my_sr >= 0) sr_rng.push_back(make_int2(A.k_begin, A.k_begin + A.k_count));
-    }
-    max_sr = std::max(max_sr, (int)sr_src.size() - sr_off[t]);
-    max_fch = std::max(max_fch, (int)fchunks.size() - fch_off[t]);
-    for (int i = kin_off[t]; i < (int)kinst.size(); ++i) {
-      enc_src.push_back(make_int2(-kinst[i].slot - 1, kinst[i].rel));
-      enc_bits.push_back(kinst[i].mb);
-    }
-    if (kc.fr_step)
-      for (int i = fin_off[t]; i < (int)finst.size(); ++i) {
-        finst[i].fp += local_k;  // its row in the step's encoder output, after the kelpie pairs
-        enc_src.push_back(fr_hr[i - fin_off[t]]);
-        enc_bits.push_back(finst[i].mb);
-      }
-    max_k = std::max(max_k, local_k);
-    max_enc = std::max(max_enc, (int)enc_src.size() - enc_off[t]);
-  }
-  enc_off[T] = (int)enc_src.size();
-  sr_off[T] = (int)sr_src.size();
-  fch_off[T] = (int)fchunks.size();
-  kin_off[T] = (int)kinst.size();
-  fin_off[T] = (int)finst.size();
-  act_o[T] = (int)acts.size();
+// the plan's element types are the HIP vector types' layout: their arrays are uploaded as such
+static_assert(sizeof(CvI2) == sizeof(int2) && alignof(CvI2) == alignof(int2), "CvI2 is int2");
+static_assert(sizeof(CvI4) == sizeof(int4) && alignof(CvI4) == alignof(int4), "CvI4 is int4");
+// a plan list on the device, at least one element long (an empty list sizes the buffer only)
+template <class T>
+T* upload1(kp_ctx* c, DevBuf& b, const std::vector<T>& v) {
+  return upload(c, b, v.data(), std::max<size_t>(1, v.size()));
+}
+int2* upload1(kp_ctx* c, DevBuf& b, const std::vector<CvI2>& v) {
+  return upload(c, b, reinterpret_cast<const int2*>(v.data()), std::max<size_t>(1, v.size()));
+}
+int4* upload1(kp_ctx* c, DevBuf& b, const std::vector<CvI4>& v) {
+  return upload(c, b, reinterpret_cast<const int4*>(v.data()), std::max<size_t>(1, v.size()));
+}
+template <class T>
+T* ensure_n(DevBuf& b, size_t n) {
+  return reinterpret_cast<T*>(b.ensure(sizeof(T) * n));
+}
 
-  const double t_plan = g_host_times ? host_ms() : 0.0;
-  // ---------------- uploads
-  std::vector<float> xp;
-  float* dX = upload_x0(c, c->cv.x, bt, xp);
-  float* dS1 = reinterpret_cast<float*>(c->cv.s1.ensure(sizeof(float) * xp.size()));
-  float* dS2 = reinterpret_cast<float*>(c->cv.s2.ensure(sizeof(float) * xp.size()));
-  KP_HIP(hipMemsetAsync(dS1, 0, sizeof(float) * xp.size(), c->stream));
-  KP_HIP(hipMemsetAsync(dS2, 0, sizeof(float) * xp.size(), c->stream));
-  CvInst* dKI = upload(c, c->cv.kinst, kinst.data(), std::max<size_t>(1, kinst.size()));
-  CvFInst* dFI = upload(c, c->cv.finst, finst.data(), std::max<size_t>(1, finst.size()));
-  CvAct* dAct = upload(c, c->cv.acts, acts.data(), std::max<size_t>(1, acts.size()));
-  int32_t* dTails = upload(c, c->cv.tails, tails.data(), std::max<size_t>(1, tails.size()));
-  const int64_t nbits = bt->rng_off[ns];
+// the device side of one call (c->cv): the plan's uploads (cv_workspaces), the frozen-head
+// pairs' FC rows (cv_frozen_fc) and the step workspaces (cv_step_workspaces)
+struct CvDev {
+  float *X, *S1, *S2;  // kelpie rows and Adam state [ns][dp]
+  CvInst* KI;
+  CvFInst* FI;
+  CvAct* act;
+  int32_t *tails, *bits;
+  float* fcf = nullptr;  // frozen-head pairs' FC output (pre-dropout), once per batch
+  bool fused = false;    // fused encoder kernels (kp_cv_fused.hpp) for d = 200: the feature map stays on chip
+  bool shared = false;   // the shared-encoder split: kelpie rows' map rows 0-17, the pairs' rows 18-19
+  int KS, mk, me, msr;   // FC forward split-K; kelpie pairs, encoder rows, shared rows per step (>= 1)
+  float *flat, *slab, *Q;
+  const __bf16 *fw = nullptr, *bw = nullptr;
+  uint8_t* relu = nullptr;
+  __bf16* g3 = nullptr;
+  int2 *sr_src = nullptr, *sr_rng = nullptr, *psr = nullptr;
+  uint8_t* relu_s = nullptr;
+  float* slab_l = nullptr;  // kelpie rows' FC split-K slabs [KSL][rows][dim]
+  float* mid = nullptr;     // pairs' map-row-18-19 FC terms [pairs][dim]
+  float* map_l = nullptr;   // kelpie rows' map rows 0-17, then (backward) g W_lhs
+  float* map_m = nullptr;   // pairs' map rows 18-19, then (backward) dfc W_mid [pairs][512]
+  float* gs = nullptr;      // kelpie rows' summed pair dfc
+  float* dls = nullptr;     // kelpie rows' lhs image gradient [rows][DP]
+  int2* src;
+  int4* fch;
+  float* fpart;
+  CvBits* enc_bits;
+  float* gscale;
+  std::vector<AttnPlan> step_plan;  // [T]
+  float *O, *dfc, *gk, *dflat, *dl, *wt;
+  float s_in, s_fm;  // the masks' multipliers as the fused kernels take them (1: not drawn)
+};
+
+CvDev cv_workspaces(kp_ctx* c, const kp_batch* bt, const CvStepPlan& sp, std::vector<float>& xp) {
+  CvDev d;
+  d.X = upload_x0(c, c->cv.x, bt, xp);
+  d.S1 = ensure_n<float>(c->cv.s1, xp.size());
+  d.S2 = ensure_n<float>(c->cv.s2, xp.size());
+  KP_HIP(hipMemsetAsync(d.S1, 0, sizeof(float) * xp.size(), c->stream));
+  KP_HIP(hipMemsetAsync(d.S2, 0, sizeof(float) * xp.size(), c->stream));
+  d.KI = upload1(c, c->cv.kinst, sp.kinst);
+  d.FI = upload1(c, c->cv.finst, sp.finst);
+  d.act = upload1(c, c->cv.acts, sp.acts);
+  d.tails = upload1(c, c->cv.tails, sp.tails);
+  const int64_t nbits = bt->rng_off[bt->n_slots];
   // the keep bits, plus one zero guard word (kp_cv_fwd_fused reads a row's input bits as
   // a 64-bit window)
-  int32_t* dBits = reinterpret_cast<int32_t*>(c->cv.keep_bits.ensure(sizeof(int32_t) * (size_t)(nbits + 2)));
+  d.bits = ensure_n<int32_t>(c->cv.keep_bits, (size_t)(nbits + 2));
   if (nbits > 0)
-    KP_HIP(hipMemcpyAsync(dBits, bt->rng, sizeof(int32_t) * (size_t)nbits, hipMemcpyHostToDevice, c->stream));
-  KP_HIP(hipMemsetAsync(dBits + nbits, 0, 2 * sizeof(int32_t), c->stream));
-  const int nfp = kc.fr_step ? 0 : (int)fpairs.size();
+    KP_HIP(hipMemcpyAsync(d.bits, bt->rng, sizeof(int32_t) * (size_t)nbits, hipMemcpyHostToDevice, c->stream));
+  KP_HIP(hipMemsetAsync(d.bits + nbits, 0, 2 * sizeof(int32_t), c->stream));
+  return d;
+}
 
-  const double t_up = g_host_times ? host_ms() : 0.0;
-  KP_HIP(hipEventRecord(c->ev0, c->stream));
-  // frozen-head pairs without an input / feature-map dropout: FC output (pre-dropout)
-  // once per batch
-  float* dFcf = reinterpret_cast<float*>(c->cv.fcf.ensure(sizeof(float) * (size_t)std::max(1, nfp) * c->dim));
+// frozen-head pairs without an input / feature-map dropout: FC output (pre-dropout) once
+// per batch.  Returns the rows it encoded
+int cv_frozen_fc(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, CvDev& d) {
+  const int nfp = kc.fr_step ? 0 : (int)sp.fpairs.size();
+  d.fcf = ensure_n<float>(c->cv.fcf, (size_t)std::max(1, nfp) * c->dim);
   if (nfp > 0) {
-    int2* dFp = upload(c, c->cv.fpairs, fpairs.data(), fpairs.size());
-    float* dflat = reinterpret_cast<float*>(c->cv.flat.ensure(sizeof(float) * (size_t)nfp * c->hidden));
-    KP_CONV_FWD(dim3(nfp), dim3(256), 0, c->stream, nfp, dFp, c->dE, dX, c->dR, kc,
-                       c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, nullptr, nullptr, dflat);
+    int2* dFp = upload(c, c->cv.fpairs, reinterpret_cast<const int2*>(sp.fpairs.data()), sp.fpairs.size());
+    float* dflat = ensure_n<float>(c->cv.flat, (size_t)nfp * c->hidden);
+    KP_CONV_FWD(dim3(nfp), dim3(256), 0, c->stream, nfp, dFp, c->dE, d.X, c->dR, kc, c->d_conv_w, c->d_conv_b,
+                c->d_bn_a, c->d_bn_b, nullptr, nullptr, dflat);
     KP_HIP(hipGetLastError());
-    launch_gemm_abt(c, dflat, c->hidden, nfp, c->d_fc_w, c->hidden, c->dim, c->hidden, dFcf, c->dim, c->d_fc_b, 0, 1);
+    launch_gemm_abt(c, dflat, c->hidden, nfp, c->d_fc_w, c->hidden, c->dim, c->hidden, d.fcf, c->dim, c->d_fc_b, 0, 1);
   }
-  // step workspaces
-  // fused encoder kernels (kp_cv_fused.hpp) for d = 200: the feature map stays on chip
-  const bool fused = c->cv_fused && c->dim == 200 && c->hidden == kpcvf::HID;
-  const int KS = fused ? kpcvf::NSPLIT : 8;  // split-K of the FC forward
-  const int mk = std::max(1, max_k);
-  const int me = std::max(1, max_enc);  // encoder rows per step (kelpie pairs + per-step frozen pairs)
-  float* dflat = reinterpret_cast<float*>(c->cv.flat.ensure(sizeof(float) * (size_t)std::max(fused ? 1 : me, nfp) * c->hidden));
-  float* dslab = reinterpret_cast<float*>(c->cv.slab.ensure(sizeof(float) * (size_t)KS * me * c->dim));
-  const __bf16* cvf_fw = nullptr;
-  const __bf16* cvf_bw = nullptr;
-  uint8_t* dRelu = nullptr;
-  __bf16* dG3 = nullptr;
-  if (fused) {
-    conve_fused_images(c, &cvf_fw, &cvf_bw);
-    dRelu = reinterpret_cast<uint8_t*>(c->cv.relu.ensure((size_t)me * kpcvf::MASK_B));
-    dG3 = reinterpret_cast<__bf16*>(c->cv.g3.ensure(3 * sizeof(__bf16) * (size_t)mk * kpcvf::KB));
+  return nfp;
+}
+
+// the attention plan of every step and its O rows
+void cv_attn_plans(kp_ctx* c, const CvStepPlan& sp, CvDev& d) {
+  const int DBV = c->dp / 16;
+  int attn_slots = c->n_cu * (DBV <= 13 ? 2 : 1);  // co-resident attention workgroups
+  if (c->attn_mode == 1) {
+    KP_DB_DISPATCH(DBV, 4, "ConvE: unsupported padded dimension",
+                   attn_slots = c->n_cu * attn3_wpc<DB, ATT_BCE_O>(c));
+  }
+  d.step_plan.resize(sp.T);
+  size_t o_rows = 1;
+  c->attn_last = {};
+  for (int t = 0; t < sp.T; ++t) {
+    const int nk = sp.kin_off[t + 1] - sp.kin_off[t];
+    // the ConvE attention (ATT_BCE_O, two workgroups per CU) keeps the plan of a launch that
+    // runs alone whatever the context's in-flight hint says (DESIGN.md section 5)
+    d.step_plan[t] = attn_plan_ctx(c, std::max(nk, 1), c->n_ent, attn_slots, KP_CV_ATTN_INFLIGHT != 0);
+    if (nk > 0) attn_plan_note(c, d.step_plan[t], nk, KP_CV_ATTN_INFLIGHT != 0);
+    o_rows = std::max(o_rows, (size_t)nk * d.step_plan[t].wk.n_parts);
+  }
+  d.O = ensure_n<float>(c->cv.o, o_rows * c->dp);
+}
+
+// the step loop's workspaces and the rest of the plan's uploads; nfp: cv_frozen_fc's rows
+// (c->cv.flat still holds them)
+void cv_step_workspaces(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, int nfp, CvDev& d) {
+  const int DP = c->dp, K = c->n_ent;
+  d.fused = c->cv_fused && c->dim == 200 && c->hidden == kpcvf::HID;
+  d.KS = d.fused ? kpcvf::NSPLIT : 8;
+  d.mk = std::max(1, sp.max_k);
+  d.me = std::max(1, sp.max_enc);  // encoder rows per step (kelpie pairs + per-step frozen pairs)
+  d.msr = std::max(1, sp.max_sr);
+  const int mk = d.mk, me = d.me, msr = d.msr;
+  d.flat = ensure_n<float>(c->cv.flat, (size_t)std::max(d.fused ? 1 : me, nfp) * c->hidden);
+  d.slab = ensure_n<float>(c->cv.slab, (size_t)d.KS * me * c->dim);
+  if (d.fused) {
+    conve_fused_images(c, &d.fw, &d.bw);
+    d.relu = reinterpret_cast<uint8_t*>(c->cv.relu.ensure((size_t)me * kpcvf::MASK_B));
+    d.g3 = ensure_n<__bf16>(c->cv.g3, 3 * (size_t)mk * kpcvf::KB);
   }
   // the shared-encoder split (kp_cv_fused.hpp): kelpie rows' map rows 0-17 in NB_L bands,
   // the pairs' rows 18-19 in NB_M, the relations' rows 20-37 (once per context) in NB_L
-  const bool shared = fused && c->cv_shared && !kc.has_in && !kc.has_fm;
-  constexpr int NB_L = 24;
-  const int msr = std::max(1, max_sr);
-  int2* dSrSrc = nullptr;
-  int2* dSrRng = nullptr;
-  int2* dPsr = nullptr;
-  uint8_t* dReluS = nullptr;
-  float* dSlabL = nullptr;  // kelpie rows' FC split-K slabs [KSL][rows][dim]
-  float* dMid = nullptr;    // pairs' map-row-18-19 FC terms [pairs][dim]
-  float* dMapL = nullptr;   // kelpie rows' map rows 0-17, then (backward) g W_lhs
-  float* dMapM = nullptr;   // pairs' map rows 18-19, then (backward) dfc W_mid [pairs][512]
-  float* dGs = nullptr;     // kelpie rows' summed pair dfc
-  float* dDls = nullptr;    // kelpie rows' lhs image gradient [rows][DP]
-  if (shared) {
-    if (!c->cv_shared_ready) {
-      float* wtm = reinterpret_cast<float*>(c->cv_wtm.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NMID));
-      hipLaunchKernelGGL(kpcvf::kp_cv_mid_wt, dim3((c->dim * kpcvf::NMID + 255) / 256), dim3(256), 0, c->stream,
-                         c->d_fc_w, c->dim, wtm);
-      KP_HIP(hipGetLastError());
-      float* wtl = reinterpret_cast<float*>(c->cv_wtl.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NLHS));
-      float* wlc = reinterpret_cast<float*>(c->cv_wlc.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NLHS));
-      float* wfm = reinterpret_cast<float*>(c->cv_wfm.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NMID));
-      const int nw = (kpcvf::NLHS + kpcvf::NMID) * c->dim;
-      hipLaunchKernelGGL(kpcvf::kp_cv_lhs_wt, dim3((nw + 255) / 256), dim3(256), 0, c->stream, c->d_fc_w, c->dim, wlc,
-                         wtl, wfm);
-      KP_HIP(hipGetLastError());
-      // the relations' FC terms: map rows 20-37 (the relation half only), no bias
-      const int nr = c->n_rel2;
-      std::vector<int2> rs(nr);
-      for (int r = 0; r < nr; ++r) rs[r] = make_int2(0, r);
-      DevBuf bs, bo;
-      int2* dRs = upload(c, bs, rs.data(), rs.size());
-      float* sl = reinterpret_cast<float*>(bo.ensure(sizeof(float) * (size_t)NB_L * nr * c->dim));
-      const int g = NB_L * ((nr + kpcvf::MT - 1) / kpcvf::MT);
-      hipLaunchKernelGGL(kpcvf::kp_cv_fwd_fused<false>, dim3(g), dim3(512), kpcvf::FWD_LDS, c->stream, nr, dRs, c->dE,
-                         dX, c->dR, DP, c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, cvf_fw, nullptr, c->dim,
-                         nullptr, dBits, 1.0f, 1.0f, sl, nullptr, 8 * (kpcvf::MID_Y + 2),
-                         8 * (kpcvf::FR - kpcvf::MID_Y - 2), NB_L, 2);
-      KP_HIP(hipGetLastError());
-      float* tr = reinterpret_cast<float*>(c->cv_trel.ensure(sizeof(float) * (size_t)nr * c->dim));
-      hipLaunchKernelGGL(kpcvf::kp_cv_slab_sum, dim3((nr * c->dim + 255) / 256), dim3(256), 0, c->stream, nr, NB_L,
-                         c->dim, sl, tr);
-      KP_HIP(hipGetLastError());
-      KP_HIP(hipStreamSynchronize(c->stream));
-      bs.release();
-      bo.release();
-      c->cv_shared_ready = true;
-    }
-    dSrSrc = upload(c, c->cv.sr_src, sr_src.data(), std::max<size_t>(1, sr_src.size()));
-    dSrRng = upload(c, c->cv.sr_rng, sr_rng.data(), std::max<size_t>(1, sr_rng.size()));
-    dPsr = upload(c, c->cv.psr, psr.data(), std::max<size_t>(1, psr.size()));
-    dReluS = reinterpret_cast<uint8_t*>(c->cv.relu_s.ensure((size_t)msr * kpcvf::MASK_B));
-    KP_HIP(hipMemsetAsync(dReluS, 0, (size_t)msr * kpcvf::MASK_B, c->stream));  // rows 18-19 stay 0
-    dSlabL = reinterpret_cast<float*>(c->cv.slab_l.ensure(sizeof(float) * (size_t)kpcvf::KSL * msr * c->dim));
-    dMapM = reinterpret_cast<float*>(c->cv.map_m.ensure(sizeof(float) * (size_t)mk * kpcvf::NMID));
-    dMid = reinterpret_cast<float*>(c->cv.mid.ensure(sizeof(float) * (size_t)mk * c->dim));
-    dMapL = reinterpret_cast<float*>(c->cv.map_l.ensure(sizeof(float) * (size_t)msr * kpcvf::NLHS));
-    dGs = reinterpret_cast<float*>(c->cv.gs.ensure(sizeof(float) * (size_t)msr * c->dim));
-    dDls = reinterpret_cast<float*>(c->cv.dls.ensure(sizeof(float) * (size_t)msr * DP));
+  d.shared = d.fused && c->cv_shared && !kc.has_in && !kc.has_fm;
+  if (d.shared) {
+    conve_shared_setup(c, d.fw, d.X, d.bits);
+    d.sr_src = upload1(c, c->cv.sr_src, sp.sr_src);
+    d.sr_rng = upload1(c, c->cv.sr_rng, sp.sr_rng);
+    d.psr = upload1(c, c->cv.psr, sp.psr);
+    d.relu_s = reinterpret_cast<uint8_t*>(c->cv.relu_s.ensure((size_t)msr * kpcvf::MASK_B));
+    KP_HIP(hipMemsetAsync(d.relu_s, 0, (size_t)msr * kpcvf::MASK_B, c->stream));  // rows 18-19 stay 0
+    d.slab_l = ensure_n<float>(c->cv.slab_l, (size_t)kpcvf::KSL * msr * c->dim);
+    d.map_m = ensure_n<float>(c->cv.map_m, (size_t)mk * kpcvf::NMID);
+    d.mid = ensure_n<float>(c->cv.mid, (size_t)mk * c->dim);
+    d.map_l = ensure_n<float>(c->cv.map_l, (size_t)msr * kpcvf::NLHS);
+    d.gs = ensure_n<float>(c->cv.gs, (size_t)msr * c->dim);
+    d.dls = ensure_n<float>(c->cv.dls, (size_t)msr * DP);
   }
-  const int n_dl = fused ? kpcvf::NSPLIT : 1;  // lhs image-gradient slabs per pair (kp_cv_bwd_fused, reduced in slab 0)
-  float* dQ = reinterpret_cast<float*>(c->cv.q.ensure(sizeof(float) * (size_t)me * DP));
-  int2* dSrc = upload(c, c->cv.enc_src, enc_src.data(), std::max<size_t>(1, enc_src.size()));
-  int4* dFch = upload(c, c->cv.fchunks, fchunks.data(), std::max<size_t>(1, fchunks.size()));
-  float* dFpart = reinterpret_cast<float*>(c->cv.fpart.ensure(sizeof(float) * (size_t)std::max(1, max_fch) * c->dim));
-  CvBits* dEncBits = upload(c, c->cv.enc_bits, enc_bits.data(), std::max<size_t>(1, enc_bits.size()));
-  float* dgs = reinterpret_cast<float*>(c->cv.gscale.ensure(sizeof(float) * (size_t)std::max<size_t>(1, kinst.size())));
+  const int n_dl = d.fused ? kpcvf::NSPLIT : 1;  // lhs image-gradient slabs per pair (kp_cv_bwd_fused, reduced in slab 0)
+  d.Q = ensure_n<float>(c->cv.q, (size_t)me * DP);
+  d.src = upload1(c, c->cv.enc_src, sp.enc_src);
+  d.fch = upload1(c, c->cv.fchunks, sp.fchunks);
+  d.fpart = ensure_n<float>(c->cv.fpart, (size_t)std::max(1, sp.max_fch) * c->dim);
+  d.enc_bits = upload1(c, c->cv.enc_bits, sp.enc_bits);
+  d.gscale = ensure_n<float>(c->cv.gscale, std::max<size_t>(1, sp.kinst.size()));
   {
-    std::vector<float> gsv(kinst.size());
-    for (size_t i = 0; i < kinst.size(); ++i) gsv[i] = 1.0f / (float)((long long)kinst[i].b * (long long)(K + 1));
+    std::vector<float> gsv(sp.kinst.size());
+    for (size_t i = 0; i < gsv.size(); ++i) gsv[i] = 1.0f / (float)((long long)sp.kinst[i].b * (long long)(K + 1));
     if (!gsv.empty())
-      KP_HIP(hipMemcpyAsync(dgs, gsv.data(), sizeof(float) * gsv.size(), hipMemcpyHostToDevice, c->stream));
+      KP_HIP(hipMemcpyAsync(d.gscale, gsv.data(), sizeof(float) * gsv.size(), hipMemcpyHostToDevice, c->stream));
   }
-  int attn_slots = c->n_cu * (DBV <= 13 ? 2 : 1);  // co-resident attention workgroups
-  if (c->attn_mode == 1) {
-    switch (DBV) {
-      case 4: attn_slots = c->n_cu * attn3_wpc<4, ATT_BCE_O>(c); break;
-      case 8: attn_slots = c->n_cu * attn3_wpc<8, ATT_BCE_O>(c); break;
-      case 13: attn_slots = c->n_cu * attn3_wpc<13, ATT_BCE_O>(c); break;
-      case 16: attn_slots = c->n_cu * attn3_wpc<16, ATT_BCE_O>(c); break;
-      case 25: attn_slots = c->n_cu * attn3_wpc<25, ATT_BCE_O>(c); break;
-      default: throw KpError{KP_ENOTSUP, "ConvE: unsupported padded dimension"};
-    }
-  }
-  std::vector<AttnPlan> step_plan(T);
-  size_t o_rows = 1;
-  c->attn_last = {};
-  for (int t = 0; t < T; ++t) {
-    const int nk = kin_off[t + 1] - kin_off[t];
-    // the ConvE attention (ATT_BCE_O, two workgroups per CU) keeps the plan of a launch that
-    // runs alone whatever the context's in-flight hint says (DESIGN.md section 5)
-    step_plan[t] = attn_plan_ctx(c, std::max(nk, 1), K, attn_slots, KP_CV_ATTN_INFLIGHT != 0);
-    if (nk > 0) attn_plan_note(c, step_plan[t], nk, KP_CV_ATTN_INFLIGHT != 0);
-    o_rows = std::max(o_rows, (size_t)nk * step_plan[t].wk.n_parts);
-  }
-  float* dO = reinterpret_cast<float*>(c->cv.o.ensure(sizeof(float) * o_rows * DP));
-  float* ddfc = reinterpret_cast<float*>(c->cv.dfc.ensure(sizeof(float) * (size_t)mk * c->dim));
-  float* dgk = reinterpret_cast<float*>(c->cv.gk.ensure(sizeof(float) * (size_t)mk));
-  float* ddflat = reinterpret_cast<float*>(c->cv.dflat.ensure(sizeof(float) * (size_t)(fused ? 1 : mk) * c->hidden));
-  float* ddl = reinterpret_cast<float*>(c->cv.dl.ensure(sizeof(float) * (size_t)n_dl * mk * DP));
-  float* dWt = conve_fc_wt(c);
-  // the masks' multipliers as the fused kernels take them (1: not drawn)
-  const float s_in = kc.has_in ? kc.scale_in : 1.0f, s_fm = kc.has_fm ? kc.scale_fm : 1.0f;
+  cv_attn_plans(c, sp, d);
+  d.dfc = ensure_n<float>(c->cv.dfc, (size_t)mk * c->dim);
+  d.gk = ensure_n<float>(c->cv.gk, (size_t)mk);
+  d.dflat = ensure_n<float>(c->cv.dflat, (size_t)(d.fused ? 1 : mk) * c->hidden);
+  d.dl = ensure_n<float>(c->cv.dl, (size_t)n_dl * mk * DP);
+  d.wt = conve_fc_wt(c);
+  d.s_in = kc.has_in ? kc.scale_in : 1.0f;
+  d.s_fm = kc.has_fm ? kc.scale_fm : 1.0f;
+}
 
+// step t's slices of the plan's device lists
+struct CvStep {
+  int t, nk, ne, na, nsr;  // kelpie pairs, encoder rows (the nk kelpie rows first), active slots, shared rows
+  const CvInst* KI;
+  const int2* ES;
+  const CvBits* EB;
+};
+CvStep cv_step(const CvStepPlan& sp, const CvDev& d, int t) {
+  return CvStep{t,
+                sp.kin_off[t + 1] - sp.kin_off[t],
+                sp.enc_off[t + 1] - sp.enc_off[t],
+                sp.act_off[t + 1] - sp.act_off[t],
+                sp.sr_off[t + 1] - sp.sr_off[t],
+                d.KI + sp.kin_off[t],
+                d.src + sp.enc_off[t],
+                d.enc_bits + sp.enc_off[t]};
+}
+
+// encoder forward, shared split (kp_cv_fused.hpp); ne == nk here
+void cv_fwd_shared(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, const CvDev& d, const CvStep& st) {
+  const int DP = c->dp, ne = st.ne, nsr = st.nsr;
+  hipLaunchKernelGGL(kpcvf::kp_cv_lhs_map, dim3(nsr), dim3(256), 0, c->stream, nsr, d.sr_src + sp.sr_off[st.t], d.X, DP,
+                     c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, d.map_l, d.relu_s);
+  KP_HIP(hipGetLastError());
+  launch_gemm_abt(c, d.map_l, kpcvf::NLHS, nsr, c->cv_wlc.as<float>(), kpcvf::NLHS, c->dim, kpcvf::NLHS, d.slab_l,
+                  c->dim, c->d_fc_b, 0, kpcvf::KSL);
+  hipLaunchKernelGGL(kpcvf::kp_cv_mid_map, dim3((ne * kpcvf::CH * 2 + 255) / 256), dim3(256), 0, c->stream, ne, st.ES,
+                     c->dE, d.X, c->dR, DP, c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, d.map_m, d.relu);
+  KP_HIP(hipGetLastError());
+  launch_gemm_abt(c, d.map_m, kpcvf::NMID, ne, c->cv_wtm.as<float>(), kpcvf::NMID, c->dim, kpcvf::NMID, d.mid, c->dim,
+                  nullptr, 0, 1);
+  hipLaunchKernelGGL(kp_cv_post_fc3, dim3(ne), dim3(256), 0, c->stream, ne, d.slab_l, kpcvf::KSL, nsr, d.mid, 1,
+                     c->cv_trel.as<float>(), st.ES, d.psr + sp.kin_off[st.t], kc, st.EB, d.bits, c->d_bn_a, c->d_bn_b,
+                     d.Q);
+  KP_HIP(hipGetLastError());
+}
+
+// conv + FC forward in one kernel (kp_cv_fused.hpp) -> the FC split-K slabs
+void cv_fwd_fused(kp_ctx* c, const CvConst& kc, const CvDev& d, const CvStep& st) {
+  const int ne = st.ne;
+  const int fgrid = kpcvf::NSPLIT * ((ne + kpcvf::MT - 1) / kpcvf::MT);
+  if (kc.fr_step)
+    hipLaunchKernelGGL(kpcvf::kp_cv_fwd_fused<true>, dim3(fgrid), dim3(512), kpcvf::FWD_LDS, c->stream, ne, st.ES,
+                       c->dE, d.X, c->dR, c->dp, c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, d.fw, c->d_fc_b,
+                       c->dim, st.EB, d.bits, d.s_in, d.s_fm, d.slab, d.relu, 0, kpcvf::FR * 8, kpcvf::NSPLIT, 8);
+  else
+    hipLaunchKernelGGL(kpcvf::kp_cv_fwd_fused<false>, dim3(fgrid), dim3(512), kpcvf::FWD_LDS, c->stream, ne, st.ES,
+                       c->dE, d.X, c->dR, c->dp, c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, d.fw, c->d_fc_b,
+                       c->dim, st.EB, d.bits, d.s_in, d.s_fm, d.slab, d.relu, 0, kpcvf::FR * 8, kpcvf::NSPLIT, 8);
+  KP_HIP(hipGetLastError());
+}
+
+// conv forward, then the FC as a split-K GEMM -> the FC split-K slabs
+void cv_fwd_plain(kp_ctx* c, const CvConst& kc, const CvDev& d, const CvStep& st) {
+  KP_CONV_FWD(dim3(st.ne), dim3(256), 0, c->stream, st.ne, st.ES, c->dE, d.X, c->dR, kc, c->d_conv_w, c->d_conv_b,
+              c->d_bn_a, c->d_bn_b, st.EB, d.bits, d.flat);
+  KP_HIP(hipGetLastError());
+  launch_gemm_abt(c, d.flat, c->hidden, st.ne, c->d_fc_w, c->hidden, c->dim, c->hidden, d.slab, c->dim, c->d_fc_b, 0,
+                  d.KS);
+}
+
+// encoder forward of the step's rows -> Q (conve.py:133-153, train-mode dropouts)
+void cv_forward(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, const CvDev& d, const CvStep& st) {
+  if (st.ne <= 0) return;
+  if (d.shared) return cv_fwd_shared(c, kc, sp, d, st);
+  if (d.fused)
+    cv_fwd_fused(c, kc, d, st);
+  else
+    cv_fwd_plain(c, kc, d, st);
+  hipLaunchKernelGGL(kp_cv_post_fc, dim3(st.ne), dim3(256), 0, c->stream, st.ne, d.slab, d.KS, kc, st.EB, d.bits,
+                     c->d_bn_a, c->d_bn_b, d.Q);
+  KP_HIP(hipGetLastError());
+}
+
+// O = sum_e G(x . E_e) E_e of the step's kelpie pairs over the frozen entities
+template <int DB>
+void launch_cv_attn(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, const CvDev& d, const CvStep& st) {
+  const AttnPlan& plan = d.step_plan[st.t];
+  const float* gscale = d.gscale + sp.kin_off[st.t];
+  if (c->attn_mode == 1)
+    launch_attn3<DB, ATT_BCE_O>(c, c->n_ent, d.Q, st.nk, plan, nullptr, nullptr, d.O, gscale, kc.ylo);
+  else
+    hipLaunchKernelGGL((kp_attn<DB, ATT_BCE_O>), dim3(plan.n_wg), dim3(256), attn_lds_bytes(c->dp / 16), c->stream,
+                       c->dE, c->n_ent, d.Q, st.nk, plan.wk, nullptr, nullptr, d.O, gscale, kc.ylo);
+}
+
+// the step's hot launch, bracketed by the context's event pair `launch` when timed
+void cv_attention(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, const CvDev& d, const CvStep& st,
+                  int64_t launch) {
+  if (c->time_hot) KP_HIP(hipEventRecord(c->event(2 * launch), c->stream));
+  KP_DB_DISPATCH(c->dp / 16, 4, "ConvE: unsupported padded dimension", launch_cv_attn<DB>(c, kc, sp, d, st));
+  KP_HIP(hipGetLastError());
+  if (c->time_hot) {
+    KP_HIP(hipEventRecord(c->event(2 * launch + 1), c->stream));
+    c->hot_pairs.push_back({(double)st.nk, 0.0});
+  }
+}
+
+// dL/dx -> dL/dfc of the step's kelpie pairs, and G at the kelpie column
+void cv_dx(kp_ctx* c, const CvConst& kc, const CvDev& d, const CvStep& st) {
+  const int nk = st.nk, n_split = d.step_plan[st.t].wk.n_parts;
+  __bf16* g3p = d.shared ? nullptr : d.g3;
+  const int nj = (c->dp + 63) / 64;
+#define CV_DX1(J)                                                                                                \
+  hipLaunchKernelGGL(kp_cv_dx1<J>, dim3(nk), dim3(64), 0, c->stream, nk, kc, st.KI, d.Q, d.O, n_split, d.tails, \
+                     c->dE, d.X, d.bits, c->d_bn_a, d.dfc, d.gk, g3p)
+  if (!c->cv_dx_block && nj <= 2)
+    CV_DX1(2);
+  else if (!c->cv_dx_block && nj <= 4)
+    CV_DX1(4);
+  else if (!c->cv_dx_block && nj <= 6)
+    CV_DX1(6);
+  else if (!c->cv_dx_block && nj <= 8)
+    CV_DX1(8);
+  else
+    hipLaunchKernelGGL(kp_cv_dx, dim3(nk), dim3(256), 0, c->stream, nk, kc, st.KI, d.Q, d.O, n_split, d.tails, c->dE,
+                       d.X, d.bits, c->d_bn_a, d.dfc, d.gk, g3p);
+#undef CV_DX1
+  KP_HIP(hipGetLastError());
+}
+
+// encoder backward, shared split: map rows 0-17 once per kelpie row (the sum of its pairs'
+// dfc; rows 18-19 of its ReLU bytes are 0), then rows 18-19 per pair, assembled into the
+// pairs' dl rows
+void cv_bwd_shared(kp_ctx* c, const CvStepPlan& sp, const CvDev& d, const CvStep& st) {
+  const int DP = c->dp, nk = st.nk, nsr = st.nsr;
+  hipLaunchKernelGGL(kpcvf::kp_cv_slot_g, dim3(nsr), dim3(256), 0, c->stream, nsr, d.sr_rng + sp.sr_off[st.t], d.dfc,
+                     c->dim, d.gs);
+  KP_HIP(hipGetLastError());
+  launch_gemm_abt(c, d.gs, c->dim, nsr, c->cv_wtl.as<float>(), c->dim, kpcvf::NLHS, c->dim, d.map_l, kpcvf::NLHS,
+                  nullptr, 0, 1);
+  hipLaunchKernelGGL(kpcvf::kp_cv_lhs_convt, dim3(nsr), dim3(256), 0, c->stream, nsr, d.map_l, d.relu_s, c->d_conv_w,
+                     c->d_bn_a, DP, d.dls);
+  KP_HIP(hipGetLastError());
+  launch_gemm_abt(c, d.dfc, c->dim, nk, c->cv_wfm.as<float>(), c->dim, kpcvf::NMID, c->dim, d.map_m, kpcvf::NMID,
+                  nullptr, 0, 1);
+  hipLaunchKernelGGL(kpcvf::kp_cv_mid_convt, dim3((nk + kpcvf::MPW - 1) / kpcvf::MPW), dim3(256), 0, c->stream, nk,
+                     d.map_m, d.relu, c->d_conv_w, c->d_bn_a, d.psr + sp.kin_off[st.t], d.dls, DP, d.dl);
+  KP_HIP(hipGetLastError());
+}
+
+// FC^T and transposed conv in one kernel (kp_cv_fused.hpp), its slabs reduced into slab 0
+void cv_bwd_fused(kp_ctx* c, const CvConst& kc, const CvDev& d, const CvStep& st) {
+  const int DP = c->dp, nk = st.nk;
+  const int bgrid = kpcvf::NSPLIT * ((nk + kpcvf::MT - 1) / kpcvf::MT);
+  hipLaunchKernelGGL(kpcvf::kp_cv_bwd_fused, dim3(bgrid), dim3(512), kpcvf::BWD_LDS, c->stream, nk, d.g3, d.bw, d.relu,
+                     c->d_conv_w, c->d_bn_a, d.s_fm, DP, d.dl);
+  KP_HIP(hipGetLastError());
+  const long long nr = (long long)nk * kpcvf::LR * kpcvf::IW;
+  hipLaunchKernelGGL(kpcvf::kp_cv_dl_reduce, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, c->stream, nk, DP,
+                     kc.has_in ? st.EB : nullptr, d.bits, d.s_in, d.dl);
+  KP_HIP(hipGetLastError());
+}
+
+// FC^T as a GEMM, then the transposed conv
+void cv_bwd_plain(kp_ctx* c, const CvConst& kc, const CvDev& d, const CvStep& st) {
+  const int nk = st.nk;
+  launch_gemm_abt(c, d.dfc, c->dim, nk, d.wt, c->dim, c->hidden, c->dim, d.dflat, c->hidden, nullptr, 0, 1);
+  const size_t shm_cbwd = sizeof(float) * 32 * 20 * (c->dim / 20 - 2);
+  hipLaunchKernelGGL(kp_cv_conv_bwd, dim3(nk), dim3(256), shm_cbwd, c->stream, nk, kc, d.dflat, d.flat, c->d_conv_w,
+                     c->d_bn_a, st.EB, d.bits, d.dl);
+  KP_HIP(hipGetLastError());
+}
+
+// gradient assembly + Adam of the step's active slots.  d.act entries index kinst / finst
+// relative to this step's lists; the frozen-head pairs read their encodings from Q (fr_step)
+// or the batch's FC rows
+void cv_update(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, const CvDev& d, const CvStep& st,
+               const CvOpt& opt) {
+  if (st.na <= 0) return;
+  const int t = st.t, nch = sp.fch_off[t + 1] - sp.fch_off[t];
+  if (nch > 0) {
+    hipLaunchKernelGGL(kp_cv_fgrad, dim3(nch), dim3(256), 0, c->stream, kc, d.fch + sp.fch_off[t],
+                       d.act + sp.act_off[t], d.FI + sp.fin_off[t], kc.fr_step ? d.Q : d.fcf, d.bits, c->d_bn_a,
+                       c->d_bn_b, d.X, d.fpart);
+    KP_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(kp_cv_update, dim3(st.na), dim3(256), 0, c->stream, kc, d.act + sp.act_off[t], d.Q, d.gk, d.dl,
+                     d.fpart, d.X, d.S1, d.S2, opt);
+  KP_HIP(hipGetLastError());
+}
+
+// the epoch/step loop; returns the hot (attention) launches
+int64_t cv_step_loop(kp_ctx* c, const kp_hp* hp, const CvConst& kc, const CvStepPlan& sp, const CvDev& d) {
   CvOpt opt{};
   opt.lr = hp->lr;
   opt.b1 = hp->beta1;
@@ -1036,187 +1070,88 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   int64_t launches = 0;
   c->hot_pairs.clear();
   c->hot_iv.clear();
-  const size_t shm_attn = attn_lds_bytes(DP / 16);
-  const size_t shm_cbwd = sizeof(float) * 32 * 20 * (c->dim / 20 - 2);
-  for (int t = 0; t < T; ++t) {
-    const int nk = kin_off[t + 1] - kin_off[t];
-    const int ne = enc_off[t + 1] - enc_off[t];  // nk kelpie rows first
-    const int na = act_o[t + 1] - act_o[t];
-    const CvInst* KI = dKI + kin_off[t];
-    const int2* ES = dSrc + enc_off[t];
-    const CvBits* EB = dEncBits + enc_off[t];
-    const int nsr = sr_off[t + 1] - sr_off[t];
-    if (ne > 0 && shared) {  // encoder forward, shared split (kp_cv_fused.hpp); ne == nk here
-      hipLaunchKernelGGL(kpcvf::kp_cv_lhs_map, dim3(nsr), dim3(256), 0, c->stream, nsr, dSrSrc + sr_off[t], dX, DP,
-                         c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, dMapL, dReluS);
-      KP_HIP(hipGetLastError());
-      launch_gemm_abt(c, dMapL, kpcvf::NLHS, nsr, c->cv_wlc.as<float>(), kpcvf::NLHS, c->dim, kpcvf::NLHS, dSlabL,
-                      c->dim, c->d_fc_b, 0, kpcvf::KSL);
-      hipLaunchKernelGGL(kpcvf::kp_cv_mid_map, dim3((ne * kpcvf::CH * 2 + 255) / 256), dim3(256), 0, c->stream, ne, ES,
-                         c->dE, dX, c->dR, DP, c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, dMapM, dRelu);
-      KP_HIP(hipGetLastError());
-      launch_gemm_abt(c, dMapM, kpcvf::NMID, ne, c->cv_wtm.as<float>(), kpcvf::NMID, c->dim, kpcvf::NMID, dMid, c->dim,
-                      nullptr, 0, 1);
-      hipLaunchKernelGGL(kp_cv_post_fc3, dim3(ne), dim3(256), 0, c->stream, ne, dSlabL, kpcvf::KSL, nsr, dMid, 1,
-                         c->cv_trel.as<float>(), ES, dPsr + kin_off[t], kc, EB, dBits, c->d_bn_a, c->d_bn_b, dQ);
-      KP_HIP(hipGetLastError());
-    } else if (ne > 0) {  // encoder forward (conve.py:133-153, train-mode dropouts)
-      if (fused) {
-        const int fgrid = kpcvf::NSPLIT * ((ne + kpcvf::MT - 1) / kpcvf::MT);
-        if (kc.fr_step)
-          hipLaunchKernelGGL(kpcvf::kp_cv_fwd_fused<true>, dim3(fgrid), dim3(512), kpcvf::FWD_LDS, c->stream, ne, ES,
-                             c->dE, dX, c->dR, DP, c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, cvf_fw, c->d_fc_b,
-                             c->dim, EB, dBits, s_in, s_fm, dslab, dRelu, 0, kpcvf::FR * 8,
-                             kpcvf::NSPLIT, 8);
-        else
-          hipLaunchKernelGGL(kpcvf::kp_cv_fwd_fused<false>, dim3(fgrid), dim3(512), kpcvf::FWD_LDS, c->stream, ne, ES,
-                             c->dE, dX, c->dR, DP, c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, cvf_fw, c->d_fc_b,
-                             c->dim, EB, dBits, s_in, s_fm, dslab, dRelu, 0, kpcvf::FR * 8,
-                             kpcvf::NSPLIT, 8);
-        KP_HIP(hipGetLastError());
-      } else {
-        KP_CONV_FWD(dim3(ne), dim3(256), 0, c->stream, ne, ES, c->dE, dX, c->dR, kc, c->d_conv_w, c->d_conv_b,
-                    c->d_bn_a, c->d_bn_b, EB, dBits, dflat);
-        KP_HIP(hipGetLastError());
-        launch_gemm_abt(c, dflat, c->hidden, ne, c->d_fc_w, c->hidden, c->dim, c->hidden, dslab, c->dim, c->d_fc_b, 0,
-                        KS);
-      }
-      hipLaunchKernelGGL(kp_cv_post_fc, dim3(ne), dim3(256), 0, c->stream, ne, dslab, KS, kc, EB, dBits, c->d_bn_a,
-                         c->d_bn_b, dQ);
-      KP_HIP(hipGetLastError());
+  for (int t = 0; t < sp.T; ++t) {
+    const CvStep st = cv_step(sp, d, t);
+    cv_forward(c, kc, sp, d, st);
+    if (st.nk > 0) {
+      cv_attention(c, kc, sp, d, st, launches++);
+      cv_dx(c, kc, d, st);
+      if (d.shared)
+        cv_bwd_shared(c, sp, d, st);
+      else if (d.fused)
+        cv_bwd_fused(c, kc, d, st);
+      else
+        cv_bwd_plain(c, kc, d, st);
     }
-    if (nk > 0) {
-      const int n_split = step_plan[t].wk.n_parts;
-      hipEvent_t ea = nullptr, eb = nullptr;
-      if (c->time_hot) {
-        ea = c->event(2 * launches);
-        eb = c->event(2 * launches + 1);
-        KP_HIP(hipEventRecord(ea, c->stream));
-      }
-      dim3 grid(step_plan[t].n_wg);
-#define CV_ATT(DBX)                                                                                                  \
-  if (c->attn_mode == 1)                                                                                             \
-    launch_attn3<DBX, ATT_BCE_O>(c, K, dQ, nk, step_plan[t], nullptr, nullptr, dO, dgs + kin_off[t], kc.ylo);       \
-  else                                                                                                               \
-    hipLaunchKernelGGL((kp_attn<DBX, ATT_BCE_O>), grid, dim3(256), shm_attn, c->stream, c->dE, K, dQ, nk,          \
-                       step_plan[t].wk,                                                                               \
-                       nullptr, nullptr, dO, dgs + kin_off[t], kc.ylo)
-      switch (DBV) {
-        case 4: CV_ATT(4); break;
-        case 8: CV_ATT(8); break;
-        case 13: CV_ATT(13); break;
-        case 16: CV_ATT(16); break;
-        case 25: CV_ATT(25); break;
-        default: throw KpError{KP_ENOTSUP, "ConvE: unsupported padded dimension"};
-      }
-#undef CV_ATT
-      KP_HIP(hipGetLastError());
-      if (c->time_hot) {
-        KP_HIP(hipEventRecord(eb, c->stream));
-        c->hot_pairs.push_back({(double)nk, 0.0});
-      }
-      ++launches;
-      {
-        __bf16* g3p = shared ? nullptr : dG3;
-        const int nj = (c->dp + 63) / 64;
-#define CV_DX1(J)                                                                                                  \
-  hipLaunchKernelGGL(kp_cv_dx1<J>, dim3(nk), dim3(64), 0, c->stream, nk, kc, KI, dQ, dO, n_split, dTails, c->dE, dX, \
-                     dBits, c->d_bn_a, ddfc, dgk, g3p)
-        if (!c->cv_dx_block && nj <= 2)
-          CV_DX1(2);
-        else if (!c->cv_dx_block && nj <= 4)
-          CV_DX1(4);
-        else if (!c->cv_dx_block && nj <= 6)
-          CV_DX1(6);
-        else if (!c->cv_dx_block && nj <= 8)
-          CV_DX1(8);
-        else
-          hipLaunchKernelGGL(kp_cv_dx, dim3(nk), dim3(256), 0, c->stream, nk, kc, KI, dQ, dO, n_split, dTails, c->dE,
-                             dX, dBits, c->d_bn_a, ddfc, dgk, g3p);
-#undef CV_DX1
-      }
-      KP_HIP(hipGetLastError());
-      if (shared) {
-        // map rows 0-17 once per kelpie row (the sum of its pairs' dfc; rows 18-19 of its
-        // ReLU bytes are 0), then rows 18-19 per pair, assembled into the pairs' dl rows
-        hipLaunchKernelGGL(kpcvf::kp_cv_slot_g, dim3(nsr), dim3(256), 0, c->stream, nsr, dSrRng + sr_off[t], ddfc,
-                           c->dim, dGs);
-        KP_HIP(hipGetLastError());
-        launch_gemm_abt(c, dGs, c->dim, nsr, c->cv_wtl.as<float>(), c->dim, kpcvf::NLHS, c->dim, dMapL, kpcvf::NLHS,
-                        nullptr, 0, 1);
-        hipLaunchKernelGGL(kpcvf::kp_cv_lhs_convt, dim3(nsr), dim3(256), 0, c->stream, nsr, dMapL, dReluS, c->d_conv_w,
-                           c->d_bn_a, DP, dDls);
-        KP_HIP(hipGetLastError());
-        launch_gemm_abt(c, ddfc, c->dim, nk, c->cv_wfm.as<float>(), c->dim, kpcvf::NMID, c->dim, dMapM, kpcvf::NMID,
-                        nullptr, 0, 1);
-        hipLaunchKernelGGL(kpcvf::kp_cv_mid_convt, dim3((nk + kpcvf::MPW - 1) / kpcvf::MPW), dim3(256), 0, c->stream, nk,
-                           dMapM, dRelu, c->d_conv_w, c->d_bn_a, dPsr + kin_off[t], dDls, DP, ddl);
-        KP_HIP(hipGetLastError());
-      } else if (fused) {
-        const int bgrid = kpcvf::NSPLIT * ((nk + kpcvf::MT - 1) / kpcvf::MT);
-        hipLaunchKernelGGL(kpcvf::kp_cv_bwd_fused, dim3(bgrid), dim3(512), kpcvf::BWD_LDS, c->stream, nk, dG3,
-                           cvf_bw, dRelu, c->d_conv_w, c->d_bn_a, s_fm, DP, ddl);
-        KP_HIP(hipGetLastError());
-        const long long nr = (long long)nk * kpcvf::LR * kpcvf::IW;
-        hipLaunchKernelGGL(kpcvf::kp_cv_dl_reduce, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, c->stream, nk, DP,
-                           kc.has_in ? EB : nullptr, dBits, s_in, ddl);
-        KP_HIP(hipGetLastError());
-      } else {
-        launch_gemm_abt(c, ddfc, c->dim, nk, dWt, c->dim, c->hidden, c->dim, ddflat, c->hidden, nullptr, 0, 1);
-      }
-      if (!fused) {
-        hipLaunchKernelGGL(kp_cv_conv_bwd, dim3(nk), dim3(256), shm_cbwd, c->stream, nk, kc, ddflat, dflat, c->d_conv_w,
-                           c->d_bn_a, EB, dBits, ddl);
-        KP_HIP(hipGetLastError());
-      }
-    }
-    const double step = (double)(t + 1);
-    opt.step_size = (float)((double)hp->lr / (1.0 - std::pow((double)hp->beta1, step)));
-    opt.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)hp->beta2, step));
-    if (na > 0) {
-      // dAct entries index kinst/finst relative to this step's lists; the frozen-head pairs
-      // read their encodings from dQ (fr_step) or the batch's FC rows
-      const int nch = fch_off[t + 1] - fch_off[t];
-      if (nch > 0) {
-        hipLaunchKernelGGL(kp_cv_fgrad, dim3(nch), dim3(256), 0, c->stream, kc, dFch + fch_off[t], dAct + act_o[t],
-                           dFI + fin_off[t], kc.fr_step ? dQ : dFcf, dBits, c->d_bn_a, c->d_bn_b, dX, dFpart);
-        KP_HIP(hipGetLastError());
-      }
-      hipLaunchKernelGGL(kp_cv_update, dim3(na), dim3(256), 0, c->stream, kc, dAct + act_o[t], dQ, dgk, ddl, dFpart,
-                         dX, dS1, dS2, opt);
-      KP_HIP(hipGetLastError());
-    }
+    const AdamStep as = adam_step(hp, t);
+    opt.step_size = as.step_size;
+    opt.bc2_sqrt = as.bc2_sqrt;
+    cv_update(c, kc, sp, d, st, opt);
   }
+  return launches;
+}
 
-  const double t_loop = g_host_times ? host_ms() : 0.0;
-  // ---------------- rank: sigmoid(enc(x, R_p) . E_e), kelpie column, maximizer
+// rank: sigmoid(enc(x, R_p) . E_e), kelpie column, maximizer
+RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const TopkOut& tk, const CvDev& d) {
+  const int ns = bt->n_slots, K = c->n_ent, DP = c->dp;
   std::vector<int2> rsrc(ns);
   for (int s = 0; s < ns; ++s) rsrc[s] = make_int2(-s - 1, bt->pred[3 * s + 1]);
   int2* dRsrc = upload(c, c->cv.rank_src, rsrc.data(), rsrc.size());
-  float* dQr = reinterpret_cast<float*>(c->cv.q.ensure(sizeof(float) * (size_t)std::max(ns, mk) * DP));
-  encode_eval(c, ns, dRsrc, dX, dQr);
+  float* dQr = ensure_n<float>(c->cv.q, (size_t)std::max(ns, d.mk) * DP);
+  encode_eval(c, ns, dRsrc, d.X, dQr);
   const RankDev rk = upload_rank_inputs(c, bt, tk);
   if (c->cv_rank64) {
     const Rank64Dev r64 = rank64_buffers(c, ns);
-    hipLaunchKernelGGL(kp_cv_rankq64, dim3(ns), dim3(64), 0, c->stream, dQr, dX, c->dE, K, DP, rk.po, ns, r64.q, r64.t,
+    hipLaunchKernelGGL(kp_cv_rankq64, dim3(ns), dim3(64), 0, c->stream, dQr, d.X, c->dE, K, DP, rk.po, ns, r64.q, r64.t,
                        r64.kcol);
     KP_HIP(hipGetLastError());
     launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_SIGMOID,
                     tk.k, rk.top_ids, rk.top_scores);
   } else {
     const int ld = round_up(K + 1, 4);
-    float* dScores = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)ns * ld));
+    float* dScores = ensure_n<float>(c->rank.scores, (size_t)ns * ld);
     launch_score_gemm(c, dQr, ns, dScores, ld, 1);
-    hipLaunchKernelGGL(kp_cv_kcol, dim3(ns), dim3(64), 0, c->stream, ns, kc, dQr, dX, dScores, ld);
+    hipLaunchKernelGGL(kp_cv_kcol, dim3(ns), dim3(64), 0, c->stream, ns, kc, dQr, d.X, dScores, ld);
     KP_HIP(hipGetLastError());
     launch_rank_count(c, ns, dScores, ld, K + 1, rk.po, rk.filt_off, rk.filt, 0, rk.target, rk.rank);
   }
+  return rk;
+}
+
+}  // namespace
+
+// KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time of the planning (kp_cv_plan.hpp),
+// the uploads, enqueueing the step loop, and the rank with the final wait
+void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
+  const double t_in = g_host_times ? host_ms() : 0.0;
+  require_batch(c, bt, "ConvE");
+  require_topk(tk, c->cv_rank64 != 0, "ConvE");
+  KP_REQUIRE(hp->batch_size >= 1 && hp->epochs >= 0, "ConvE: bad hyper-parameters");
+  const CvConst kc = make_const(c, hp);
+
+  CvStepPlan sp;
+  if (const char* why = cv_step_plan(c->n_ent, c->n_rel2, c->dim, hp->batch_size, hp->epochs, kc.has_in != 0,
+                                     kc.has_fm != 0, kc.has_mask != 0, kc.fr_step != 0, bt, sp))
+    throw KpError{KP_EINVAL, std::string("ConvE: ") + why};
+  const double t_plan = g_host_times ? host_ms() : 0.0;
+
+  std::vector<float> xp;
+  CvDev d = cv_workspaces(c, bt, sp, xp);
+  const double t_up = g_host_times ? host_ms() : 0.0;
+  KP_HIP(hipEventRecord(c->ev0, c->stream));
+  const int nfp = cv_frozen_fc(c, kc, sp, d);
+  cv_step_workspaces(c, kc, sp, nfp, d);
+
+  const int64_t launches = cv_step_loop(c, hp, kc, sp, d);
+  const double t_loop = g_host_times ? host_ms() : 0.0;
+
+  const RankDev rk = cv_rank(c, kc, bt, tk, d);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
-  download_results(c, bt, dX, rk, xp, tk);
+  download_results(c, bt, d.X, rk, xp, tk);
   if (g_host_times)
     std::fprintf(stderr, "[kp_cv] slots %d steps %d pairs %zu: plan %.2f ms, uploads %.2f ms, loop enqueue %.2f ms, "
-                 "rank + wait %.2f ms\n", ns, T, kinst.size(), t_plan - t_in, t_up - t_plan, t_loop - t_up,
-                 host_ms() - t_loop);
+                 "rank + wait %.2f ms\n", bt->n_slots, sp.T, sp.kinst.size(), t_plan - t_in, t_up - t_plan,
+                 t_loop - t_up, host_ms() - t_loop);
   record_hot_timing(c, launches, c->ev0, c->ev1);  // the whole call counts as its loop
 }
 

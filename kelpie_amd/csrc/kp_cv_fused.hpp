@@ -41,17 +41,11 @@
 
 #include "kp_common.hpp"
 #include "kp_attn3.hpp"
+#include "kp_cv_plan.hpp"  // CvBits: a pair's keep-bit offsets
 
 namespace kpcvf {
 
 using kpattn::bf16x8;
-
-// bit offsets of one pair's dropout keep bits in a batch's draws (-1: that dropout is
-// not drawn): input image (2 d bits, row-major 40 x d/20), feature-map channels (32),
-// hidden units (d)
-struct CvBits {
-  long long in, fm, hid;
-};
 
 constexpr int CH = 32;                // conv channels
 constexpr int IW = 10;                // image width (d = 200: 20 x 10 per half)

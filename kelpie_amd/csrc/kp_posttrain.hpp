@@ -1,10 +1,13 @@
 // kp_posttrain.hpp -- the host work the three *_posttrain_rank functions share: the batch
-// check, the kelpie rows' padding, the rank inputs, the result download and the hot-launch
-// timing.  Everything model-specific (planning, launches, where in the call the rank inputs
-// are uploaded) stays in kp_complex.hip / kp_transe.hip / kp_conve.hip.
+// check, Adam's step scalars, the kelpie rows' padding, the rank inputs, the result download
+// and the hot-launch timing.  The model-specific step planning is pure host code in headers
+// of its own (kp_cx_plan.hpp: ComplEx / DistMult; kp_cv_plan.hpp: ConvE; TransE's schedule
+// is kp_sched.cpp); the launches, and where in the call the rank inputs are uploaded, stay
+// in kp_complex.hip / kp_transe.hip / kp_conve.hip.
 #pragma once
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -33,6 +36,17 @@ inline void require_topk(const TopkOut& tk, bool rank64, const char* model) {
   if (tk.k > 0 && (!tk.ids || !tk.scores)) throw KpError{KP_EINVAL, std::string(model) + ": top-k: missing output"};
   if (tk.k > 0 && !rank64)
     throw KpError{KP_ENOTSUP, std::string(model) + ": top-k needs the fp64 rank (the fp32 rank switch is set)"};
+}
+
+// Adam's per-step scalars at step t (0-based) of a call: lr / (1 - beta1^(t+1)) and
+// sqrt(1 - beta2^(t+1)), in double and rounded once (CxOpt / CvOpt step_size, bc2_sqrt)
+struct AdamStep {
+  float step_size, bc2_sqrt;
+};
+inline AdamStep adam_step(const kp_hp* hp, int t) {
+  const double step = (double)(t + 1);
+  return {(float)((double)hp->lr / (1.0 - std::pow((double)hp->beta1, step))),
+          (float)std::sqrt(1.0 - std::pow((double)hp->beta2, step))};
 }
 
 // x0 [ns][dim] zero-padded to [ns][dp] in `xp` (kept by the caller for download_results)

@@ -1,8 +1,9 @@
 """CPU companion of test_gpu_widths.py: the case table is complete and its checks decide.
 
 * Completeness: every width the kernels are compiled for (the ``dbs[]`` list of cx_pick_db in
-  kp_complex.hip, the ``case`` labels of CV_ATT in kp_conve.hip, the (VPL, NT) launches of
-  kp_transe.hip) has a case in width_cases.py or a named test elsewhere in the GPU suite.
+  kp_complex.hip, the ``case`` labels of KP_DB_DISPATCH in kp_attn3.hpp from the narrowest width
+  kp_conve.hip dispatches with, the (VPL, NT) launches of kp_transe.hip) has a case in
+  width_cases.py or a named test elsewhere in the GPU suite.
 * The rank rule is not vacuous: on the oracle side of every case, every slot's bounds are at
   most one apart, three quarters of a case's slots admit one rank only, and the oracle's own
   rank lies inside (a condition on the inputs: seeds and scales are chosen for it).
@@ -30,13 +31,31 @@ def _compiled_dbs():
     return tuple(int(v) for v in m.group(1).split(","))
 
 
+def _dispatch_dbs():
+    """The case labels of KP_DB_DISPATCH, the one switch over the compiled widths."""
+    m = re.search(r"#define KP_DB_DISPATCH\(DBV, DB_MIN, MSG, \.\.\.\)(.*?)default:", _source("kp_attn3.hpp"), re.S)
+    assert m, "KP_DB_DISPATCH not found"
+    return tuple(int(v) for v in re.findall(r"KP_DB_CASE\((\d+), DB_MIN, __VA_ARGS__\)", m.group(1)))
+
+
+def _dispatch_min(name, message):
+    """The narrowest width `name` dispatches with: one value in all of its KP_DB_DISPATCH uses."""
+    src = _source(name)
+    mins = re.findall(r'KP_DB_DISPATCH\([^,;]+, (\d+),\s*"' + re.escape(message) + '"', src)
+    assert mins and len(mins) == src.count("KP_DB_DISPATCH(") and len(set(mins)) == 1, (name, mins)
+    return int(mins[0])
+
+
 def _conve_dbs():
-    return sorted({int(v) for v in re.findall(r"case (\d+): CV_ATT\(\1\); break;", _source("kp_conve.hip"))})
+    lo = _dispatch_min("kp_conve.hip", "ConvE: unsupported padded dimension")
+    return sorted(db for db in _dispatch_dbs() if db >= lo)
 
 
 # --------------------------------------------------------------------------- completeness
 def test_pick_db_restates_the_library():
     assert _compiled_dbs() == wc.DBS
+    assert _dispatch_dbs() == wc.DBS, "KP_DB_DISPATCH's cases differ from cx_pick_db's list"
+    assert _dispatch_min("kp_complex.hip", "ComplEx / DistMult: unsupported padded dimension") == 1
     assert [wc.pick_db(w) for w in (1, 16, 17, 32, 33, 64, 65, 128, 129, 208, 209, 256, 257, 400, 401)] == \
         [1, 1, 2, 2, 4, 4, 8, 8, 13, 13, 16, 16, 25, 25, -1]
 
@@ -46,7 +65,7 @@ def test_every_compiled_attention_width_has_a_gpu_case():
     conve = _conve_dbs()
     assert conve and set(conve) <= set(dbs)
     smallest = wc.pick_db(60)  # ConvE's smallest image, 20 x 3
-    assert conve == [db for db in dbs if db >= smallest], "a ConvE width without a CV_ATT label (or the reverse)"
+    assert conve == [db for db in dbs if db >= smallest], "a ConvE width that is not dispatched (or the reverse)"
     wanted = [(m, db) for m in ("ComplEx", "DistMult") for db in dbs] + [("ConvE", db) for db in conve]
     have = {(c["model"], c["db"]) for c in wc.SWEEP if "db" in c}
     for model, db in wanted:

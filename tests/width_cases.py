@@ -133,7 +133,7 @@ COVERED_BY = {
     ("ConvE", "BCE_O", 13): "test_gpu_parity.py::test_conve_vs_oracle_full_width[200-0.2-streamk]",
 }
 # a ComplEx row is even and DistMult's d = 8 is DB 1 too, so DB 1 / 2 need no ConvE case:
-# ConvE's smallest image (d = 60) is DB 4 and CV_ATT has no smaller label
+# ConvE's smallest image (d = 60) is DB 4 and kp_conve.hip dispatches (KP_DB_DISPATCH) from that width
 ATTN_MODE = {"ComplEx": "SOFTMAX_O", "DistMult": "SOFTMAX_O", "ConvE": "BCE_O"}
 
 
