@@ -185,6 +185,40 @@ int kp_posttrain_rank(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch);
 int kp_posttrain_rank_topk(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
                            float* out_scores);
 
+/* Probes: further kelpie-form triples (kelpie, p, o) ranked against the post-trained row of
+ * a slot, each as get_triple_results (post_training_engine.py:101-125) ranks it on that
+ * slot's post-trained model -- scored, masked, counted and converted exactly as the slot's
+ * own target is.  Slot s owns the probes [probe_off[s], probe_off[s+1]).
+ *   probe_off   [n_slots+1]  CSR offsets into probes; probe_off[0] = 0, probe_off[n_slots] = n
+ *   probes      [n][2]       (p, o): p in [0, n_rel2), o in [0, n_ent] (n_ent = the kelpie entity)
+ *   filt_off    [n+1]        CSR offsets into filt, one list per probe
+ *   filt        [...]        to_filter[(kelpie, p)] of the owning slot's edited KelpieDataset
+ * outputs:
+ *   out_score   [n]          the probe's score, converted as kp_batch.out_score is
+ *   out_rank    [n]          its filtered rank */
+typedef struct {
+  int32_t n;
+  const int32_t* probe_off;
+  const int32_t* probes;
+  const int32_t* filt_off;
+  const int32_t* filt;
+  float* out_score;
+  int64_t* out_rank;
+} kp_probes;
+
+/* kp_posttrain_rank_topk, plus the probes' scores and ranks (get_triple_results,
+ * post_training_engine.py:101-125, called on the slot's post-trained model for other
+ * triples than the explained prediction).  A probe equal to its slot's own (p, o) with the
+ * slot's own filter returns the slot's out_score bit for bit and its out_rank.  out_x,
+ * out_score, out_rank and the top-k lists are bit for bit those without probes.
+ * probes == NULL or probes->n == 0 is kp_posttrain_rank_topk.  KP_EINVAL (after the batch
+ * check, before any upload) for malformed probes; KP_ENOTSUP with probes when the context
+ * ranks in fp32 (KP_TE_RANK=f32, KP_CV_RANK=f32).  The probe rows run in chunks whose fp64
+ * query rows and filter bitmaps stay within 64 MiB (KP_PROBE_CHUNK=n, a diagnostic, forces
+ * n rows per chunk). */
+int kp_posttrain_rank_probes(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
+                             float* out_scores, const kp_probes* probes);
+
 /* Model.all_scores (model.py:19; transe.py:48-65, complex.py:88-112,
  * conve.py:133-158) for n (head, relation) pairs over the frozen entities:
  * out[n][n_ent].  The RelevanceEngine.select_entities_to_convert sweep

@@ -29,7 +29,7 @@ EXPORTS = ["kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_posttrain_ran
            "kp_sched_batch_create", "kp_sched_batch_destroy", "kp_sched_add_calls", "kp_sched_pack",
            "kp_gather_i32", "kp_rng_transe_calls_async", "kp_rng_torch_take", "kp_conve_train_begin",
            "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free", "kp_ctx_set_inflight",
-           "kp_last_attn_plan", "kp_posttrain_rank_topk"]
+           "kp_last_attn_plan", "kp_posttrain_rank_topk", "kp_posttrain_rank_probes"]
 
 
 class ModelDesc(C.Structure):
@@ -56,6 +56,11 @@ class Batch(C.Structure):
                 ("filt", C.c_void_p), ("out_x", C.c_void_p), ("out_score", C.c_void_p), ("out_rank", C.c_void_p)]
 
 
+class Probes(C.Structure):
+    _fields_ = [("n", C.c_int32), ("probe_off", C.c_void_p), ("probes", C.c_void_p), ("filt_off", C.c_void_p),
+                ("filt", C.c_void_p), ("out_score", C.c_void_p), ("out_rank", C.c_void_p)]
+
+
 class KelpieHipError(RuntimeError):
     pass
 
@@ -79,6 +84,9 @@ def lib():
         L.kp_posttrain_rank.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch)]
         L.kp_posttrain_rank_topk.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
                                              C.c_void_p]
+        if hasattr(L, "kp_posttrain_rank_probes"):  # KELPIE_HIP_LIB may name a build from before the probes
+            L.kp_posttrain_rank_probes.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
+                                                   C.c_void_p, C.POINTER(Probes)]
         L.kp_all_scores.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kp_convertible.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
@@ -371,10 +379,13 @@ class Context:
         except Exception:
             pass
 
-    def posttrain_rank(self, hp: HP, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False, topk=0):
+    def posttrain_rank(self, hp: HP, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False, topk=0,
+                       probes=None):
         """kp_posttrain_rank: (target scores, ranks, final rows or None).  With ``topk`` > 0
         (kp_posttrain_rank_topk) a fourth element: (ids int32 [n][topk], scores float32
-        [n][topk]), the slots' best unmasked tails, -1 / 0 past the last one."""
+        [n][topk]), the slots' best unmasked tails, -1 / 0 past the last one.  With ``probes``
+        = (probe_off [n+1], probes [m][2] = (p, o), filt_off [m+1], filt)
+        (kp_posttrain_rank_probes) a last element: (scores float32 [m], ranks int64 [m])."""
         topk = int(topk)
         if not 0 <= topk <= 32:
             raise ValueError(f"topk must be in [0, 32], got {topk}")
@@ -392,13 +403,29 @@ class Context:
         out_r = np.zeros(n, np.int64)
         b = Batch(n, _ptr(x0), _ptr(row_off), _ptr(rows), _ptr(rng_off), _ptr(rng), _ptr(pred), _ptr(filt_off),
                   _ptr(filt), _ptr(out_x), _ptr(out_s), _ptr(out_r))
-        if topk == 0:
+        if topk == 0 and probes is None:
             check(lib().kp_posttrain_rank(self.h, C.byref(hp), C.byref(b)), self.h)
             return out_s, out_r, out_x
-        ids = np.full((n, topk), -1, np.int32)
-        top = np.zeros((n, topk), np.float32)
-        check(lib().kp_posttrain_rank_topk(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top)), self.h)
-        return out_s, out_r, out_x, (ids, top)
+        ids = np.full((n, topk), -1, np.int32) if topk else None
+        top = np.zeros((n, topk), np.float32) if topk else None
+        ret = (out_s, out_r, out_x) + (((ids, top),) if topk else ())
+        if probes is None:
+            check(lib().kp_posttrain_rank_topk(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top)), self.h)
+            return ret
+        p_off, p_tr, pf_off, pf = probes
+        p_off = np.ascontiguousarray(p_off, dtype=np.int32)
+        p_tr = np.ascontiguousarray(np.asarray(p_tr, dtype=np.int32).reshape(-1, 2))
+        pf_off = np.ascontiguousarray(pf_off, dtype=np.int32)
+        pf = np.ascontiguousarray(pf, dtype=np.int32) if len(pf) else np.zeros(1, np.int32)
+        m = len(p_tr)
+        if len(p_off) != n + 1 or len(pf_off) != m + 1:
+            raise ValueError("probes: probe_off needs one entry per slot plus one, filt_off one per probe plus one")
+        p_s = np.zeros(m, np.float32)
+        p_r = np.zeros(m, np.int64)
+        pr = Probes(m, _ptr(p_off), _ptr(p_tr), _ptr(pf_off), _ptr(pf), _ptr(p_s), _ptr(p_r))
+        check(lib().kp_posttrain_rank_probes(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top),
+                                             C.byref(pr)), self.h)
+        return ret + ((p_s, p_r),)
 
     def all_scores(self, heads, rels):
         heads = np.ascontiguousarray(heads, dtype=np.int32)

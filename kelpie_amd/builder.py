@@ -42,6 +42,15 @@ post-trained row would predict (``engine.top_k``), and each record gains
 ``post`` lists of [label, score] pairs (the sufficient engine: one such pair of lists per
 conversion entity, with its label); the kelpie entity is printed as ``kelpie:`` plus the
 label of the entity it clones.  The lists come with the batches the search runs anyway.
+
+With ``side_effects`` = cap > 0 every post-training also ranks the subject's other held-out
+facts (``engine.side_effects``: its validation then test triples without the prediction,
+the first ``cap``), and each record gains ``"side_effects"``, aligned with
+``rule_to_relevance``: per rule the probe count ``"probes"``, ``"base"`` and ``"post"`` =
+{"mrr", "h1"} over the probes (compute_metrics' formulas and rounding) and ``"ranks"`` =
+[labelled triple, base rank, post rank] per probe (the sufficient engine: one such record
+per conversion entity, with its label).  A base result cached without probes gives None
+for the base figures.
 """
 from __future__ import annotations
 
@@ -54,7 +63,7 @@ class StochasticBuilder:
     AUTO_MIN, AUTO_MAX = 4, 32
 
     def __init__(self, xsi, engine, summarization: str = None, max_explanation_length: int = 4, window=32,
-                 pipelined=False, top_k=0):
+                 pipelined=False, top_k=0, side_effects=0):
         if summarization is not None:
             raise NotImplementedError("summarisation (simulation / bisimulation) is out of scope")
         self.xsi = xsi
@@ -69,6 +78,9 @@ class StochasticBuilder:
         self.top_k = int(top_k)
         if self.top_k:
             engine.top_k = self.top_k  # validates the range
+        self.side_effects = int(side_effects)
+        if self.side_effects:
+            engine.side_effects = self.side_effects  # validates the range
         self._details = {}  # rule -> the engine's (post-trained, base) results of its evaluation
         self.stats = {"batches": 0, "evaluated": 0, "wasted": 0, "batch_s": 0.0, "schedule_s": 0.0, "pack_s": 0.0,
                       "lib_s": 0.0}
@@ -108,11 +120,13 @@ class StochasticBuilder:
                "#relevances": rels_num, "execution_time": time.time() - start}
         if self.top_k:
             out["counterfactuals"] = [self._counterfactual(pred, self._details[rule]) for rule, _ in rule_to_rel]
+        if self.side_effects:
+            out["side_effects"] = [self._side_effect(self._details[rule]) for rule, _ in rule_to_rel]
         return out
 
     def _keep_details(self, rules, n):
         """The engine's per-rule results of its last batch, for the first ``n`` of ``rules``."""
-        if self.top_k:
+        if self.top_k or self.side_effects:
             for rule, det in zip(rules[:n], self.engine.last_results):
                 self._details[tuple(rule)] = det
 
@@ -131,6 +145,37 @@ class StochasticBuilder:
             return {"base": self._labelled(base, s), "post": self._labelled(pt, s)}
         # sufficient: one pair per conversion entity
         return [{"entity": self.dataset.id_to_entity[e], "base": self._labelled(base, e), "post": self._labelled(pt, e)}
+                for e, (pt, base) in zip(self.engine.entities_to_convert, det)]
+
+    @staticmethod
+    def _probe_metrics(ranks):
+        """MRR and H@1 of a list of ranks (compute_metrics' formulas and rounding,
+        kelpie_amd/verification.py); None for no ranks.  A maximizer's filtered object does
+        not count itself (get_triple_results), so a held-out fact the model answers first
+        has rank 0: it enters both figures as rank 1."""
+        if not ranks:
+            return None
+        ranks = [max(1, int(r)) for r in ranks]
+        acc = 0.0
+        for r in ranks:
+            acc += 1.0 / float(r)
+        return {"mrr": round(acc / float(len(ranks)), 3),
+                "h1": round(sum(1.0 for r in ranks if r <= 1) / float(len(ranks)), 3)}
+
+    def _side_effect_pair(self, pt, base):
+        post = pt.get("probes") or []
+        before = base.get("probes")
+        ranks = [[list(self.dataset.labels_triple(p["triple"])), None if before is None else before[i]["rank"], p["rank"]]
+                 for i, p in enumerate(post)]
+        return {"probes": len(post),
+                "base": None if before is None else self._probe_metrics([p["rank"] for p in before]),
+                "post": self._probe_metrics([p["rank"] for p in post]), "ranks": ranks}
+
+    def _side_effect(self, det):
+        if isinstance(det, tuple):  # necessary: (post-trained, base) of the prediction's subject
+            return self._side_effect_pair(*det)
+        # sufficient: one pair per conversion entity
+        return [dict(self._side_effect_pair(pt, base), entity=self.dataset.id_to_entity[e])
                 for e, (pt, base) in zip(self.engine.entities_to_convert, det)]
 
     def explore_singleton_rules(self, pred, triples: list):

@@ -202,14 +202,16 @@ int kp_ctx_destroy(kp_ctx* c) {
   return KP_OK;
 }
 
-// kp_posttrain_rank and kp_posttrain_rank_topk (tk.k == 0: no lists).  The model's function
-// checks k and the list outputs itself, after the batch check and before its first upload.
+// kp_posttrain_rank, kp_posttrain_rank_topk (tk.k == 0: no lists) and kp_posttrain_rank_probes
+// (tk.probes null or empty: no probes).  The model's function checks k, the list outputs and
+// the probes itself, after the batch check and before its first upload.
 static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk) {
   if (!c || !hp || !b) return KP_EINVAL;
   return guarded(c, [&] {
     KP_REQUIRE(b->n_slots >= 0, "kp_posttrain_rank: negative n_slots");
     if (b->n_slots == 0) {
       KP_REQUIRE(tk.k >= 0 && tk.k <= 32, "kp_posttrain_rank_topk: k must be in [0, 32]");
+      KP_REQUIRE(tk.n_probes() == 0, "kp_posttrain_rank_probes: probes without a slot");
       return;
     }
     KP_REQUIRE(b->x0 && b->row_off && b->pred && b->filt_off && b->out_score && b->out_rank,
@@ -232,6 +234,18 @@ int kp_posttrain_rank_topk(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_
   tk.k = k;
   tk.ids = out_ids;
   tk.scores = out_scores;
+  return posttrain_rank_call(c, hp, b, tk);
+}
+
+// get_triple_results (post_training_engine.py:101-125) on every slot's post-trained model,
+// for its probes as well as its own target
+int kp_posttrain_rank_probes(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k, int32_t* out_ids,
+                             float* out_scores, const kp_probes* probes) {
+  TopkOut tk;
+  tk.k = k;
+  tk.ids = out_ids;
+  tk.scores = out_scores;
+  tk.probes = probes;
   return posttrain_rank_call(c, hp, b, tk);
 }
 

@@ -130,9 +130,18 @@ struct RankWs {
   // final lists [ns][k]
   DevBuf cand_key, cand_col;
   DevBuf top_ids, top_scores;
+  // kp_posttrain_rank_probes (kp_posttrain.hpp fills them): the probes' (slot, p, o) [n][3],
+  // objects [n], filter CSR and results [n]; one chunk of probe rows' fp64 queries
+  // [chunk][dp], target | kelpie column scores [2][chunk] and filter bitmaps.  The slots' own
+  // buffers above are not reused: their downloads are still pending when the probes run
+  DevBuf p_trip, p_po, p_filt_off, p_filt;
+  DevBuf p_target, p_rank;
+  DevBuf p_q64, p_t64, p_bits;
   auto all() {
-    return std::array{&pred, &po,   &filt_off, &filt,     &target,   &rank,    &q64,
-                      &t64,  &scores, &bits,   &cand_key, &cand_col, &top_ids, &top_scores};
+    return std::array{&pred,     &po,       &filt_off, &filt,       &target,     &rank,   &q64,
+                      &t64,      &scores,   &bits,     &cand_key,   &cand_col,   &top_ids, &top_scores,
+                      &p_trip,   &p_po,     &p_filt_off, &p_filt,   &p_target,   &p_rank, &p_q64,
+                      &p_t64,    &p_bits};
   }
 };
 KP_WS_COMPLETE(RankWs);
@@ -188,10 +197,12 @@ struct ConveWs {
   DevBuf o;                       // attention output [rows * splits][dp]
   DevBuf dfc, gk, dflat, dl;      // backward: dL/dfc, g . x, dL/dflat (unfused), lhs image gradient
   DevBuf rank_src;                // the ranked triples' encoder sources
+  DevBuf probe_src, probe_q;      // a chunk of probes' encoder sources (-slot - 1, p) and outputs [chunk][dp]
   auto all() {
     return std::array{&x, &s1, &s2, &kinst, &finst, &acts, &tails, &keep_bits, &fcf, &fpairs, &flat, &slab,
                       &relu, &g3, &sr_src, &sr_rng, &psr, &relu_s, &slab_l, &mid, &map_l, &map_m, &gs, &dls,
-                      &q, &enc_src, &enc_bits, &fchunks, &fpart, &gscale, &o, &dfc, &gk, &dflat, &dl, &rank_src};
+                      &q, &enc_src, &enc_bits, &fchunks, &fpart, &gscale, &o, &dfc, &gk, &dflat, &dl, &rank_src,
+                      &probe_src, &probe_q};
   }
 };
 KP_WS_COMPLETE(ConveWs);
@@ -327,6 +338,9 @@ struct TopkOut {
   int k = 0;
   int32_t* ids = nullptr;
   float* scores = nullptr;
+  // kp_posttrain_rank_probes' request (nullptr or n == 0: no probes)
+  const kp_probes* probes = nullptr;
+  int n_probes() const { return probes ? probes->n : 0; }
 };
 void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
 // kp_complex.hip, product policy
@@ -379,12 +393,13 @@ enum { RANK_TRIPLE_RESULTS = 0, RANK_PREDICT_TAILS = 1, RANK_SORT_POSITION = 2 }
 // topk > 0: also the topk best unmasked columns of every slot (better value first, equal
 // values by column), ids and converted scores into d_top_ids / d_top_scores [n][topk]
 // (device), -1 / 0 past the last unmasked column; the ranks are those of topk == 0
+// bits_buf: the filter bitmaps' buffer (default c->rank.bits; the probe rows bring their own)
 // launch_rank_f64's score kinds
 enum { RANK64_DOT = 0, RANK64_SIGMOID = 1, RANK64_DIST = 2, RANK64_DIST1 = 3 };
 void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* d_t64, const double* d_kcol64,
                      const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt, float* d_target,
                      int64_t* d_rank, int act = 0, int topk = 0, int32_t* d_top_ids = nullptr,
-                     float* d_top_scores = nullptr);
+                     float* d_top_scores = nullptr, DevBuf* bits_buf = nullptr);
 void launch_rank_count(kp_ctx* c, int n_slots, const float* d_scores, int ld, int n_cols,
                        const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt,
                        int minimizer, float* d_target, int64_t* d_rank,

@@ -457,14 +457,16 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
 
 // fp64 ranking queries (launch_rank_f64): q_s = x_s o R[p_s] from exact fp64 products of
 // the fp32 operands; the target score q_s . E_o and the kelpie column q_s . x_s as one
-// sequential fp64 FMA chain over d (the order kp_rank_f64_count scores every entity in)
-template <int DP, class Prod>
+// sequential fp64 FMA chain over d (the order kp_rank_f64_count scores every entity in).
+// PROBE (kp_posttrain_rank_probes): row s is a probe, pred its (slot, p, o), and x the
+// kelpie row of that slot instead of row s; every operation and its order are the slot form's
+template <int DP, class Prod, bool PROBE = false>
 __global__ void kp_cx_rankq64(const float* __restrict__ X, const float* __restrict__ R, const float* __restrict__ E,
                               int n_ent, int half, const int32_t* __restrict__ pred, int n_slots,
                               double* __restrict__ Q, double* __restrict__ t64, double* __restrict__ kcol64) {
   const int s = blockIdx.x;
   if (s >= n_slots) return;
-  const float* x = X + (size_t)s * DP;
+  const float* x = X + (size_t)(PROBE ? pred[3 * s] : s) * DP;
   const float* rel = R + (size_t)pred[3 * s + 1] * DP;
   double* q = Q + (size_t)s * DP;
   for (int d = threadIdx.x; d < DP; d += blockDim.x) q[d] = Prod::q64(x, rel, d, half);
@@ -574,6 +576,14 @@ void launch_rankq64(kp_ctx* c, const float* X, const int32_t* pred, int n, doubl
   KP_HIP(hipGetLastError());
 }
 
+// the probe form: the probes [r0, r0 + m) of pd into its chunk buffers
+template <int DB, class Prod>
+void launch_probeq64(kp_ctx* c, const float* X, const ProbeDev& pd, int r0, int m) {
+  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod, true>), dim3(m), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
+                     Prod::extent(c->dim), pd.trip + 3 * (size_t)r0, m, pd.q, pd.t, pd.kcol);
+  KP_HIP(hipGetLastError());
+}
+
 #define CX_DISPATCH(DBV, ...) \
   KP_DB_DISPATCH(DBV, 1, "ComplEx / DistMult: unsupported padded dimension", __VA_ARGS__)
 
@@ -605,6 +615,7 @@ struct CxDev {
   Rank64Dev r64;
   int32_t* pred;
   RankDev rk;
+  ProbeDev probes;
   // the attention's: sized and planned by cx_preloop
   float *am = nullptr, *al = nullptr, *ao = nullptr, *qs = nullptr;
   std::vector<AttnPlan> step_plan;  // [T]
@@ -644,6 +655,7 @@ CxDev cx_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, const CxSt
   d.r64 = rank64_buffers(c, ns);
   d.pred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
   d.rk = upload_rank_inputs(c, bt, tk);
+  d.probes = upload_probes(c, bt, tk);
   return d;
 }
 
@@ -746,6 +758,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   // model family (kp_batch_check.hpp)
   require_batch(c, bt, Prod::name);
   require_topk(tk, true, Prod::name);
+  require_probes(c, bt, tk, true, Prod::name);
   const CxOpt opt = make_opt(hp, who);
 
   CxStepPlan sp;
@@ -778,9 +791,12 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   CX_DISPATCH(c->dp / 16, launch_rankq64<DB, Prod>(c, d.X, d.pred, ns, d.r64.q, d.r64.t, d.r64.kcol));
   launch_rank_f64(c, ns, d.r64.q, d.r64.t, d.r64.kcol, d.rk.po, d.rk.filt_off, d.rk.filt, d.rk.target, d.rk.rank,
                   RANK64_DOT, tk.k, d.rk.top_ids, d.rk.top_scores);
+  rank_probes(c, d.probes, RANK64_DOT, [&](int r0, int m) {
+    CX_DISPATCH(c->dp / 16, launch_probeq64<DB, Prod>(c, d.X, d.probes, r0, m));
+  });
   KP_HIP(hipEventRecord(c->ev1, c->stream));
 
-  const double t_enq = download_results(c, bt, d.X, d.rk, xp, tk);
+  const double t_enq = download_results(c, bt, d.X, d.rk, xp, tk, d.probes);
   const double t_done = g_host_times ? host_ms() : 0.0;
   if (g_host_times)
     std::fprintf(stderr,

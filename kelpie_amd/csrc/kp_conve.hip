@@ -559,6 +559,10 @@ __global__ __launch_bounds__(256) void kp_cv_update(CvConst k, const CvAct* __re
 // the order kp_rank_f64_count scores every entity in.  At the reference init the sigmoid
 // scores of ~10^5 entities lie within ~0.005 of 0.5, a few per fp32 ulp there, so fp32
 // scores tie and their rounding moves the rank; the logits order them as a fp64 run does.
+// PROBE (kp_posttrain_rank_probes): row s is a probe, po its (slot, p, o) and Qr its encoder
+// output (encode_eval on (-slot - 1, p)); x is the kelpie row of that slot instead of row s.
+// Every operation and its order are the slot form's
+template <bool PROBE = false>
 __global__ void kp_cv_rankq64(const float* __restrict__ Qr, const float* __restrict__ X,
                               const float* __restrict__ E, int n_ent, int dp, const int32_t* __restrict__ po,
                               int n_slots, double* __restrict__ Q, double* __restrict__ t64,
@@ -569,8 +573,8 @@ __global__ void kp_cv_rankq64(const float* __restrict__ Qr, const float* __restr
   for (int d = threadIdx.x; d < dp; d += blockDim.x) q[d] = (double)Qr[(size_t)s * dp + d];
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float* x = X + (size_t)s * dp;
-    const int o = po[s];
+    const float* x = X + (size_t)(PROBE ? po[3 * s] : s) * dp;
+    const int o = PROBE ? po[3 * s + 2] : po[s];
     double z = 0.0, t = 0.0;
     for (int d = 0; d < dp; ++d) z = __fma_rn(q[d], (double)x[d], z);
     if (o < n_ent) {
@@ -1091,8 +1095,25 @@ int64_t cv_step_loop(kp_ctx* c, const kp_hp* hp, const CvConst& kc, const CvStep
   return launches;
 }
 
+// the probes' uploads and buffers (ahead of the step loop): the shared ones, the encoder
+// sources (-slot - 1, p) of every probe and one chunk's encoder rows.  A chunk's rows also
+// pass through encode_eval's feature maps and FC output, counted into the chunk's budget
+ProbeDev cv_probe_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk) {
+  const size_t enc_row = sizeof(float) * ((size_t)c->hidden + c->dim + c->dp);
+  const ProbeDev pd = upload_probes(c, bt, tk, enc_row);
+  if (pd.n == 0) return pd;
+  const kp_probes* pr = tk.probes;
+  std::vector<int2> src(pd.n);
+  for (int s = 0; s < bt->n_slots; ++s)
+    for (int i = pr->probe_off[s]; i < pr->probe_off[s + 1]; ++i) src[i] = make_int2(-s - 1, pr->probes[2 * (size_t)i]);
+  upload(c, c->cv.probe_src, src.data(), src.size());
+  ensure_n<float>(c->cv.probe_q, (size_t)pd.chunk * c->dp);
+  return pd;
+}
+
 // rank: sigmoid(enc(x, R_p) . E_e), kelpie column, maximizer
-RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const TopkOut& tk, const CvDev& d) {
+RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const TopkOut& tk, const CvDev& d,
+                const ProbeDev& pd) {
   const int ns = bt->n_slots, K = c->n_ent, DP = c->dp;
   std::vector<int2> rsrc(ns);
   for (int s = 0; s < ns; ++s) rsrc[s] = make_int2(-s - 1, bt->pred[3 * s + 1]);
@@ -1102,11 +1123,18 @@ RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const TopkOut&
   const RankDev rk = upload_rank_inputs(c, bt, tk);
   if (c->cv_rank64) {
     const Rank64Dev r64 = rank64_buffers(c, ns);
-    hipLaunchKernelGGL(kp_cv_rankq64, dim3(ns), dim3(64), 0, c->stream, dQr, d.X, c->dE, K, DP, rk.po, ns, r64.q, r64.t,
-                       r64.kcol);
+    hipLaunchKernelGGL(kp_cv_rankq64<false>, dim3(ns), dim3(64), 0, c->stream, dQr, d.X, c->dE, K, DP, rk.po, ns, r64.q,
+                       r64.t, r64.kcol);
     KP_HIP(hipGetLastError());
     launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_SIGMOID,
                     tk.k, rk.top_ids, rk.top_scores);
+    // the probes: a chunk's rows through the encoder on their slots' kelpie rows, then the count
+    rank_probes(c, pd, RANK64_SIGMOID, [&](int r0, int m) {
+      encode_eval(c, m, c->cv.probe_src.as<int2>() + r0, d.X, c->cv.probe_q.as<float>());
+      hipLaunchKernelGGL(kp_cv_rankq64<true>, dim3(m), dim3(64), 0, c->stream, c->cv.probe_q.as<float>(), d.X, c->dE, K,
+                         DP, pd.trip + 3 * (size_t)r0, m, pd.q, pd.t, pd.kcol);
+      KP_HIP(hipGetLastError());
+    });
   } else {
     const int ld = round_up(K + 1, 4);
     float* dScores = ensure_n<float>(c->rank.scores, (size_t)ns * ld);
@@ -1126,6 +1154,7 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   const double t_in = g_host_times ? host_ms() : 0.0;
   require_batch(c, bt, "ConvE");
   require_topk(tk, c->cv_rank64 != 0, "ConvE");
+  require_probes(c, bt, tk, c->cv_rank64 != 0, "ConvE");
   KP_REQUIRE(hp->batch_size >= 1 && hp->epochs >= 0, "ConvE: bad hyper-parameters");
   const CvConst kc = make_const(c, hp);
 
@@ -1137,6 +1166,7 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
 
   std::vector<float> xp;
   CvDev d = cv_workspaces(c, bt, sp, xp);
+  const ProbeDev pd = cv_probe_workspaces(c, bt, tk);
   const double t_up = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipEventRecord(c->ev0, c->stream));
   const int nfp = cv_frozen_fc(c, kc, sp, d);
@@ -1145,9 +1175,9 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   const int64_t launches = cv_step_loop(c, hp, kc, sp, d);
   const double t_loop = g_host_times ? host_ms() : 0.0;
 
-  const RankDev rk = cv_rank(c, kc, bt, tk, d);
+  const RankDev rk = cv_rank(c, kc, bt, tk, d, pd);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
-  download_results(c, bt, d.X, rk, xp, tk);
+  download_results(c, bt, d.X, rk, xp, tk, pd);
   if (g_host_times)
     std::fprintf(stderr, "[kp_cv] slots %d steps %d pairs %zu: plan %.2f ms, uploads %.2f ms, loop enqueue %.2f ms, "
                  "rank + wait %.2f ms\n", bt->n_slots, sp.T, sp.kinst.size(), t_plan - t_in, t_up - t_plan,

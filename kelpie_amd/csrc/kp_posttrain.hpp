@@ -13,6 +13,7 @@
 
 #include "kp_batch_check.hpp"
 #include "kp_common.hpp"
+#include "kp_probe_check.hpp"
 
 // KP_HOST_TIMES=1 (diagnostic): ComplEx and ConvE print, per call on stderr, the host time
 // of their phases (planning, uploads, enqueueing the loop, waiting for the device)
@@ -36,6 +37,16 @@ inline void require_topk(const TopkOut& tk, bool rank64, const char* model) {
   if (tk.k > 0 && (!tk.ids || !tk.scores)) throw KpError{KP_EINVAL, std::string(model) + ": top-k: missing output"};
   if (tk.k > 0 && !rank64)
     throw KpError{KP_ENOTSUP, std::string(model) + ": top-k needs the fp64 rank (the fp32 rank switch is set)"};
+}
+
+// kp_posttrain_rank_probes' probes (kp_probe_check.hpp), checked right after the batch and
+// the top-k request and before the first upload; like the lists they need the fp64 rank
+inline void require_probes(const kp_ctx* c, const kp_batch* bt, const TopkOut& tk, bool rank64, const char* model) {
+  if (!tk.probes) return;
+  if (const char* why = kp_check_probes(c->n_ent, c->n_rel2, bt->n_slots, tk.probes))
+    throw KpError{KP_EINVAL, std::string(model) + ": probes: " + why};
+  if (tk.probes->n > 0 && !rank64)
+    throw KpError{KP_ENOTSUP, std::string(model) + ": probes need the fp64 rank (the fp32 rank switch is set)"};
 }
 
 // Adam's per-step scalars at step t (0-based) of a call: lr / (1 - beta1^(t+1)) and
@@ -102,12 +113,74 @@ inline Rank64Dev rank64_buffers(kp_ctx* c, int ns) {
   return r;
 }
 
+// the probes on the device (c->rank.p_*): inputs and results of all n probes, and the fp64
+// operands of one chunk of probe rows (the chunks run one after the other on the stream)
+constexpr size_t PROBE_WS_BYTES = (size_t)64 << 20;  // a chunk's query rows and bitmaps, as TOPK_WS_BYTES
+constexpr int PROBE_GROUP = 16;                      // kp_rank_f64_count's rows per workgroup row (RQ)
+struct ProbeDev {
+  int n = 0, chunk = 0;
+  int32_t* trip = nullptr;  // [n][3] (slot, p, o)
+  int32_t* po = nullptr;    // [n]
+  int32_t* filt_off = nullptr;
+  int32_t* filt = nullptr;
+  float* target = nullptr;  // [n]
+  int64_t* rank = nullptr;  // [n]
+  double *q = nullptr, *t = nullptr, *kcol = nullptr;  // [chunk][dp], [chunk], [chunk]
+};
+
+// upload the probes and size every probe buffer; called with the call's other uploads,
+// ahead of the step loop.  `extra_row_bytes`: what else the model holds per probe row of a
+// chunk (ConvE: the encoder's rows), counted into the chunk's budget
+inline ProbeDev upload_probes(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, size_t extra_row_bytes = 0) {
+  ProbeDev d;
+  const int n = tk.n_probes();
+  if (n == 0) return d;
+  const kp_probes* pr = tk.probes;
+  std::vector<int32_t> trip((size_t)n * 3), po(n);
+  for (int s = 0; s < bt->n_slots; ++s)
+    for (int i = pr->probe_off[s]; i < pr->probe_off[s + 1]; ++i) {
+      trip[3 * (size_t)i] = s;
+      trip[3 * (size_t)i + 1] = pr->probes[2 * (size_t)i];
+      trip[3 * (size_t)i + 2] = po[i] = pr->probes[2 * (size_t)i + 1];
+    }
+  const int nwords = (c->n_ent + 1 + 31) / 32;
+  int forced = 0;
+  if (const char* a = std::getenv("KP_PROBE_CHUNK")) forced = std::max(0, std::atoi(a));
+  d.n = n;
+  d.chunk = kp_probe_chunk(n, sizeof(double) * c->dp + sizeof(uint32_t) * nwords + extra_row_bytes, PROBE_WS_BYTES,
+                           PROBE_GROUP, forced);
+  d.trip = upload(c, c->rank.p_trip, trip.data(), trip.size());
+  d.po = upload(c, c->rank.p_po, po.data(), po.size());
+  d.filt_off = upload(c, c->rank.p_filt_off, pr->filt_off, (size_t)n + 1);
+  d.filt = upload(c, c->rank.p_filt, pr->filt, (size_t)pr->filt_off[n]);
+  d.target = reinterpret_cast<float*>(c->rank.p_target.ensure(sizeof(float) * (size_t)n));
+  d.rank = reinterpret_cast<int64_t*>(c->rank.p_rank.ensure(sizeof(int64_t) * (size_t)n));
+  d.q = reinterpret_cast<double*>(c->rank.p_q64.ensure(sizeof(double) * (size_t)d.chunk * c->dp));
+  d.t = reinterpret_cast<double*>(c->rank.p_t64.ensure(sizeof(double) * 2 * (size_t)d.chunk));
+  d.kcol = d.t + d.chunk;
+  (void)c->rank.p_bits.ensure(sizeof(uint32_t) * (size_t)d.chunk * nwords);
+  return d;
+}
+
+// rank the probe rows, chunk by chunk: `queries(r0, m)` enqueues the model's probe form of
+// its query kernel for the probes [r0, r0 + m) (their fp64 rows, target and kelpie column
+// scores into d.q / d.t / d.kcol), then the slots' own count runs over those rows (k = 0)
+template <class F>
+inline void rank_probes(kp_ctx* c, const ProbeDev& d, int act, F&& queries) {
+  for (int r0 = 0; r0 < d.n; r0 += d.chunk) {
+    const int m = std::min(d.chunk, d.n - r0);
+    queries(r0, m);
+    launch_rank_f64(c, m, d.q, d.t, d.kcol, d.po + r0, d.filt_off + r0, d.filt, d.target + r0, d.rank + r0, act, 0,
+                    nullptr, nullptr, &c->rank.p_bits);
+  }
+}
+
 // the tail of a call: enqueue the downloads of the kelpie rows (when out_x is set), the
-// target scores, the ranks and the top-k lists (when asked for), wait for the stream once,
-// unpad the rows into out_x.
+// target scores, the ranks, the top-k lists and the probes' results (when asked for), wait
+// for the stream once, unpad the rows into out_x.
 // Returns the host time at which the wait began (0 unless KP_HOST_TIMES).
 inline double download_results(kp_ctx* c, const kp_batch* bt, const float* dX, const RankDev& r,
-                               std::vector<float>& xp, const TopkOut& tk = {}) {
+                               std::vector<float>& xp, const TopkOut& tk = {}, const ProbeDev& pd = {}) {
   const int ns = bt->n_slots;
   if (bt->out_x) KP_HIP(hipMemcpyAsync(xp.data(), dX, sizeof(float) * xp.size(), hipMemcpyDeviceToHost, c->stream));
   KP_HIP(hipMemcpyAsync(bt->out_score, r.target, sizeof(float) * ns, hipMemcpyDeviceToHost, c->stream));
@@ -116,6 +189,10 @@ inline double download_results(kp_ctx* c, const kp_batch* bt, const float* dX, c
     const size_t n = (size_t)ns * tk.k;
     KP_HIP(hipMemcpyAsync(tk.ids, r.top_ids, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
     KP_HIP(hipMemcpyAsync(tk.scores, r.top_scores, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (pd.n > 0) {
+    KP_HIP(hipMemcpyAsync(tk.probes->out_score, pd.target, sizeof(float) * pd.n, hipMemcpyDeviceToHost, c->stream));
+    KP_HIP(hipMemcpyAsync(tk.probes->out_rank, pd.rank, sizeof(int64_t) * pd.n, hipMemcpyDeviceToHost, c->stream));
   }
   const double t_wait = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipStreamSynchronize(c->stream));

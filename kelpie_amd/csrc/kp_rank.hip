@@ -482,7 +482,7 @@ constexpr size_t TOPK_WS_BYTES = (size_t)64 << 20;
 
 void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* d_t64, const double* d_kcol64,
                      const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt, float* d_target,
-                     int64_t* d_rank, int act, int topk, int32_t* d_top_ids, float* d_top_scores) {
+                     int64_t* d_rank, int act, int topk, int32_t* d_top_ids, float* d_top_scores, DevBuf* bits_buf) {
   if (n_slots <= 0) return;
   const int ldt = (c->n_ent + 255) / 256 * 256;
   if (!c->eT_ready) {
@@ -494,7 +494,8 @@ void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* 
   }
   const int n_cols = c->n_ent + 1;
   const int nwords = (n_cols + 31) / 32;
-  uint32_t* bits = reinterpret_cast<uint32_t*>(c->rank.bits.ensure(sizeof(uint32_t) * (size_t)n_slots * nwords));
+  DevBuf& bb = bits_buf ? *bits_buf : c->rank.bits;
+  uint32_t* bits = reinterpret_cast<uint32_t*>(bb.ensure(sizeof(uint32_t) * (size_t)n_slots * nwords));
   unsigned long long* rank = reinterpret_cast<unsigned long long*>(d_rank);
   hipLaunchKernelGGL(kp_rank_filter_bits, dim3(n_slots), dim3(256), 0, c->stream, n_slots, nwords, d_filt_off, d_filt,
                      n_cols, bits);

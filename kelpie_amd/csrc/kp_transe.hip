@@ -476,13 +476,16 @@ void launch_te_scores(kp_ctx* c, int nq, const int32_t* dh, const int32_t* dr, c
 // chain over d, the order
 // kp_rank_f64_count scores every entity in.  An fp32 norm over 200 terms is ~1e-7
 // relative off, enough to swap near-tied entities (FB15k-237 necessary fixtures).
+// PROBE (kp_posttrain_rank_probes): row s is a probe, pred its (slot, p, o), and x the
+// kelpie row of that slot instead of row s; every operation and its order are the slot form's
+template <bool PROBE = false>
 __global__ void kp_te_rankq64(const float* __restrict__ X, const float* __restrict__ R,
                               const float* __restrict__ E, int n_ent, int dp, const int32_t* __restrict__ pred,
                               int n_slots, double* __restrict__ Q, double* __restrict__ t64,
                               double* __restrict__ kcol64, int l1) {
   const int s = blockIdx.x;
   if (s >= n_slots) return;
-  const float* x = X + (size_t)s * dp;
+  const float* x = X + (size_t)(PROBE ? pred[3 * s] : s) * dp;
   const float* r = R + (size_t)pred[3 * s + 1] * dp;
   double* q = Q + (size_t)s * dp;
   for (int d = threadIdx.x; d < dp; d += blockDim.x) q[d] = (double)x[d] + (double)r[d];
@@ -516,6 +519,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   const bool l1 = c->te_norm == 1;
   require_batch(c, bt, "TransE");
   require_topk(tk, c->te_rank64 != 0, "TransE");
+  require_probes(c, bt, tk, c->te_rank64 != 0, "TransE");
   // before the first upload: the buffers below are sized by DP, the kernels hold DP / 256 float4 per lane
   KP_REQUIRE(DP <= 512, "TransE: dimension > 512 not supported");
   KP_REQUIRE(hp->neg_ratio >= 1 && hp->batch_size >= 1 && hp->epochs >= 0, "TransE: bad hyper-parameters");
@@ -533,6 +537,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   int32_t* dRows = upload(c, c->te.rows, bt->rows, (size_t)std::max(1, 3 * total_rows));
   const int64_t nrng = bt->rng_off[ns];
   int32_t* dRng = upload(c, c->te.rng, bt->rng, (size_t)std::max<int64_t>(1, nrng));
+  const ProbeDev pd = upload_probes(c, bt, tk);
 
   TeHp h{};
   h.epochs = hp->epochs;
@@ -606,18 +611,23 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   if (c->te_rank64) {
     int32_t* dPred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
     const Rank64Dev r64 = rank64_buffers(c, ns);
-    hipLaunchKernelGGL(kp_te_rankq64, dim3(ns), dim3(64), 0, c->stream, dX, c->dR, c->dE, c->n_ent, DP, dPred, ns,
-                       r64.q, r64.t, r64.kcol, l1 ? 1 : 0);
+    hipLaunchKernelGGL(kp_te_rankq64<false>, dim3(ns), dim3(64), 0, c->stream, dX, c->dR, c->dE, c->n_ent, DP, dPred,
+                       ns, r64.q, r64.t, r64.kcol, l1 ? 1 : 0);
     KP_HIP(hipGetLastError());
     launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank,
                     l1 ? RANK64_DIST1 : RANK64_DIST, tk.k, rk.top_ids, rk.top_scores);
+    rank_probes(c, pd, l1 ? RANK64_DIST1 : RANK64_DIST, [&](int r0, int m) {
+      hipLaunchKernelGGL(kp_te_rankq64<true>, dim3(m), dim3(64), 0, c->stream, dX, c->dR, c->dE, c->n_ent, DP,
+                         pd.trip + 3 * (size_t)r0, m, pd.q, pd.t, pd.kcol, l1 ? 1 : 0);
+      KP_HIP(hipGetLastError());
+    });
   } else {
     float* dScores = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)ns * ld));
     launch_te_scores(c, ns, dH, dRl, dX, dScores, ld, c->n_ent);
     launch_rank_count(c, ns, dScores, ld, c->n_ent + 1, rk.po, rk.filt_off, rk.filt, 1, rk.target, rk.rank);
   }
   KP_HIP(hipEventRecord(c->ev1, c->stream));
-  download_results(c, bt, dX, rk, xp, tk);
+  download_results(c, bt, dX, rk, xp, tk, pd);
   float ms_all = 0.f, ms_hot = 0.f;
   KP_HIP(hipEventElapsedTime(&ms_all, c->ev0, c->ev1));
   KP_HIP(hipEventElapsedTime(&ms_hot, ea, eb));

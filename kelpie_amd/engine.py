@@ -50,6 +50,9 @@ class _Slot:
     # rows and filter held by the library's host scheduler instead of rows / filt:
     # (SchedBatch, its slot index, row count, filter length) (kelpie_amd/_lib.py)
     native: tuple = None
+    # probes ranked on this slot's post-trained row (compute_side_effects): a list of
+    # (triple in original ids, (p, o) in kelpie form, filter); None: no probes asked for
+    probes: list = None
 
 
 def _contiguous_draws(slots, total, ctx=None):
@@ -173,9 +176,69 @@ class PostTrainingEngine(RelevanceEngine):
         self.set_cache()
         self.last_batch_stats = {}
         self._top_k = 0
+        self._side_effects = 0
+        self._probe_req = None
+        self._cur_probes = None
 
     TOP_K_MAX = 32  # kp_posttrain_rank_topk's largest k
     _top_k = 0
+    PROBES_MAX = 64  # probes per slot
+    _side_effects = 0    # default probes per prediction (side_effects)
+    _probe_req = None    # compute_side_effects' explicit probes: (subject, [triples])
+    _cur_probes = None   # the probes of the prediction being scheduled: (subject, [triples]) or None
+
+    @property
+    def side_effects(self):
+        """How many of the subject's other held-out facts every post-training also ranks (0:
+        none, the default; at most ``PROBES_MAX``): the subject's validation then test triples
+        without the prediction, the first ``side_effects`` of them, each ranked on the slot's
+        post-trained row as ``get_triple_results`` ranks the prediction
+        (post_training_engine.py:101-125).  Every slot's result gains ``"probes"``:
+        [{"triple", "score", "rank"}].  The relevances, the draws and the batches are those of
+        ``side_effects`` = 0."""
+        return self._side_effects
+
+    @side_effects.setter
+    def side_effects(self, cap):
+        if isinstance(cap, bool) or int(cap) != cap:
+            raise TypeError(f"side_effects must be an integer, got {cap!r}")
+        if not 0 <= int(cap) <= self.PROBES_MAX:
+            raise ValueError(f"side_effects must be in [0, {self.PROBES_MAX}], got {cap}")
+        self._side_effects = int(cap)
+
+    def default_probes(self, pred, cap):
+        """The subject's validation then test triples without the prediction, the first ``cap``."""
+        ds = self.dataset
+        pred = tuple(int(v) for v in pred)
+        held = list(ds.entity_to_validation_triples.get(pred[0], [])) + list(ds.entity_to_testing_triples.get(pred[0], []))
+        return [t for t in (tuple(int(v) for v in x) for x in held) if t != pred][:int(cap)]
+
+    def _probes_of(self, pred):
+        """(subject, probes) of a prediction about to be scheduled, or None."""
+        s = int(pred[0])
+        if self._probe_req is not None:
+            return self._probe_req
+        if self._side_effects:
+            return (s, self.default_probes(pred, self._side_effects))
+        return None
+
+    def _slot_probes(self, view, delta):
+        """The probes of one slot of ``view`` whose edit's filter delta is ``delta`` (None: the
+        base slot): each of the prediction's probes moved to the view's entity as the
+        prediction is, in kelpie form -- the view's entity as tail gives the inverse relation's
+        (p + |R|, head) -- with to_filter[(kelpie, p)] after the edit."""
+        if self._cur_probes is None:
+            return None
+        s, probes = self._cur_probes
+        e, k, R = view.original_entity, view.kelpie_entity, self.dataset.num_relations
+        out = []
+        for t in probes:
+            t = Dataset.replace_entity_in_triple(t, s, e)
+            a, p, b = view.as_kelpie_triple(t)
+            if a != k:
+                p, b = p + R, a
+            out.append((t, (int(p), int(b)), list(view.filter_for(p, delta.get(p) if delta else None))))
+        return out
 
     @property
     def top_k(self):
@@ -240,10 +303,12 @@ class PostTrainingEngine(RelevanceEngine):
         if pred not in self.base_pt_results and pred not in pending_base:
             pending_base[pred] = len(slots)
             slots.append(self._slot(x_base, view.base_rows, kp, view.filter_for(kp[1])))
+            slots[-1].probes = self._slot_probes(view, None)
         x_pt = self.model.kelpie_init(init, self.rng)
         rows, delta = view.removed(triples) if mode == "necessary" else view.added(triples)
         filt = view.filter_for(kp[1], delta.get(kp[1]))
         slots.append(self._slot(x_pt, rows, kp, filt))
+        slots[-1].probes = self._slot_probes(view, delta)
         return len(slots) - 1, pred
 
     def _schedule_sharded(self, pred, view, triples, mode, slots, pending_base):
@@ -324,6 +389,7 @@ class PostTrainingEngine(RelevanceEngine):
         pt = _Slot(None, None, None, kp, None, None, own_pt, pt_owner, (sb, sb.n_slots))
         sb.n_slots += 1
         slots.append(pt)
+        self._fused_probes(view, triples, mode, base, pt)
         # a queued call: (view, kelpie triple, rule triples, flags, base slot, pt slot)
         self._fused.append((view, kp, [(int(a), int(b), int(c)) for a, b, c in triples],
                             (1 if need_base else 0) | (2 if own_base else 0) | (4 if own_pt else 0)
@@ -334,6 +400,16 @@ class PostTrainingEngine(RelevanceEngine):
             # the sequential numpy chain starts right away)
             self._flush_fused()
         return len(slots) - 1, pred
+
+    def _fused_probes(self, view, triples, mode, base, pt):
+        """The probes of a queued TransE call's slots: the library's scheduler makes the edit
+        and the rank filter; the probes' filters need the edit's delta here as well."""
+        if self._cur_probes is None:
+            return
+        if base is not None:
+            base.probes = self._slot_probes(view, None)
+        conv = [Dataset.replace_entity_in_triple(tuple(t), view.original_entity, view.kelpie_entity) for t in triples]
+        pt.probes = self._slot_probes(view, view._delta(conv, -1 if mode == "necessary" else +1))
 
     def _schedule_fused_pred(self, pred, rules, mode, slots, pending_base):
         """:meth:`_schedule_fused` for every rule of one prediction (no checkpoints, no
@@ -376,6 +452,8 @@ class PostTrainingEngine(RelevanceEngine):
             pt = _Slot(None, None, None, kp, None, None, own_pt, pt_owner, (sb, j))
             append(pt)
             sb.n_slots = j + 1
+            if self._cur_probes is not None:
+                self._fused_probes(view, triples, mode, base, pt)
             fused.append((view, kp, triples, (1 if need_base else 0) | (2 if own_base else 0) | (4 if own_pt else 0)
                           | suf, base, pt))
             out.append((len(slots) - 1, pred))
@@ -476,6 +554,9 @@ class PostTrainingEngine(RelevanceEngine):
         if self._top_k and self._sharded():
             # before any draw: the gather's records hold a score and a rank per slot
             raise NotImplementedError("top_k > 0 with a slot sharding: the lists are not gathered across ranks")
+        if (self._side_effects or self._probe_req is not None) and self._sharded():
+            # before any draw, as the lists
+            raise NotImplementedError("probes with a slot sharding: their results are not gathered across ranks")
         self._sched = None  # this batch's natively assembled slots (TransE), made on first use
         if self._sharded():
             # ComplEx / ConvE: every rank owns one contiguous run of the batch's slots, so it
@@ -557,6 +638,19 @@ class PostTrainingEngine(RelevanceEngine):
             else np.zeros(1, np.int32)
         assert x0.shape == (n, self.model.dimension)
         return x0, row_off, rows, rng_off, rng, pred, filt_off, filt
+
+    @staticmethod
+    def _pack_probes(slots):
+        """The library call's probe arrays (probe_off, probes [n][2], filt_off, filt)."""
+        per = [s.probes or [] for s in slots]
+        p_off = np.zeros(len(slots) + 1, np.int32)
+        p_off[1:] = np.cumsum([len(p) for p in per])
+        flat = [pr for p in per for pr in p]
+        tr = np.array([po for _, po, _ in flat], np.int32).reshape(-1, 2)
+        f_off = np.zeros(len(flat) + 1, np.int32)
+        f_off[1:] = np.cumsum([len(f) for _, _, f in flat])
+        filt = np.array([e for _, _, f in flat for e in f] or [0], np.int32)
+        return p_off, tr, f_off, filt
 
     @staticmethod
     def _native_arrays(sb):
@@ -655,14 +749,25 @@ class PostTrainingEngine(RelevanceEngine):
             return None
         t_lib = time.perf_counter()
         k = self._top_k
+        kw = {"topk": k} if k else {}
+        probed = any(s.probes is not None for s in slots)
+        if probed:
+            kw["probes"] = self._pack_probes(slots)
+        out = ctx.posttrain_rank(self._kp_hp, *packed, **kw)
+        score, rank = out[0], out[1]
         if k:
-            score, rank, _, (top_ids, top_scores) = ctx.posttrain_rank(self._kp_hp, *packed, topk=k)
-        else:
-            score, rank, _ = ctx.posttrain_rank(self._kp_hp, *packed)
+            top_ids, top_scores = out[3]
         t_end = time.perf_counter()
         if fill:
             for i, s in enumerate(slots):
                 s.result = {"target_score": float(score[i]), "target_rank": int(rank[i])}
+            if probed:
+                p_score, p_rank = out[-1]
+                j = 0
+                for s in slots:
+                    s.result["probes"] = [{"triple": t, "score": float(p_score[j + i]), "rank": int(p_rank[j + i])}
+                                          for i, (t, _, _) in enumerate(s.probes or [])]
+                    j += len(s.probes or [])
             if k:
                 top_ids, top_scores = np.asarray(top_ids), np.asarray(top_scores)
                 # a list ends at its first -1 (fewer than k unmasked columns)
@@ -727,6 +832,47 @@ class PostTrainingEngine(RelevanceEngine):
         finally:
             self._top_k = old
         return [self._cf_rule(rel, det, int(k)) for rel, det in zip(rels, self.last_results)]
+
+    @staticmethod
+    def _se_side(res):
+        """One post-training of a side-effects report: its target score and rank and its
+        probes' [{"triple", "score", "rank"}], None when the result was cached without them."""
+        return {"score": res["target_score"], "rank": res["target_rank"], "probes": res.get("probes")}
+
+    def _se_rule(self, relevance, detail):
+        raise NotImplementedError
+
+    def compute_side_effects(self, pred, rules, probes=None, cap=16):
+        """``compute_relevance_batch(pred, rules)`` -- the same schedule, draws, batches and
+        relevances, the generators left where it leaves them -- that also reports what each
+        edit does to the subject's other facts: ``probes`` are triples about the prediction's
+        subject (default: :meth:`default_probes`, the first ``cap``), each moved to the slot's
+        entity as the prediction is and ranked on the slot's post-trained row as
+        ``get_triple_results`` ranks the prediction (post_training_engine.py:101-125).  Per rule
+        ``{"relevance", "base", "post"}`` (the sufficient engine: ``{"relevance",
+        "conversions": [{"entity", "base", "post"}, ...]}``), ``base`` / ``post`` =
+        ``{"score", "rank", "probes"}``, ``probes`` = [{"triple", "score", "rank"}] with the
+        triple in original ids.  No post-training runs for the sake of a probe: a base result
+        cached without probes reports ``"probes": None``."""
+        pred = tuple(int(v) for v in pred)
+        if probes is None:
+            if isinstance(cap, bool) or int(cap) != cap:
+                raise TypeError(f"cap must be an integer, got {cap!r}")
+            if int(cap) < 0:
+                raise ValueError(f"cap must not be negative, got {cap}")
+            probes = self.default_probes(pred, cap)
+        probes = [tuple(int(v) for v in t) for t in probes]
+        if len(probes) > self.PROBES_MAX:
+            raise ValueError(f"at most {self.PROBES_MAX} probes per slot, got {len(probes)}")
+        view = self._get_kelpie_dataset(pred[0])
+        for t in probes:
+            view.as_kelpie_triple(t)  # "Could not find the original entity": before any draw
+        self._probe_req = (pred[0], probes)
+        try:
+            rels = self.compute_relevance_batch(pred, rules)
+        finally:
+            self._probe_req = None
+        return [self._se_rule(rel, det) for rel, det in zip(rels, self.last_results)]
 
     def _schedule_multi(self, items, checkpoints):
         raise NotImplementedError
@@ -1120,6 +1266,7 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
         slots, pending, jobs = [], {}, []
         fast = checkpoints is None and getattr(self.model, "fused_call_draws", False)
         for pred, rules in items:
+            self._cur_probes = self._probes_of(pred)
             if fast and all(len(r) for r in rules):
                 jobs.append(self._schedule_fused_pred(pred, rules, "necessary", slots, pending))
                 continue
@@ -1171,6 +1318,10 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
         pt, base = detail
         return {"relevance": relevance, "base": self._cf_side(base, k), "post": self._cf_side(pt, k)}
 
+    def _se_rule(self, relevance, detail):
+        pt, base = detail
+        return {"relevance": relevance, "base": self._se_side(base), "post": self._se_side(pt)}
+
 
 class SufficientPostTrainingEngine(PostTrainingEngine):
     """post_training_engine.py:160-207."""
@@ -1179,6 +1330,11 @@ class SufficientPostTrainingEngine(PostTrainingEngine):
         # one (post-trained, base) pair per conversion entity, in entities_to_convert's order
         return {"relevance": relevance,
                 "conversions": [{"entity": int(e), "base": self._cf_side(base, k), "post": self._cf_side(pt, k)}
+                                for e, (pt, base) in zip(self.entities_to_convert, detail)]}
+
+    def _se_rule(self, relevance, detail):
+        return {"relevance": relevance,
+                "conversions": [{"entity": int(e), "base": self._se_side(base), "post": self._se_side(pt)}
                                 for e, (pt, base) in zip(self.entities_to_convert, detail)]}
 
     def __init__(self, model, dataset, hp, rng=None):
@@ -1214,6 +1370,7 @@ class SufficientPostTrainingEngine(PostTrainingEngine):
         for pred, rules, ents in items:
             pred = tuple(int(v) for v in pred)
             s = pred[0]
+            self._cur_probes = self._probes_of(pred)
             pj = []
             for rule in rules:
                 if not ents:

@@ -10,7 +10,9 @@ Mirrors the reference's callers of the relevance engine:
   ``output.json`` list of ``{"triple", "rule_to_relevance", "#relevances",
   "execution_time"[, "entities_to_convert"]}`` records, rewritten after every
   prediction as the reference does.  With ``top_k`` > 0 every record also holds
-  ``"counterfactuals"`` (kelpie_amd/builder.py): what the model predicts instead.
+  ``"counterfactuals"`` (kelpie_amd/builder.py): what the model predicts instead.  With
+  ``side_effects`` > 0 every record also holds ``"side_effects"``: what each rule's edit
+  does to the subject's other held-out facts.
 
 The DP / CRIAGE baselines and summarisation are out of scope.
 """
@@ -53,7 +55,7 @@ class SufficientPipeline(Pipeline):
 
 
 def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="auto", entity_classes=None,
-                   pipelined=False, top_k=0):
+                   pipelined=False, top_k=0, side_effects=0):
     """explain.py:49-89 for the post-training engines (baseline=None, no summarisation)."""
     if prefilter == TYPE_PREFILTER:
         raise NotImplementedError("type_based prefilter: out of scope (kelpie_amd/prefilters.py)")
@@ -63,12 +65,12 @@ def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="a
         xsi = 5 if xsi is None else xsi
         engine = NecessaryPostTrainingEngine(model, dataset, hp)
         return NecessaryPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
-                                                                  top_k=top_k))
+                                                                  top_k=top_k, side_effects=side_effects))
     if mode == "sufficient":
         xsi = 0.9 if xsi is None else xsi
         engine = SufficientPostTrainingEngine(model, dataset, hp)
         return SufficientPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
-                                                                  top_k=top_k))
+                                                                  top_k=top_k, side_effects=side_effects))
     raise ValueError(f"unknown mode {mode!r}")
 
 
@@ -83,10 +85,14 @@ def write_explanations(path, explanations):
         json.dump(explanations, f)
 
 
-def explain_preds(pipeline, dataset, preds, prefilter_k, skip=-1, output_path=None):
+def explain_preds(pipeline, dataset, preds, prefilter_k, skip=-1, output_path=None, side_effects=None):
     """The loop of explain.py:190-203: label triples -> ids -> pipeline.explain;
     predictions with index <= skip are skipped; ``output.json`` is rewritten after
-    each prediction when ``output_path`` is given."""
+    each prediction when ``output_path`` is given.  ``side_effects`` (a cap, 0 = off): set
+    on the pipeline's builder and engine for this and later calls (None: as they are)."""
+    if side_effects is not None:
+        pipeline.engine.side_effects = int(side_effects)
+        pipeline.builder.side_effects = int(side_effects)
     explanations = []
     for i, pred in enumerate(preds):
         if i <= skip:
@@ -137,7 +143,7 @@ def reference_construction_draws(model_name, num_entities, num_relations, model_
 
 
 def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefilter=None, prefilter_k=20,
-                xsi=None, skip=-1, output_path=None, device=0, top_k=0):
+                xsi=None, skip=-1, output_path=None, device=0, top_k=0, side_effects=0):
     """explain.py main() (explain.py:143-203) without the CLI: seeds 42 (explain.py:144),
     the reference model construction's random draws (:171-172), the checkpoint state dict
     (``torch.load(path, weights_only=True)``, :174) as a frozen model on the MI355X, the
@@ -153,5 +159,6 @@ def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefi
     torch.manual_seed(42)
     reference_construction_draws(model_name, dataset.num_entities, dataset.num_relations, model_params)
     model = from_state_dict(model_name, dataset, state, model_params, device=device)
-    pipe = build_pipeline(model, dataset, hp, mode, prefilter=prefilter, xsi=xsi, top_k=top_k)
+    pipe = build_pipeline(model, dataset, hp, mode, prefilter=prefilter, xsi=xsi, top_k=top_k,
+                          side_effects=side_effects)
     return explain_preds(pipe, dataset, preds, prefilter_k=prefilter_k, skip=skip, output_path=output_path)
