@@ -11,7 +11,7 @@ LIB := kelpie_amd/libkelpie_hip.so
 
 all: $(LIB)
 
-build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn_plan.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp kelpie_amd/csrc/kp_probe_check.hpp kelpie_amd/csrc/kp_cx_plan.hpp kelpie_amd/csrc/kp_cv_plan.hpp include/kelpie_hip.h
+build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn_plan.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp kelpie_amd/csrc/kp_probe_check.hpp kelpie_amd/csrc/kp_trace_check.hpp kelpie_amd/csrc/kp_cx_plan.hpp kelpie_amd/csrc/kp_cv_plan.hpp include/kelpie_hip.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -106,4 +106,18 @@ build/san/probe_check_asan: $(PROBE_CHECK_DEP)
 	@mkdir -p build/san
 	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
 
-.PHONY: asan tsan batch_asan attn_plan attn_plan_asan step_plan step_plan_asan probe_check probe_check_asan
+# the trace's step counts and check (kp_trace_check.hpp, no HIP) alone in
+# tests/native/trace_check_driver.cpp, plain and under the host sanitizers; run by
+# tests/test_trace_check.py (CPU suite)
+TRACE_CHECK_DEP := tests/native/trace_check_driver.cpp kelpie_amd/csrc/kp_trace_check.hpp include/kelpie_hip.h
+trace_check: build/san/trace_check
+trace_check_asan: build/san/trace_check_asan
+build/san/trace_check: $(TRACE_CHECK_DEP)
+	@mkdir -p build/san
+	$(CXX) -O2 -std=c++17 -Wall $< -o $@
+build/san/trace_check_asan: $(TRACE_CHECK_DEP)
+	@mkdir -p build/san
+	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
+
+.PHONY: asan tsan batch_asan attn_plan attn_plan_asan step_plan step_plan_asan probe_check probe_check_asan \
+        trace_check trace_check_asan

@@ -219,6 +219,56 @@ typedef struct {
 int kp_posttrain_rank_probes(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
                              float* out_scores, const kp_probes* probes);
 
+/* ---- Post-training trace: the optimizer's loss of every step of every slot ----
+ * Step j of slot s is the j-th step_on_batch call of that post-training in the reference
+ * (multiclass_nll_optimizer.py:147-164, pairwise_ranking_optimizer.py:165-203,
+ * bce_optimizer.py:167-208); its trace value is the `l` that call returns: the loss at the
+ * kelpie row BEFORE the step's update, on the step's minibatch of B rows, with the step's
+ * own dropout masks.
+ *   ComplEx / DistMult  CrossEntropyLoss(mean) of the batch's rows against all n_ent + 1
+ *       columns, the kelpie column included, plus the regulariser's value:
+ *       N3 (regularizers.py:37-46)  w (sum |lhs|^3 + sum |rel|^3 + sum |rhs|^3) / B,
+ *       N2 (regularizers.py:25-35)  w (sum_rows ||lhs||^3 + ||rel||^3 + ||rhs||^3) / B,
+ *       |.| the model's factor modulus (ComplEx sqrt(re^2 + im^2), complex.py:80-84;
+ *       DistMult |x_i|, distmult.py:66), ||.|| the 2-norm of a row's moduli.  The frozen
+ *       rows' factors count in the value (they are constant in the gradient, not in l).
+ *   TransE  mean(max(0, f+ - f- + margin)) + lambda (L2(pos) + L2(neg)) / 2,
+ *       L2 = (mean lhs^2 + mean rel^2 + mean rhs^2) / 3 over the rows actually stepped
+ *       (regularizers.py:15-22, pairwise_ranking_optimizer.py:183-203).
+ *   ConvE   BCELoss (mean over B x (n_ent + 1), every log clamped at -100 as torch does) of
+ *       the train-mode forward -- batch norms in eval mode, the three dropouts with the
+ *       masks the step draws -- against the targets (1 - ls) y + 1 / (n_ent + 1)
+ *       (bce_optimizer.py:190-208).
+ * Steps per slot: ComplEx / DistMult / TransE epochs * ceil(R / batch_size), R the slot's
+ * rows including the inverses; ConvE epochs * ceil(P / batch_size), P the slot's distinct
+ * (head, relation) pairs (er_vocab).  A slot without rows has zero steps.
+ * A value is accumulated in fp64 in a fixed order and rounded to fp32 once, at the store: a
+ * trace is bitwise the same on a rerun with a fresh context. */
+
+/* out_steps[s] = the steps of slot s by the rule above: pure host work, no context.  hp:
+ * epochs and batch_size are read.  KP_EINVAL (kp_last_error(NULL) names the rule) for an
+ * unknown model, batch_size <= 0, epochs < 0, a row_off that does not start at 0 or
+ * decreases, or a missing array. */
+int kp_trace_steps(int32_t model, const kp_hp* hp, int32_t n_slots, const int32_t* row_off, const int32_t* rows,
+                   int32_t* out_steps);
+
+/*   trace_off   [n_slots+1]            CSR offsets into out_loss: the prefix sums of kp_trace_steps
+ *   out_loss    [trace_off[n_slots]]   slot s's losses at [trace_off[s], trace_off[s+1]), step order */
+typedef struct {
+  const int32_t* trace_off;
+  float* out_loss;
+} kp_trace;
+
+/* kp_posttrain_rank_probes, plus the trace of every slot.  out_x, out_score, out_rank, the
+ * top-k lists and the probes' results are bit for bit those without the trace.  trace == NULL
+ * is kp_posttrain_rank_probes.  KP_EINVAL (after the batch and probe checks, before any
+ * upload) for a trace_off that disagrees with kp_trace_steps or a NULL out_loss with steps
+ * to write.  The trace does not depend on the rank: the fp32 rank switches do not refuse it.
+ * Every model family.  ConvE scores each row of a step against all columns for it, in chunks
+ * of rows whose logits stay within 64 MiB (KP_TRACE_CHUNK=n, a diagnostic, forces n rows). */
+int kp_posttrain_rank_trace(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
+                            float* out_scores, const kp_probes* probes, const kp_trace* trace);
+
 /* Model.all_scores (model.py:19; transe.py:48-65, complex.py:88-112,
  * conve.py:133-158) for n (head, relation) pairs over the frozen entities:
  * out[n][n_ent].  The RelevanceEngine.select_entities_to_convert sweep

@@ -29,7 +29,8 @@ EXPORTS = ["kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_posttrain_ran
            "kp_sched_batch_create", "kp_sched_batch_destroy", "kp_sched_add_calls", "kp_sched_pack",
            "kp_gather_i32", "kp_rng_transe_calls_async", "kp_rng_torch_take", "kp_conve_train_begin",
            "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free", "kp_ctx_set_inflight",
-           "kp_last_attn_plan", "kp_posttrain_rank_topk", "kp_posttrain_rank_probes"]
+           "kp_last_attn_plan", "kp_posttrain_rank_topk", "kp_posttrain_rank_probes", "kp_trace_steps",
+           "kp_posttrain_rank_trace"]
 
 
 class ModelDesc(C.Structure):
@@ -61,6 +62,10 @@ class Probes(C.Structure):
                 ("filt", C.c_void_p), ("out_score", C.c_void_p), ("out_rank", C.c_void_p)]
 
 
+class Trace(C.Structure):
+    _fields_ = [("trace_off", C.c_void_p), ("out_loss", C.c_void_p)]
+
+
 class KelpieHipError(RuntimeError):
     pass
 
@@ -87,6 +92,10 @@ def lib():
         if hasattr(L, "kp_posttrain_rank_probes"):  # KELPIE_HIP_LIB may name a build from before the probes
             L.kp_posttrain_rank_probes.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
                                                    C.c_void_p, C.POINTER(Probes)]
+        if hasattr(L, "kp_posttrain_rank_trace"):  # KELPIE_HIP_LIB may name a build from before the trace
+            L.kp_posttrain_rank_trace.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.POINTER(Probes), C.POINTER(Trace)]
+            L.kp_trace_steps.argtypes = [C.c_int32, C.POINTER(HP), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kp_all_scores.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kp_convertible.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
@@ -182,6 +191,19 @@ def check(rc, ctx=None):
     if rc != 0:
         msg = lib().kp_last_error(ctx).decode(errors="replace")
         raise KelpieHipError(f"libkelpie_hip error {rc}: {msg}")
+
+
+def trace_steps(model_name: str, hp: HP, row_off, rows) -> np.ndarray:
+    """kp_trace_steps: the optimizer steps (step_on_batch calls) of every slot's post-training,
+    int32 [n_slots]: epochs * ceil(R / batch_size) over the slot's rows, ConvE over its
+    distinct (head, relation) pairs.  Host work only: no context, no device."""
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1, 3))
+    n = len(row_off) - 1
+    out = np.zeros(max(1, n), np.int32)
+    check(lib().kp_trace_steps(KP_MODEL[model_name], C.byref(hp), n, _ptr(row_off),
+                               _ptr(rows) if len(rows) else None, _ptr(out)))
+    return out[:n]
 
 
 def mt19937_discard(state: np.ndarray, n: int):
@@ -365,6 +387,7 @@ class Context:
         if rc != 0:
             raise KelpieHipError(f"kp_ctx_create failed ({rc}): {L.kp_last_error(None).decode()}")
         self.h = h
+        self.model_name = model_name
         self.n_ent, self.dim = E.shape
         self._keep = []  # tables are copied to the device
 
@@ -380,12 +403,15 @@ class Context:
             pass
 
     def posttrain_rank(self, hp: HP, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False, topk=0,
-                       probes=None):
+                       probes=None, trace=False):
         """kp_posttrain_rank: (target scores, ranks, final rows or None).  With ``topk`` > 0
         (kp_posttrain_rank_topk) a fourth element: (ids int32 [n][topk], scores float32
         [n][topk]), the slots' best unmasked tails, -1 / 0 past the last one.  With ``probes``
         = (probe_off [n+1], probes [m][2] = (p, o), filt_off [m+1], filt)
-        (kp_posttrain_rank_probes) a last element: (scores float32 [m], ranks int64 [m])."""
+        (kp_posttrain_rank_probes) a further element: (scores float32 [m], ranks int64 [m]).
+        With ``trace`` (kp_posttrain_rank_trace) a last element: the slots' loss arrays, one
+        float32 array per slot with the loss of every optimizer step (sized by
+        kp_trace_steps)."""
         topk = int(topk)
         if not 0 <= topk <= 32:
             raise ValueError(f"topk must be in [0, 32], got {topk}")
@@ -403,15 +429,25 @@ class Context:
         out_r = np.zeros(n, np.int64)
         b = Batch(n, _ptr(x0), _ptr(row_off), _ptr(rows), _ptr(rng_off), _ptr(rng), _ptr(pred), _ptr(filt_off),
                   _ptr(filt), _ptr(out_x), _ptr(out_s), _ptr(out_r))
-        if topk == 0 and probes is None:
+        if topk == 0 and probes is None and not trace:
             check(lib().kp_posttrain_rank(self.h, C.byref(hp), C.byref(b)), self.h)
             return out_s, out_r, out_x
         ids = np.full((n, topk), -1, np.int32) if topk else None
         top = np.zeros((n, topk), np.float32) if topk else None
         ret = (out_s, out_r, out_x) + (((ids, top),) if topk else ())
-        if probes is None:
+        if probes is None and not trace:
             check(lib().kp_posttrain_rank_topk(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top)), self.h)
             return ret
+        if trace:
+            t_off = np.zeros(n + 1, np.int32)
+            np.cumsum(trace_steps(self.model_name, hp, row_off, rows), out=t_off[1:])
+            loss = np.zeros(max(1, int(t_off[-1])), np.float32)
+            tr = Trace(_ptr(t_off), _ptr(loss))
+            losses = [loss[t_off[i]:t_off[i + 1]] for i in range(n)]
+        if probes is None:
+            check(lib().kp_posttrain_rank_trace(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top), None,
+                                                C.byref(tr)), self.h)
+            return ret + (losses,)
         p_off, p_tr, pf_off, pf = probes
         p_off = np.ascontiguousarray(p_off, dtype=np.int32)
         p_tr = np.ascontiguousarray(np.asarray(p_tr, dtype=np.int32).reshape(-1, 2))
@@ -423,6 +459,10 @@ class Context:
         p_s = np.zeros(m, np.float32)
         p_r = np.zeros(m, np.int64)
         pr = Probes(m, _ptr(p_off), _ptr(p_tr), _ptr(pf_off), _ptr(pf), _ptr(p_s), _ptr(p_r))
+        if trace:
+            check(lib().kp_posttrain_rank_trace(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top),
+                                                C.byref(pr), C.byref(tr)), self.h)
+            return ret + ((p_s, p_r), losses)
         check(lib().kp_posttrain_rank_probes(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top),
                                              C.byref(pr)), self.h)
         return ret + ((p_s, p_r),)

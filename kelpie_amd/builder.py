@@ -51,6 +51,12 @@ the first ``cap``), and each record gains ``"side_effects"``, aligned with
 [labelled triple, base rank, post rank] per probe (the sufficient engine: one such record
 per conversion entity, with its label).  A base result cached without probes gives None
 for the base figures.
+
+With ``trace`` = True every post-training also reports the optimizer's loss of each of its
+steps (``engine.trace``), and each record gains ``"traces"``, aligned with
+``rule_to_relevance``: per rule ``{"base", "post"}``, each the list of losses in step order
+(the sufficient engine: one such record per conversion entity, with its label).  A base
+result cached without a trace gives None.
 """
 from __future__ import annotations
 
@@ -63,7 +69,7 @@ class StochasticBuilder:
     AUTO_MIN, AUTO_MAX = 4, 32
 
     def __init__(self, xsi, engine, summarization: str = None, max_explanation_length: int = 4, window=32,
-                 pipelined=False, top_k=0, side_effects=0):
+                 pipelined=False, top_k=0, side_effects=0, trace=False):
         if summarization is not None:
             raise NotImplementedError("summarisation (simulation / bisimulation) is out of scope")
         self.xsi = xsi
@@ -81,6 +87,9 @@ class StochasticBuilder:
         self.side_effects = int(side_effects)
         if self.side_effects:
             engine.side_effects = self.side_effects  # validates the range
+        self.trace = bool(trace)
+        if self.trace:
+            engine.trace = True
         self._details = {}  # rule -> the engine's (post-trained, base) results of its evaluation
         self.stats = {"batches": 0, "evaluated": 0, "wasted": 0, "batch_s": 0.0, "schedule_s": 0.0, "pack_s": 0.0,
                       "lib_s": 0.0}
@@ -122,11 +131,13 @@ class StochasticBuilder:
             out["counterfactuals"] = [self._counterfactual(pred, self._details[rule]) for rule, _ in rule_to_rel]
         if self.side_effects:
             out["side_effects"] = [self._side_effect(self._details[rule]) for rule, _ in rule_to_rel]
+        if self.trace:
+            out["traces"] = [self._trace_of(self._details[rule]) for rule, _ in rule_to_rel]
         return out
 
     def _keep_details(self, rules, n):
         """The engine's per-rule results of its last batch, for the first ``n`` of ``rules``."""
-        if self.top_k or self.side_effects:
+        if self.top_k or self.side_effects or self.trace:
             for rule, det in zip(rules[:n], self.engine.last_results):
                 self._details[tuple(rule)] = det
 
@@ -145,6 +156,14 @@ class StochasticBuilder:
             return {"base": self._labelled(base, s), "post": self._labelled(pt, s)}
         # sufficient: one pair per conversion entity
         return [{"entity": self.dataset.id_to_entity[e], "base": self._labelled(base, e), "post": self._labelled(pt, e)}
+                for e, (pt, base) in zip(self.engine.entities_to_convert, det)]
+
+    def _trace_of(self, det):
+        if isinstance(det, tuple):  # necessary: (post-trained, base) of the prediction's subject
+            pt, base = det
+            return {"base": base.get("loss"), "post": pt.get("loss")}
+        # sufficient: one pair per conversion entity
+        return [{"entity": self.dataset.id_to_entity[e], "base": base.get("loss"), "post": pt.get("loss")}
                 for e, (pt, base) in zip(self.engine.entities_to_convert, det)]
 
     @staticmethod

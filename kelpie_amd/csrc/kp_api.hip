@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "kp_common.hpp"
+#include "kp_trace_check.hpp"
 
 int cx_pick_db(int dim);
 
@@ -212,6 +213,11 @@ static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, co
     if (b->n_slots == 0) {
       KP_REQUIRE(tk.k >= 0 && tk.k <= 32, "kp_posttrain_rank_topk: k must be in [0, 32]");
       KP_REQUIRE(tk.n_probes() == 0, "kp_posttrain_rank_probes: probes without a slot");
+      if (tk.trace) {  // the same rule and message as with slots (kp_trace_check.hpp handles n_slots == 0)
+        static const char* const names[] = {"TransE", "ComplEx", "ConvE", "DistMult"};
+        if (const char* why = kp_check_trace(c->model, hp, 0, b->row_off, b->rows, tk.trace))
+          throw KpError{KP_EINVAL, std::string(names[c->model]) + ": trace: " + why};
+      }
       return;
     }
     KP_REQUIRE(b->x0 && b->row_off && b->pred && b->filt_off && b->out_score && b->out_rank,
@@ -247,6 +253,29 @@ int kp_posttrain_rank_probes(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int3
   tk.scores = out_scores;
   tk.probes = probes;
   return posttrain_rank_call(c, hp, b, tk);
+}
+
+// kp_posttrain_rank_probes with the optimizer's loss of every step of every slot
+// (step_on_batch's return: multiclass_nll_optimizer.py:147-164,
+// pairwise_ranking_optimizer.py:165-203, bce_optimizer.py:167-208)
+int kp_posttrain_rank_trace(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k, int32_t* out_ids,
+                            float* out_scores, const kp_probes* probes, const kp_trace* trace) {
+  TopkOut tk;
+  tk.k = k;
+  tk.ids = out_ids;
+  tk.scores = out_scores;
+  tk.probes = probes;
+  tk.trace = trace;
+  return posttrain_rank_call(c, hp, b, tk);
+}
+
+// the steps of every slot (kp_trace_check.hpp): host work only
+int kp_trace_steps(int32_t model, const kp_hp* hp, int32_t n_slots, const int32_t* row_off, const int32_t* rows,
+                   int32_t* out_steps) {
+  return guarded(nullptr, [&] {
+    if (const char* why = kp_trace_steps_host(model, hp, n_slots, row_off, rows, out_steps))
+      throw KpError{KP_EINVAL, std::string("kp_trace_steps: ") + why};
+  });
 }
 
 int kp_all_scores(kp_ctx* c, int32_t n, const int32_t* heads, const int32_t* rels, float* out) {

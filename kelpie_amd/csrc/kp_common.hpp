@@ -157,9 +157,14 @@ struct ComplexWs {
   DevBuf am, al, ao;               // attention split results (max, sum, output)
   DevBuf qs;                       // the step's queries [nq][dp]
   DevBuf score_q, score_out;       // complex_scores_dev's queries, complex_all_scores' scores
+  // kp_posttrain_rank_trace: the step's fp64 loss term per item [items], the frozen rows'
+  // regulariser factors [n_ent] / [n_rel2] (fp64, once per batch), the trace offsets
+  // [ns + 1] and the losses [steps]
+  DevBuf tr_term, tr_fe, tr_fr, tr_off, tr_loss;
   auto all() {
     return std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
-                      &tsum, &qpair, &lsef, &am, &al, &ao, &qs, &score_q, &score_out};
+                      &tsum, &qpair, &lsef, &am, &al, &ao, &qs, &score_q, &score_out, &tr_term, &tr_fe, &tr_fr,
+                      &tr_off, &tr_loss};
   }
 };
 KP_WS_COMPLETE(ComplexWs);
@@ -170,7 +175,8 @@ struct TranseWs {
   DevBuf slots, rows, rng;  // TeSlot, the batch's training rows and draws
   DevBuf order;             // slots, longest first
   DevBuf heads, rels;       // score queries: the ranked triples' (-1, relation), and transe_all_scores' pairs
-  auto all() { return std::array{&x, &slots, &rows, &rng, &order, &heads, &rels}; }
+  DevBuf tr_off, tr_loss;   // kp_posttrain_rank_trace: the trace offsets [ns + 1] and the losses [steps]
+  auto all() { return std::array{&x, &slots, &rows, &rng, &order, &heads, &rels, &tr_off, &tr_loss}; }
 };
 KP_WS_COMPLETE(TranseWs);
 
@@ -198,11 +204,14 @@ struct ConveWs {
   DevBuf dfc, gk, dflat, dl;      // backward: dL/dfc, g . x, dL/dflat (unfused), lhs image gradient
   DevBuf rank_src;                // the ranked triples' encoder sources
   DevBuf probe_src, probe_q;      // a chunk of probes' encoder sources (-slot - 1, p) and outputs [chunk][dp]
+  // kp_posttrain_rank_trace: the trace offsets [ns + 1] and losses [steps]; a step's rows
+  // [rows][dp], one chunk's logits [chunk][ld] and the rows' summed BCE terms (fp64)
+  DevBuf tr_off, tr_loss, tr_rows, tr_scores, tr_rowloss;
   auto all() {
     return std::array{&x, &s1, &s2, &kinst, &finst, &acts, &tails, &keep_bits, &fcf, &fpairs, &flat, &slab,
                       &relu, &g3, &sr_src, &sr_rng, &psr, &relu_s, &slab_l, &mid, &map_l, &map_m, &gs, &dls,
                       &q, &enc_src, &enc_bits, &fchunks, &fpart, &gscale, &o, &dfc, &gk, &dflat, &dl, &rank_src,
-                      &probe_src, &probe_q};
+                      &probe_src, &probe_q, &tr_off, &tr_loss, &tr_rows, &tr_scores, &tr_rowloss};
   }
 };
 KP_WS_COMPLETE(ConveWs);
@@ -341,6 +350,8 @@ struct TopkOut {
   // kp_posttrain_rank_probes' request (nullptr or n == 0: no probes)
   const kp_probes* probes = nullptr;
   int n_probes() const { return probes ? probes->n : 0; }
+  // kp_posttrain_rank_trace's request (nullptr: no trace)
+  const kp_trace* trace = nullptr;
 };
 void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
 // kp_complex.hip, product policy

@@ -168,6 +168,16 @@ struct CxOpt {
 
 #define UPD_MAXSPLIT 16
 
+// kp_posttrain_rank_trace: the TRACE form of kp_cx_contrib also writes the item's fp64 share
+// of the step's summed negative log-likelihood (include/kelpie_hip.h, "Post-training
+// trace"); without the flag the argument is an empty struct and the kernel the one it was
+template <bool TRACE>
+struct CxTraceArgs {};
+template <>
+struct CxTraceArgs<true> {
+  double* term;  // [nq + nt]
+};
+
 // One wave per (query or frozen-head row) of this step: its contribution to the
 // kelpie row's gradient (un-normalised by the batch size).
 //   query (kelpie-head rows sharing relation r, count c, kelpie targets ck):
@@ -175,7 +185,10 @@ struct CxOpt {
 //     (frozen part sum_sp w_sp O_sp merged with the kelpie column p_k x)
 //   frozen-head row pair (count c, target = kelpie):  c (p_k - 1) q_pair
 // (`half` is the policy's extent w: d / 2 for ComplEx, d for DistMult)
-template <int DP, class Prod>
+// TRACE: item's loss term, from the fp64 values above:
+//   query:  c lse - q . Tsum - ck z  (the c rows' lse minus their targets' scores)
+//   frozen-head pair:  c (lse - z)
+template <int DP, class Prod, bool TRACE = false>
 __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __restrict__ stepq, int nq,
                                                      const int4* __restrict__ stept, int nt,
                                                      const CxQuery* __restrict__ pq, const float* __restrict__ X,
@@ -183,7 +196,7 @@ __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __res
                                                      const float* __restrict__ Qpair, const float* __restrict__ lsef,
                                                      const float* __restrict__ att_m, const float* __restrict__ att_l,
                                                      const float* __restrict__ att_O, int n_split,
-                                                     float* __restrict__ contrib) {
+                                                     float* __restrict__ contrib, CxTraceArgs<TRACE> tr) {
   const int lane = threadIdx.x & 63;
   const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= nq + nt) return;
@@ -262,6 +275,15 @@ __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __res
       }
       Prod::emit(out, i, half, xv, rv, dv, cf);
     }
+    if constexpr (TRACE) {
+      // q . Tsum on the step's fp32 query (the q of z and of the attention), summed in fp64:
+      // lane-strided, then a butterfly
+      double qt = 0.0;
+      for (int d = lane; d < Prod::G * half; d += 64) qt += (double)Prod::q(x, rel, d, half) * (double)ts[d];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) qt += __shfl_xor(qt, o, 64);
+      if (lane == 0) tr.term[item] = fc * lse - qt - fck * (double)z;
+    }
   } else {
     const int4 st = stept[item - nq];  // slot, pair, count
     const float* x = X + (size_t)st.x * DP;
@@ -274,6 +296,98 @@ __global__ __launch_bounds__(256) void kp_cx_contrib(int half, const int4* __res
     const double lse = hi + log1p(exp(lo - hi));
     const double coef = (double)st.z * (exp((double)z - lse) - 1.0);
     for (int d = lane; d < Prod::G * half; d += 64) out[d] = (float)(coef * (double)qp[d]);
+    if constexpr (TRACE) {
+      if (lane == 0) tr.term[item] = (double)st.z * (lse - (double)z);
+    }
+  }
+}
+
+// kp_posttrain_rank_trace: freg[r] = the regulariser's factor of row r of a frozen table
+// (E or R), once per batch: N3 sum_i |f_i|^3, N2 (sum_i |f_i|^2)^(3/2), |f_i| the policy's
+// modulus.  One wave per row, fp64, lane-strided then a butterfly (a fixed order).
+template <class Prod>
+__global__ __launch_bounds__(256) void kp_cx_rowreg(const float* __restrict__ T, int n, int dp, int half, int reg_n2,
+                                                    double* __restrict__ freg) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  const float* row = T + (size_t)r * dp;
+  double acc = 0.0;
+  for (int i = lane; i < half; i += 64) {
+    float xv[Prod::G];
+#pragma unroll
+    for (int h = 0; h < Prod::G; ++h) xv[h] = row[i + h * half];
+    const double f = Prod::mod64(xv);
+    acc += reg_n2 ? f * f : f * f * f;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) freg[r] = reg_n2 ? acc * sqrt(acc) : acc;
+}
+
+// kp_posttrain_rank_trace: one wave per active slot of the step, after kp_cx_contrib<TRACE>
+// and before kp_cx_update moves x.  Sums the slot's item terms (its queries, then its
+// frozen-head pairs; lane-strided in item order, then a butterfly: a fixed order), divides
+// by the batch size and adds the regulariser's value: the frozen rows' factors from freg_e /
+// freg_r, the kelpie row's (cnt_l + cnt_r occurrences) from x as it is before the update.
+// One fp32 rounding, at the store of step `step` of the slot.
+template <int DP, class Prod>
+__global__ __launch_bounds__(64) void kp_cx_trace_sum(int half, const int4* __restrict__ act,
+                                                      const CxPlan* __restrict__ plans,
+                                                      const CxQuery* __restrict__ pq,
+                                                      const int32_t* __restrict__ targets,
+                                                      const int2* __restrict__ pairs, const int4* __restrict__ stept,
+                                                      int nq, const float* __restrict__ X,
+                                                      const double* __restrict__ term,
+                                                      const double* __restrict__ freg_e,
+                                                      const double* __restrict__ freg_r, float reg_w, int reg_n2,
+                                                      const int32_t* __restrict__ trace_off, int step,
+                                                      float* __restrict__ loss) {
+  const int lane = threadIdx.x;
+  const int4 a4 = act[blockIdx.x];  // slot, plan, qoff, toff
+  const CxPlan P = plans[a4.y];
+  const bool reg = reg_w != 0.f;
+  double nll = 0.0, fz = 0.0;
+  for (int j = lane; j < P.q_count; j += 64) {
+    nll += term[a4.z + j];
+    if (reg) {
+      const CxQuery Q = pq[P.q_begin + j];
+      fz += (double)Q.c * freg_r[Q.rel];
+      for (int i = 0; i < Q.tg_count; ++i) fz += freg_e[targets[Q.tg_begin + i]];
+    }
+  }
+  for (int j = lane; j < P.t_count; j += 64) {
+    nll += term[nq + a4.w + j];
+    if (reg) {
+      const int4 st = stept[a4.w + j];  // slot, pair, count
+      const int2 hr = pairs[st.y];
+      fz += (double)st.z * (freg_e[hr.x] + freg_r[hr.y]);
+    }
+  }
+  double fx = 0.0;
+  if (reg) {
+    const float* x = X + (size_t)a4.x * DP;
+    for (int i = lane; i < half; i += 64) {
+      float xv[Prod::G];
+#pragma unroll
+      for (int h = 0; h < Prod::G; ++h) xv[h] = x[i + h * half];
+      const double f = Prod::mod64(xv);
+      fx += reg_n2 ? f * f : f * f * f;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    nll += __shfl_xor(nll, o, 64);
+    fz += __shfl_xor(fz, o, 64);
+    fx += __shfl_xor(fx, o, 64);
+  }
+  if (lane == 0) {
+    double l = nll / (double)P.b;
+    if (reg) {
+      if (reg_n2) fx = fx * sqrt(fx);
+      l += (double)reg_w * (fz + (double)(P.cnt_l + P.cnt_r) * fx) / (double)P.b;
+    }
+    loss[trace_off[a4.x] + step] = (float)l;
   }
 }
 
@@ -550,17 +664,39 @@ void launch_attn(kp_ctx* c, bool with_o, const float* Q, int nq, const AttnPlan&
   KP_HIP(hipGetLastError());
 }
 
+// kp_posttrain_rank_trace's device side (loss == nullptr: no trace)
+struct CxTraceDev {
+  double *term = nullptr, *freg_e = nullptr, *freg_r = nullptr;
+  const int32_t* targets = nullptr;
+  const int2* pairs = nullptr;
+  int32_t* off = nullptr;  // [ns + 1]
+  float* loss = nullptr;   // [total]
+  int total = 0;
+};
+
 template <int DB, class Prod>
 void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, const CxQuery* pq,
                    const int4* stepq, int nq, const int4* stept, int nt, const float* tsum, const float* qpair,
                    const float* lsef, const float* am, const float* al, const float* aO, int n_split, float* contrib,
-                   float* X, float* S1, float* S2, const CxOpt& opt) {
+                   float* X, float* S1, float* S2, const CxOpt& opt, const CxTraceDev& tr = {}, int step = 0) {
   if (n_act <= 0) return;
   const int half = Prod::extent(c->dim);
   KP_REQUIRE(n_split >= 1 && n_split <= 64, "cx contrib: one attention split per lane");
-  if (nq + nt > 0) {
+  if (nq + nt > 0 && !tr.loss) {
     hipLaunchKernelGGL((kp_cx_contrib<16 * DB, Prod>), dim3((nq + nt + 3) / 4), dim3(256), 0, c->stream, half, stepq, nq,
-                       stept, nt, pq, X, c->dR, tsum, qpair, lsef, am, al, aO, n_split, contrib);
+                       stept, nt, pq, X, c->dR, tsum, qpair, lsef, am, al, aO, n_split, contrib, CxTraceArgs<false>{});
+    KP_HIP(hipGetLastError());
+  }
+  if (tr.loss) {  // kp_posttrain_rank_trace: the items' loss terms, then the slots' losses, before x moves
+    if (nq + nt > 0) {
+      hipLaunchKernelGGL((kp_cx_contrib<16 * DB, Prod, true>), dim3((nq + nt + 3) / 4), dim3(256), 0, c->stream, half,
+                         stepq, nq, stept, nt, pq, X, c->dR, tsum, qpair, lsef, am, al, aO, n_split, contrib,
+                         CxTraceArgs<true>{tr.term});
+      KP_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL((kp_cx_trace_sum<16 * DB, Prod>), dim3(n_act), dim3(64), 0, c->stream, half, act, plans, pq,
+                       tr.targets, tr.pairs, stept, nq, X, tr.term, tr.freg_e, tr.freg_r, opt.reg_w, opt.reg_n2,
+                       tr.off, step, tr.loss);
     KP_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq, contrib, X,
@@ -616,6 +752,7 @@ struct CxDev {
   int32_t* pred;
   RankDev rk;
   ProbeDev probes;
+  CxTraceDev trace;
   // the attention's: sized and planned by cx_preloop
   float *am = nullptr, *al = nullptr, *ao = nullptr, *qs = nullptr;
   std::vector<AttnPlan> step_plan;  // [T]
@@ -656,18 +793,38 @@ CxDev cx_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, const CxSt
   d.pred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
   d.rk = upload_rank_inputs(c, bt, tk);
   d.probes = upload_probes(c, bt, tk);
+  if (tk.trace) {  // the trace's offsets and workspaces, with the call's other uploads
+    CxTraceDev& t = d.trace;
+    t.total = tk.trace->trace_off[ns];
+    t.off = upload(c, c->cx.tr_off, tk.trace->trace_off, (size_t)ns + 1);
+    t.loss = reinterpret_cast<float*>(c->cx.tr_loss.ensure(sizeof(float) * (size_t)std::max(1, t.total)));
+    t.term = reinterpret_cast<double*>(c->cx.tr_term.ensure(sizeof(double) * (size_t)std::max(1, sp.max_items)));
+    t.freg_e = reinterpret_cast<double*>(c->cx.tr_fe.ensure(sizeof(double) * (size_t)c->n_ent));
+    t.freg_r = reinterpret_cast<double*>(c->cx.tr_fr.ensure(sizeof(double) * (size_t)c->n_rel2));
+    t.targets = d.tg;
+    t.pairs = d.pairs;
+  }
   return d;
 }
 
 // before the loop: the queries' frozen-target sums, the attention plans and workspaces of
 // every step, and the frozen-head pairs' q and frozen log-sum-exp
 template <class Prod>
-void cx_preloop(kp_ctx* c, const CxStepPlan& sp, CxDev& d) {
+void cx_preloop(kp_ctx* c, const CxStepPlan& sp, CxDev& d, float reg_w, int reg_n2) {
   const int DP = c->dp, DBV = DP / 16;
   const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
   KP_HIP(hipEventRecord(c->ev0, c->stream));
   if (npq > 0) {
     hipLaunchKernelGGL(kp_cx_tsum, dim3(npq), dim3(128), 0, c->stream, c->dE, DP, d.pq, npq, d.tg, d.tsum);
+    KP_HIP(hipGetLastError());
+  }
+  if (d.trace.loss && reg_w != 0.f && sp.T > 0) {  // the frozen rows' regulariser factors, once per batch
+    const int half = Prod::extent(c->dim);
+    hipLaunchKernelGGL(kp_cx_rowreg<Prod>, dim3((c->n_ent + 3) / 4), dim3(256), 0, c->stream, c->dE, c->n_ent, DP, half,
+                       reg_n2, d.trace.freg_e);
+    KP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kp_cx_rowreg<Prod>, dim3((c->n_rel2 + 3) / 4), dim3(256), 0, c->stream, c->dR, c->n_rel2, DP,
+                       half, reg_n2, d.trace.freg_r);
     KP_HIP(hipGetLastError());
   }
   int slots_attn = 0;
@@ -732,7 +889,8 @@ int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxD
     opt.bc2_sqrt = as.bc2_sqrt;
     CX_DISPATCH(DBV, launch_update<DB, Prod>(c, na, d.acts + sp.act_off[t], d.plans, d.pq, d.stepq + sp.q_off[t], nq,
                                              d.stept + sp.t_off[t], sp.t_off[t + 1] - sp.t_off[t], d.tsum, d.qpair,
-                                             d.lsef, d.am, d.al, d.ao, sp_n, d.contrib, d.X, d.S1, d.S2, opt));
+                                             d.lsef, d.am, d.al, d.ao, sp_n, d.contrib, d.X, d.S1, d.S2, opt,
+                                             d.trace, t));
     if (g_host_times) {
       if (t == 0) t_steps[0] = host_ms();
       if (t == 1) t_steps[1] = host_ms();
@@ -759,6 +917,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   require_batch(c, bt, Prod::name);
   require_topk(tk, true, Prod::name);
   require_probes(c, bt, tk, true, Prod::name);
+  require_trace(c, hp, bt, tk, Prod::name);
   const CxOpt opt = make_opt(hp, who);
 
   CxStepPlan sp;
@@ -768,7 +927,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
 
   std::vector<float> xp;
   CxDev d = cx_workspaces(c, bt, tk, sp, xp);
-  cx_preloop<Prod>(c, sp, d);
+  cx_preloop<Prod>(c, sp, d, opt.reg_w, opt.reg_n2);
 
   // loop-interval events, destroyed on every exit path (a KP_HIP / KP_REQUIRE below throws)
   struct LoopEvents {
@@ -796,6 +955,9 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   });
   KP_HIP(hipEventRecord(c->ev1, c->stream));
 
+  if (d.trace.total > 0)  // with the other downloads, ahead of download_results' one wait
+    KP_HIP(hipMemcpyAsync(tk.trace->out_loss, d.trace.loss, sizeof(float) * (size_t)d.trace.total,
+                          hipMemcpyDeviceToHost, c->stream));
   const double t_enq = download_results(c, bt, d.X, d.rk, xp, tk, d.probes);
   const double t_done = g_host_times ? host_ms() : 0.0;
   if (g_host_times)

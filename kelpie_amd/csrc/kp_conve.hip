@@ -599,6 +599,115 @@ __global__ void kp_cv_kcol(int n, CvConst k, const float* __restrict__ Q, const 
   if (threadIdx.x == 0) scores[(size_t)s * ld + k.n_ent] = 1.0f / (1.0f + expf(-z));
 }
 
+// ---- kp_posttrain_rank_trace (include/kelpie_hip.h, "Post-training trace") ----------------
+// The step loop evaluates no loss: the attention forms G(s_e), and the frozen-head pairs never
+// meet the frozen entities.  So the trace scores every row of a step -- the kelpie pairs and
+// the frozen-head pairs, encoded with the step's masks as the step encodes them -- against all
+// n_ent + 1 columns (one fp32 MFMA pass over E per chunk of rows, kp_gemm_abt) and reduces
+// the BCE terms in fp64.
+
+// the step's rows [nk + nf][dp]: the kelpie pairs' encoder outputs (copied from Q), then the
+// frozen-head pairs' rows from their batch-wide FC rows with this step's hidden mask, as
+// kp_cv_fgrad forms them (with an input or feature-map dropout Q holds them all already)
+__global__ void kp_cv_trace_rows(int nk, int nf, CvConst k, const float* __restrict__ Q,
+                                 const CvFInst* __restrict__ fi, const float* __restrict__ fcf,
+                                 const int32_t* __restrict__ bits, const float* __restrict__ bna,
+                                 const float* __restrict__ bnb, float* __restrict__ TQ) {
+  const int i = blockIdx.x;
+  if (i >= nk + nf) return;
+  float* out = TQ + (size_t)i * k.dp;
+  if (i < nk) {
+    for (int d = threadIdx.x; d < k.dp; d += blockDim.x) out[d] = Q[(size_t)i * k.dp + d];
+    return;
+  }
+  const CvFInst F = fi[i - nk];
+  const float* a3 = bna + 33;
+  const float* b3 = bnb + 33;
+  for (int d = threadIdx.x; d < k.dp; d += blockDim.x) {
+    float v = 0.f;
+    if (d < k.dim) {
+      const float fc = fcf[(size_t)F.fp * k.dim + d];
+      const float nz = k.has_mask ? noise_at(bits, F.mb.hid, d, k.scale) : 1.0f;
+      const float dr = k.has_mask ? fc * nz : fc;
+      v = fmaxf(dr * a3[d] + b3[d], 0.f);
+    }
+    out[d] = v;
+  }
+}
+
+// one BCELoss term on the logit s with target y, in fp64: -(y log p + (1 - y) log(1 - p)),
+// p = sigmoid(s), each log clamped at -100 as torch clamps it
+__device__ __forceinline__ double cv_bce_term(double s, double y) {
+  const double lp = fmin(s, 0.0) - log1p(exp(-fabs(s)));  // log sigmoid(s); log(1 - sigmoid(s)) = lp - s
+  return -(y * fmax(lp, -100.0) + (1.0 - y) * fmax(lp - s, -100.0));
+}
+
+// the summed BCE terms of one row over all n_ent + 1 columns; one workgroup per row of the
+// chunk [r0, r0 + gridDim.x).  Every frozen column first counts with the smoothed zero target,
+// thread-strided partials, a butterfly per wave and the four wave sums in wave order (a fixed
+// order); then the kelpie column (its logit the row's fp64 dot with the slot's x) and the
+// pair's own tails are put right
+__global__ __launch_bounds__(256) void kp_cv_trace_row(int r0, int nk, CvConst k, const float* __restrict__ S, int ld,
+                                                       const float* __restrict__ TQ, const CvInst* __restrict__ ki,
+                                                       const CvFInst* __restrict__ fi,
+                                                       const int32_t* __restrict__ tails,
+                                                       const float* __restrict__ X, double* __restrict__ rowloss) {
+  __shared__ double part[2][4];
+  const int row = r0 + blockIdx.x, tid = threadIdx.x;
+  const float* srow = S + (size_t)blockIdx.x * ld;
+  const bool kelpie = row < nk;
+  const int slot = kelpie ? ki[row].slot : fi[row - nk].slot;
+  const float* q = TQ + (size_t)row * k.dp;
+  const float* x = X + (size_t)slot * k.dp;
+  const double ylo = (double)k.ylo, yhi = (double)k.yhi;
+  double acc = 0.0, z = 0.0;
+  for (int e = tid; e < k.n_ent; e += 256) acc += cv_bce_term((double)srow[e], ylo);
+  for (int d = tid; d < k.dim; d += 256) z += (double)q[d] * (double)x[d];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    acc += __shfl_xor(acc, o, 64);
+    z += __shfl_xor(z, o, 64);
+  }
+  if ((tid & 63) == 0) {
+    part[0][tid >> 6] = acc;
+    part[1][tid >> 6] = z;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double total = ((part[0][0] + part[0][1]) + part[0][2]) + part[0][3];
+  const double zk = ((part[1][0] + part[1][1]) + part[1][2]) + part[1][3];
+  bool k_is_tail = !kelpie;  // a frozen-head pair's only tail is the kelpie entity
+  if (kelpie) {
+    const CvInst I = ki[row];
+    for (int u = 0; u < I.tail_count; ++u) {
+      const int e = tails[I.tail_begin + u];
+      if (e == k.n_ent) {
+        k_is_tail = true;
+      } else {
+        const double st = (double)srow[e];
+        total += cv_bce_term(st, yhi) - cv_bce_term(st, ylo);
+      }
+    }
+  }
+  rowloss[row] = total + cv_bce_term(zk, k_is_tail ? yhi : ylo);
+}
+
+// one thread per active slot: its rows' sums in row order (kelpie pairs, then frozen-head
+// pairs), the mean over b x (n_ent + 1), one fp32 rounding at the store of step `step`
+__global__ void kp_cv_trace_slot(int na, int nk, CvConst k, const CvAct* __restrict__ act,
+                                 const CvInst* __restrict__ ki, const CvFInst* __restrict__ fi,
+                                 const double* __restrict__ rowloss, const int32_t* __restrict__ trace_off, int step,
+                                 float* __restrict__ loss) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= na) return;
+  const CvAct A = act[a];
+  double sum = 0.0;
+  for (int j = 0; j < A.k_count; ++j) sum += rowloss[A.k_begin + j];
+  for (int j = 0; j < A.f_count; ++j) sum += rowloss[nk + A.f_begin + j];
+  const int b = A.k_count > 0 ? ki[A.k_begin].b : fi[A.f_begin].b;
+  loss[trace_off[A.slot] + step] = (float)(sum / ((double)b * (double)(k.n_ent + 1)));
+}
+
 CvConst make_const(kp_ctx* c, const kp_hp* hp) {
   CvConst k{};
   k.n_ent = c->n_ent;
@@ -1062,8 +1171,65 @@ void cv_update(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, const CvDev& 
   KP_HIP(hipGetLastError());
 }
 
+// kp_posttrain_rank_trace's device side (loss == nullptr: no trace): the trace offsets and
+// losses, the step's rows, one chunk's logits [chunk][ld] and the rows' summed terms
+constexpr size_t TRACE_WS_BYTES = (size_t)64 << 20;  // a chunk's logits, as TOPK_WS_BYTES
+struct CvTraceDev {
+  int32_t* off = nullptr;
+  float* loss = nullptr;
+  float *rows = nullptr, *scores = nullptr;
+  double* rowloss = nullptr;
+  int total = 0, chunk = 0, ld = 0;
+};
+
+CvTraceDev cv_trace_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, const CvStepPlan& sp) {
+  CvTraceDev t;
+  if (!tk.trace) return t;
+  const int ns = bt->n_slots;
+  int max_rows = 1;
+  for (int s = 0; s < sp.T; ++s)
+    max_rows = std::max(max_rows, (sp.kin_off[s + 1] - sp.kin_off[s]) + (sp.fin_off[s + 1] - sp.fin_off[s]));
+  t.total = tk.trace->trace_off[ns];
+  t.ld = round_up(c->n_ent, 4);
+  t.chunk = (int)std::min<size_t>((size_t)max_rows, std::max<size_t>(1, TRACE_WS_BYTES / (sizeof(float) * t.ld)));
+  if (const char* e = std::getenv("KP_TRACE_CHUNK"))  // diagnostic: n rows per chunk, as KP_PROBE_CHUNK
+    t.chunk = std::min(max_rows, std::max(1, std::atoi(e)));
+  t.off = upload(c, c->cv.tr_off, tk.trace->trace_off, (size_t)ns + 1);
+  t.loss = ensure_n<float>(c->cv.tr_loss, (size_t)std::max(1, t.total));
+  t.rows = ensure_n<float>(c->cv.tr_rows, (size_t)max_rows * c->dp);
+  t.scores = ensure_n<float>(c->cv.tr_scores, (size_t)t.chunk * t.ld);
+  t.rowloss = ensure_n<double>(c->cv.tr_rowloss, (size_t)max_rows);
+  return t;
+}
+
+// the losses of step t's active slots, after the forward and before the update moves x
+void cv_trace_step(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, const CvDev& d, const CvStep& st,
+                   const CvTraceDev& tr) {
+  if (!tr.loss || st.na <= 0) return;
+  const int t = st.t, nk = st.nk, nf = sp.fin_off[t + 1] - sp.fin_off[t], n = nk + nf;
+  const CvFInst* FI = d.FI + sp.fin_off[t];
+  const float* TQ = d.Q;  // fr_step: the step's encoder rows, kelpie pairs first
+  if (!kc.fr_step) {
+    hipLaunchKernelGGL(kp_cv_trace_rows, dim3(n), dim3(256), 0, c->stream, nk, nf, kc, d.Q, FI, d.fcf, d.bits, c->d_bn_a,
+                       c->d_bn_b, tr.rows);
+    KP_HIP(hipGetLastError());
+    TQ = tr.rows;
+  }
+  for (int r0 = 0; r0 < n; r0 += tr.chunk) {  // E streams once per chunk of rows, not once per row
+    const int m = std::min(tr.chunk, n - r0);
+    launch_gemm_abt(c, TQ + (size_t)r0 * c->dp, c->dp, m, c->dE, c->dp, c->n_ent, c->dp, tr.scores, tr.ld, nullptr, 0, 1);
+    hipLaunchKernelGGL(kp_cv_trace_row, dim3(m), dim3(256), 0, c->stream, r0, nk, kc, tr.scores, tr.ld, TQ, st.KI, FI,
+                       d.tails, d.X, tr.rowloss);
+    KP_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(kp_cv_trace_slot, dim3((st.na + 63) / 64), dim3(64), 0, c->stream, st.na, nk, kc,
+                     d.act + sp.act_off[t], st.KI, FI, tr.rowloss, tr.off, t, tr.loss);
+  KP_HIP(hipGetLastError());
+}
+
 // the epoch/step loop; returns the hot (attention) launches
-int64_t cv_step_loop(kp_ctx* c, const kp_hp* hp, const CvConst& kc, const CvStepPlan& sp, const CvDev& d) {
+int64_t cv_step_loop(kp_ctx* c, const kp_hp* hp, const CvConst& kc, const CvStepPlan& sp, const CvDev& d,
+                     const CvTraceDev& tr) {
   CvOpt opt{};
   opt.lr = hp->lr;
   opt.b1 = hp->beta1;
@@ -1090,6 +1256,7 @@ int64_t cv_step_loop(kp_ctx* c, const kp_hp* hp, const CvConst& kc, const CvStep
     const AdamStep as = adam_step(hp, t);
     opt.step_size = as.step_size;
     opt.bc2_sqrt = as.bc2_sqrt;
+    cv_trace_step(c, kc, sp, d, st, tr);
     cv_update(c, kc, sp, d, st, opt);
   }
   return launches;
@@ -1156,6 +1323,7 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   require_topk(tk, c->cv_rank64 != 0, "ConvE");
   require_probes(c, bt, tk, c->cv_rank64 != 0, "ConvE");
   KP_REQUIRE(hp->batch_size >= 1 && hp->epochs >= 0, "ConvE: bad hyper-parameters");
+  require_trace(c, hp, bt, tk, "ConvE");
   const CvConst kc = make_const(c, hp);
 
   CvStepPlan sp;
@@ -1167,16 +1335,20 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   std::vector<float> xp;
   CvDev d = cv_workspaces(c, bt, sp, xp);
   const ProbeDev pd = cv_probe_workspaces(c, bt, tk);
+  const CvTraceDev tr = cv_trace_workspaces(c, bt, tk, sp);
   const double t_up = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipEventRecord(c->ev0, c->stream));
   const int nfp = cv_frozen_fc(c, kc, sp, d);
   cv_step_workspaces(c, kc, sp, nfp, d);
 
-  const int64_t launches = cv_step_loop(c, hp, kc, sp, d);
+  const int64_t launches = cv_step_loop(c, hp, kc, sp, d, tr);
   const double t_loop = g_host_times ? host_ms() : 0.0;
 
   const RankDev rk = cv_rank(c, kc, bt, tk, d, pd);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
+  if (tr.total > 0)  // with the other downloads, ahead of download_results' one wait
+    KP_HIP(hipMemcpyAsync(tk.trace->out_loss, tr.loss, sizeof(float) * (size_t)tr.total, hipMemcpyDeviceToHost,
+                          c->stream));
   download_results(c, bt, d.X, rk, xp, tk, pd);
   if (g_host_times)
     std::fprintf(stderr, "[kp_cv] slots %d steps %d pairs %zu: plan %.2f ms, uploads %.2f ms, loop enqueue %.2f ms, "

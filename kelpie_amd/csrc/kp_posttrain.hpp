@@ -14,6 +14,7 @@
 #include "kp_batch_check.hpp"
 #include "kp_common.hpp"
 #include "kp_probe_check.hpp"
+#include "kp_trace_check.hpp"
 
 // KP_HOST_TIMES=1 (diagnostic): ComplEx and ConvE print, per call on stderr, the host time
 // of their phases (planning, uploads, enqueueing the loop, waiting for the device)
@@ -47,6 +48,15 @@ inline void require_probes(const kp_ctx* c, const kp_batch* bt, const TopkOut& t
     throw KpError{KP_EINVAL, std::string(model) + ": probes: " + why};
   if (tk.probes->n > 0 && !rank64)
     throw KpError{KP_ENOTSUP, std::string(model) + ": probes need the fp64 rank (the fp32 rank switch is set)"};
+}
+
+// kp_posttrain_rank_trace's request (kp_trace_check.hpp), checked after the batch and the
+// probes and before the first upload.  The trace does not depend on the rank, so the fp32
+// rank switches are no reason to refuse it
+inline void require_trace(const kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk, const char* model) {
+  if (!tk.trace) return;
+  if (const char* why = kp_check_trace(c->model, hp, bt->n_slots, bt->row_off, bt->rows, tk.trace))
+    throw KpError{KP_EINVAL, std::string(model) + ": trace: " + why};
 }
 
 // Adam's per-step scalars at step t (0-based) of a call: lr / (1 - beta1^(t+1)) and

@@ -125,12 +125,38 @@ __device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlan
 // wave-uniform masks; forcing them into scalar branches was measured 1.9x slower.
 __device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
+// kp_posttrain_rank_trace: what a wave adds up over its items of one step for the step's loss
+// (include/kelpie_hip.h, "Post-training trace"): the pairs' hinge terms and the squared rows
+// of the positives' and negatives' three factors, both in fp64; sx = |x|^2 of the step.
+// Without the flag the struct is empty and te_item / kp_te_posttrain are what they were.
+template <bool TRACE>
+struct TeTraceAcc {};
+template <>
+struct TeTraceAcc<true> {
+  double hinge, sq;
+  float sx;
+};
+template <bool TRACE>
+struct TeTraceArgs {};
+template <>
+struct TeTraceArgs<true> {
+  const int32_t* off;  // [ns + 1]
+  float* loss;         // [off[ns]]
+};
+__device__ __forceinline__ float sq4(float4 v) { return fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, v.w * v.w))); }
+// the TRACE forms' per-wave partials [hinge | squares], summed by one thread in wave order
+template <int NW>
+__device__ __forceinline__ double* te_trace_lds() {
+  __shared__ double part[2 * NW];
+  return part;
+}
+
 // L1 (norm p = 1): f = sum |v| and d f / d v = sgn(v) with sgn(0) = 0 (torch's p = 1 norm
 // backward); the per-pair coefficient is then +-1 instead of +-1 / f
-template <int VPL, bool L1>
+template <int VPL, bool L1, bool TRACE = false>
 __device__ __forceinline__ void te_item(const int4* rec, const float* __restrict__ E, const float* __restrict__ Rt,
                                         const float4* x4, const int* fo, const bool* on, float margin, float4* g,
-                                        int& cnt) {
+                                        int& cnt, TeTraceAcc<TRACE>& acc) {
   const int4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
   const int a_off = rfl(r0.x), rel_off = rfl(r0.y), flags = rfl(r0.z);
   const int noff[TE_NB] = {rfl(r1.x), rfl(r1.y), rfl(r1.z), rfl(r1.w), rfl(r2.x)};
@@ -191,6 +217,7 @@ __device__ __forceinline__ void te_item(const int4* rec, const float* __restrict
   for (int q = 0; q < TE_NB; ++q) {
     const float fn = L1 ? wave_fold_u(sn[q]) : sqrtf(wave_fold_u(sn[q]));
     if (q >= nb) continue;
+    if constexpr (TRACE) acc.hinge += (double)fmaxf((fp - fn) + margin, 0.f);  // MarginRankingLoss, target -1
     const bool act = (fp - fn) + margin >= 0.f;  // clamp_min backward passes grad where self >= min
     n_act += act ? 1 : 0;
     const int sgn_n = ((sgnb >> (2 * q)) & 3) - 1;
@@ -218,6 +245,36 @@ __device__ __forceinline__ void te_item(const int4* rec, const float* __restrict
     }
   }
   cnt += rfl(r0.w);
+  if constexpr (TRACE) {
+    // the L2 regulariser's value (regularizers.py:15-22): every stepped pair counts the three
+    // rows of its positive and of its negative; a row's squares are a wave sum
+    float s_av = 0.f, s_b = 0.f, s_q[TE_NB];
+#pragma unroll
+    for (int u = 0; u < VPL; ++u) {
+      s_av += on[u] ? sq4(av[u]) : 0.f;
+      s_b += on[u] ? sq4(bb[u]) : 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < TE_NB; ++q) {
+      const bool ek = flags & (1 << (16 + q));
+      s_q[q] = 0.f;
+#pragma unroll
+      for (int u = 0; u < VPL; ++u) s_q[q] += on[u] ? sq4(bn[q][u]) : 0.f;
+      s_q[q] = wave_fold_u(row16_sum_f(s_q[q]));
+      if (ek) s_q[q] = acc.sx;
+    }
+    s_av = wave_fold_u(row16_sum_f(s_av));
+    s_b = wave_fold_u(row16_sum_f(s_b));
+    const double d_lp = hk ? acc.sx : s_av, d_rp = tk ? acc.sx : s_av, d_b = s_b;
+    double sq = (double)nb * (d_lp + d_b + d_rp);
+#pragma unroll
+    for (int q = 0; q < TE_NB; ++q) {
+      if (q >= nb) continue;
+      const bool ch = flags & (1 << (8 + q));
+      sq += d_b + (double)s_q[q] + (ch ? d_rp : d_lp);  // corrupted head keeps rhs, corrupted tail lhs
+    }
+    acc.sq += sq;
+  }
 }
 
 // One workgroup per slot (slots issued longest first) runs every epoch on chip: x in
@@ -241,14 +298,17 @@ __device__ __forceinline__ void te_item(const int4* rec, const float* __restrict
 // row-gather round per bundle, two barriers and the Adam step per epoch.  NT = 1024
 // threads per workgroup (1024: one per CU; 512 for diagnostics).
 // STAGED = false (slots too long for the LDS buffers) reads the descriptors from memory.
-template <int VPL, int NT, bool STAGED, bool L1>  // VPL float4 per lane: dp <= 256 * VPL
+// TRACE (kp_posttrain_rank_trace): every step also stores its loss before the update --
+// the waves' fp64 hinge and squared-row partials meet in LDS with the gradient partials and
+// one thread sums them in wave order, rounds once to fp32 and stores
+template <int VPL, int NT, bool STAGED, bool L1, bool TRACE = false>  // VPL float4 per lane: dp <= 256 * VPL
 __global__ __launch_bounds__(NT) void kp_te_posttrain(int n_ent, int dp, int d, const float* __restrict__ E,
                                                           const float* __restrict__ Rt,
                                                           const TeSlot* __restrict__ slots,
                                                           const int32_t* __restrict__ slot_of_block,
                                                           const int32_t* __restrict__ rows,
                                                           const int32_t* __restrict__ rng, TeHp hp,
-                                                          float* __restrict__ X) {
+                                                          float* __restrict__ X, TeTraceArgs<TRACE> tr) {
   constexpr int TE_NW = NT / 64;  // waves
   constexpr int PF = 4;           // prefetched draw words per thread (STAGED: 3 R <= PF * NT)
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -295,6 +355,8 @@ __global__ __launch_bounds__(NT) void kp_te_posttrain(int n_ent, int dp, int d, 
     fo[u] = 4 * (f < NF4 ? f : NF4 - 1);
   }
   double b1t = 1.0, b2t = 1.0;
+  TeTraceAcc<TRACE> acc;
+  int step_idx = 0;  // (TRACE) the slot's steps so far
   for (int e = 0; e < hp.epochs; ++e) {
     const int32_t* order = STAGED ? drw + (e & 1) * R3 : rngs + (long long)e * R3;
     const int32_t* ents = order + S.R;
@@ -324,6 +386,14 @@ __global__ __launch_bounds__(NT) void kp_te_posttrain(int n_ent, int dp, int d, 
       float4 x4[VPL];
 #pragma unroll
       for (int u = 0; u < VPL; ++u) x4[u] = ld4(xs + fo[u]);
+      if constexpr (TRACE) {
+        float sx = 0.f;
+#pragma unroll
+        for (int u = 0; u < VPL; ++u) sx += on[u] ? sq4(x4[u]) : 0.f;
+        acc.sx = wave_fold_u(row16_sum_f(sx));
+        acc.hinge = 0.0;
+        acc.sq = 0.0;
+      }
       for (int c0 = 0; c0 < n_items; c0 += TE_RCH) {
         const int nc = min(TE_RCH, n_items - c0);
         if (c0 > 0) __syncthreads();  // the previous chunk's records are consumed
@@ -334,7 +404,7 @@ __global__ __launch_bounds__(NT) void kp_te_posttrain(int n_ent, int dp, int d, 
 #ifdef KP_TE_STAMPS
           const long long c1 = __builtin_amdgcn_s_memtime();
 #endif
-          te_item<VPL, L1>(recs + 3 * k, E, Rt, x4, fo, on, hp.margin, g, cnt);
+          te_item<VPL, L1, TRACE>(recs + 3 * k, E, Rt, x4, fo, on, hp.margin, g, cnt, acc);
 #ifdef KP_TE_STAMPS
           asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
           st_comp += __builtin_amdgcn_s_memtime() - c1;
@@ -360,7 +430,27 @@ __global__ __launch_bounds__(NT) void kp_te_posttrain(int n_ent, int dp, int d, 
         if (f < NF4) *reinterpret_cast<float4*>(red + wave * dp + 4 * f) = g[u];
       }
       if (lane == 0) cnt_s[wave] = cnt;
+      if constexpr (TRACE) {
+        if (lane == 0) {
+          double* part = te_trace_lds<TE_NW>();
+          part[wave] = acc.hinge;
+          part[TE_NW + wave] = acc.sq;
+        }
+      }
       __syncthreads();
+      if constexpr (TRACE) {
+        if (tid == 0) {  // read before the step's closing barrier, rewritten only after it
+          const double* part = te_trace_lds<TE_NW>();
+          double hs = 0.0, qs = 0.0;
+          for (int k = 0; k < TE_NW; ++k) {
+            hs += part[k];
+            qs += part[TE_NW + k];
+          }
+          // mean hinge + lambda (L2(pos) + L2(neg)) / 2, L2 = (three means over B x d) / 3
+          tr.loss[tr.off[slot] + step_idx] = (float)(hs / (double)B + (double)hp.lam * qs / (6.0 * (double)B * (double)d));
+        }
+        ++step_idx;
+      }
       b1t *= (double)hp.b1;
       b2t *= (double)hp.b2;
       if (tid < dp) {
@@ -520,6 +610,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   require_batch(c, bt, "TransE");
   require_topk(tk, c->te_rank64 != 0, "TransE");
   require_probes(c, bt, tk, c->te_rank64 != 0, "TransE");
+  require_trace(c, hp, bt, tk, "TransE");
   // before the first upload: the buffers below are sized by DP, the kernels hold DP / 256 float4 per lane
   KP_REQUIRE(DP <= 512, "TransE: dimension > 512 not supported");
   KP_REQUIRE(hp->neg_ratio >= 1 && hp->batch_size >= 1 && hp->epochs >= 0, "TransE: bad hyper-parameters");
@@ -538,6 +629,13 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   const int64_t nrng = bt->rng_off[ns];
   int32_t* dRng = upload(c, c->te.rng, bt->rng, (size_t)std::max<int64_t>(1, nrng));
   const ProbeDev pd = upload_probes(c, bt, tk);
+  // kp_posttrain_rank_trace: the offsets and the losses, with the call's other uploads
+  const int n_trace = tk.trace ? tk.trace->trace_off[ns] : 0;
+  TeTraceArgs<true> trd{nullptr, nullptr};
+  if (tk.trace) {
+    trd.off = upload(c, c->te.tr_off, tk.trace->trace_off, (size_t)ns + 1);
+    trd.loss = reinterpret_cast<float*>(c->te.tr_loss.ensure(sizeof(float) * (size_t)std::max(1, n_trace)));
+  }
 
   TeHp h{};
   h.epochs = hp->epochs;
@@ -572,14 +670,19 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   hipEvent_t ea = c->event(0), eb = c->event(1);
   KP_HIP(hipEventRecord(ea, c->stream));
   const int vpl = (DP + 255) / 256;
-#define TE_LAUNCH(V, T, ST, L)                                                                                   \
-  hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP, c->dim, c->dE, \
-                     c->dR, dSlots, dOrder, dRows, dRng, h, dX)
-#define TE_NORM(V, T, ST)     \
-  if (l1)                     \
-    TE_LAUNCH(V, T, ST, true); \
-  else                        \
-    TE_LAUNCH(V, T, ST, false)
+#define TE_LAUNCH(V, T, ST, L)                                                                                      \
+  if (tk.trace)                                                                                                    \
+    hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L, true>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP, c->dim, \
+                       c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, trd);                                      \
+  else                                                                                                             \
+    hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP, c->dim,      \
+                       c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, TeTraceArgs<false>{})
+#define TE_NORM(V, T, ST)       \
+  if (l1) {                     \
+    TE_LAUNCH(V, T, ST, true);  \
+  } else {                      \
+    TE_LAUNCH(V, T, ST, false); \
+  }
 #define TE_STAGE(V, T)      \
   if (staged) {             \
     TE_NORM(V, T, true);    \
@@ -627,6 +730,9 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
     launch_rank_count(c, ns, dScores, ld, c->n_ent + 1, rk.po, rk.filt_off, rk.filt, 1, rk.target, rk.rank);
   }
   KP_HIP(hipEventRecord(c->ev1, c->stream));
+  if (n_trace > 0)  // with the other downloads, ahead of download_results' one wait
+    KP_HIP(hipMemcpyAsync(tk.trace->out_loss, trd.loss, sizeof(float) * (size_t)n_trace, hipMemcpyDeviceToHost,
+                          c->stream));
   download_results(c, bt, dX, rk, xp, tk, pd);
   float ms_all = 0.f, ms_hot = 0.f;
   KP_HIP(hipEventElapsedTime(&ms_all, c->ev0, c->ev1));

@@ -179,7 +179,9 @@ class PostTrainingEngine(RelevanceEngine):
         self._side_effects = 0
         self._probe_req = None
         self._cur_probes = None
+        self._trace = False
 
+    _trace = False
     TOP_K_MAX = 32  # kp_posttrain_rank_topk's largest k
     _top_k = 0
     PROBES_MAX = 64  # probes per slot
@@ -239,6 +241,22 @@ class PostTrainingEngine(RelevanceEngine):
                 p, b = p + R, a
             out.append((t, (int(p), int(b)), list(view.filter_for(p, delta.get(p) if delta else None))))
         return out
+
+    @property
+    def trace(self):
+        """Whether every post-training also reports the optimizer's loss of each of its steps
+        (False: the default): the ``l`` the reference's ``step_on_batch`` returns and shows on
+        its progress bar (multiclass_nll_optimizer.py:147-164,
+        pairwise_ranking_optimizer.py:165-203, bce_optimizer.py:167-208).  Every slot's result
+        gains ``"loss"``: [float, ...], one per step.  The relevances, the draws and the batches
+        are those of ``trace`` = False."""
+        return self._trace
+
+    @trace.setter
+    def trace(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise TypeError(f"trace must be a bool, got {on!r}")
+        self._trace = bool(on)
 
     @property
     def top_k(self):
@@ -557,6 +575,9 @@ class PostTrainingEngine(RelevanceEngine):
         if (self._side_effects or self._probe_req is not None) and self._sharded():
             # before any draw, as the lists
             raise NotImplementedError("probes with a slot sharding: their results are not gathered across ranks")
+        if self._trace and self._sharded():
+            # before any draw, as the lists and the probes
+            raise NotImplementedError("trace with a slot sharding: the losses are not gathered across ranks")
         self._sched = None  # this batch's natively assembled slots (TransE), made on first use
         if self._sharded():
             # ComplEx / ConvE: every rank owns one contiguous run of the batch's slots, so it
@@ -753,6 +774,9 @@ class PostTrainingEngine(RelevanceEngine):
         probed = any(s.probes is not None for s in slots)
         if probed:
             kw["probes"] = self._pack_probes(slots)
+        traced = self._trace
+        if traced:
+            kw["trace"] = True
         out = ctx.posttrain_rank(self._kp_hp, *packed, **kw)
         score, rank = out[0], out[1]
         if k:
@@ -761,8 +785,11 @@ class PostTrainingEngine(RelevanceEngine):
         if fill:
             for i, s in enumerate(slots):
                 s.result = {"target_score": float(score[i]), "target_rank": int(rank[i])}
+            if traced:
+                for s, loss in zip(slots, out[-1]):
+                    s.result["loss"] = [float(v) for v in loss]
             if probed:
-                p_score, p_rank = out[-1]
+                p_score, p_rank = out[-2 if traced else -1]
                 j = 0
                 for s in slots:
                     s.result["probes"] = [{"triple": t, "score": float(p_score[j + i]), "rank": int(p_rank[j + i])}
@@ -789,7 +816,10 @@ class PostTrainingEngine(RelevanceEngine):
 
     def _base_result(self, key, slots, pending_base):
         if key in self.base_pt_results:
-            return self.base_pt_results[key]
+            res = self.base_pt_results[key]
+            if self._trace:  # cached without a trace: no post-training runs for its sake
+                res.setdefault("loss", None)
+            return res
         res = slots[pending_base[key]].result
         self.base_pt_results[key] = res
         return res
@@ -873,6 +903,32 @@ class PostTrainingEngine(RelevanceEngine):
         finally:
             self._probe_req = None
         return [self._se_rule(rel, det) for rel, det in zip(rels, self.last_results)]
+
+    @staticmethod
+    def _tr_side(res):
+        """One post-training of a trace report: its target score and rank and the loss of each
+        of its steps, None when the result was cached without a trace."""
+        loss = res.get("loss")
+        return {"score": res["target_score"], "rank": res["target_rank"], "loss": None if loss is None else list(loss)}
+
+    def _tr_rule(self, relevance, detail):
+        raise NotImplementedError
+
+    def compute_traces(self, pred, rules):
+        """``compute_relevance_batch(pred, rules)`` -- the same schedule, draws, batches and
+        relevances, the generators left where it leaves them -- that also reports how every
+        post-training went: per rule ``{"relevance", "base", "post"}`` (the sufficient engine:
+        ``{"relevance", "conversions": [{"entity", "base", "post"}, ...]}``), ``base`` / ``post``
+        = ``{"score", "rank", "loss"}``, ``loss`` the optimizer's loss of each step in step
+        order (:attr:`trace`).  No post-training runs for the sake of a trace: a base result
+        cached without one reports ``"loss": None``."""
+        old = self._trace
+        self._trace = True
+        try:
+            rels = self.compute_relevance_batch(pred, rules)
+        finally:
+            self._trace = old
+        return [self._tr_rule(rel, det) for rel, det in zip(rels, self.last_results)]
 
     def _schedule_multi(self, items, checkpoints):
         raise NotImplementedError
@@ -1322,6 +1378,10 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
         pt, base = detail
         return {"relevance": relevance, "base": self._se_side(base), "post": self._se_side(pt)}
 
+    def _tr_rule(self, relevance, detail):
+        pt, base = detail
+        return {"relevance": relevance, "base": self._tr_side(base), "post": self._tr_side(pt)}
+
 
 class SufficientPostTrainingEngine(PostTrainingEngine):
     """post_training_engine.py:160-207."""
@@ -1335,6 +1395,11 @@ class SufficientPostTrainingEngine(PostTrainingEngine):
     def _se_rule(self, relevance, detail):
         return {"relevance": relevance,
                 "conversions": [{"entity": int(e), "base": self._se_side(base), "post": self._se_side(pt)}
+                                for e, (pt, base) in zip(self.entities_to_convert, detail)]}
+
+    def _tr_rule(self, relevance, detail):
+        return {"relevance": relevance,
+                "conversions": [{"entity": int(e), "base": self._tr_side(base), "post": self._tr_side(pt)}
                                 for e, (pt, base) in zip(self.entities_to_convert, detail)]}
 
     def __init__(self, model, dataset, hp, rng=None):

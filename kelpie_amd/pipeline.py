@@ -12,7 +12,8 @@ Mirrors the reference's callers of the relevance engine:
   prediction as the reference does.  With ``top_k`` > 0 every record also holds
   ``"counterfactuals"`` (kelpie_amd/builder.py): what the model predicts instead.  With
   ``side_effects`` > 0 every record also holds ``"side_effects"``: what each rule's edit
-  does to the subject's other held-out facts.
+  does to the subject's other held-out facts.  With ``trace`` every record also holds
+  ``"traces"``: the optimizer's per-step loss of each rule's post-trainings.
 
 The DP / CRIAGE baselines and summarisation are out of scope.
 """
@@ -55,7 +56,7 @@ class SufficientPipeline(Pipeline):
 
 
 def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="auto", entity_classes=None,
-                   pipelined=False, top_k=0, side_effects=0):
+                   pipelined=False, top_k=0, side_effects=0, trace=False):
     """explain.py:49-89 for the post-training engines (baseline=None, no summarisation)."""
     if prefilter == TYPE_PREFILTER:
         raise NotImplementedError("type_based prefilter: out of scope (kelpie_amd/prefilters.py)")
@@ -65,12 +66,14 @@ def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="a
         xsi = 5 if xsi is None else xsi
         engine = NecessaryPostTrainingEngine(model, dataset, hp)
         return NecessaryPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
-                                                                  top_k=top_k, side_effects=side_effects))
+                                                                  top_k=top_k, side_effects=side_effects,
+                                                                  trace=trace))
     if mode == "sufficient":
         xsi = 0.9 if xsi is None else xsi
         engine = SufficientPostTrainingEngine(model, dataset, hp)
         return SufficientPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
-                                                                  top_k=top_k, side_effects=side_effects))
+                                                                  top_k=top_k, side_effects=side_effects,
+                                                                  trace=trace))
     raise ValueError(f"unknown mode {mode!r}")
 
 
@@ -143,7 +146,7 @@ def reference_construction_draws(model_name, num_entities, num_relations, model_
 
 
 def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefilter=None, prefilter_k=20,
-                xsi=None, skip=-1, output_path=None, device=0, top_k=0, side_effects=0):
+                xsi=None, skip=-1, output_path=None, device=0, top_k=0, side_effects=0, trace=False):
     """explain.py main() (explain.py:143-203) without the CLI: seeds 42 (explain.py:144),
     the reference model construction's random draws (:171-172), the checkpoint state dict
     (``torch.load(path, weights_only=True)``, :174) as a frozen model on the MI355X, the
@@ -160,5 +163,5 @@ def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefi
     reference_construction_draws(model_name, dataset.num_entities, dataset.num_relations, model_params)
     model = from_state_dict(model_name, dataset, state, model_params, device=device)
     pipe = build_pipeline(model, dataset, hp, mode, prefilter=prefilter, xsi=xsi, top_k=top_k,
-                          side_effects=side_effects)
+                          side_effects=side_effects, trace=trace)
     return explain_preds(pipe, dataset, preds, prefilter_k=prefilter_k, skip=skip, output_path=output_path)
