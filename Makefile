@@ -11,7 +11,7 @@ LIB := kelpie_amd/libkelpie_hip.so
 
 all: $(LIB)
 
-build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn_plan.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp kelpie_amd/csrc/kp_probe_check.hpp kelpie_amd/csrc/kp_trace_check.hpp kelpie_amd/csrc/kp_cx_plan.hpp kelpie_amd/csrc/kp_cv_plan.hpp include/kelpie_hip.h
+build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn_plan.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp kelpie_amd/csrc/kp_probe_check.hpp kelpie_amd/csrc/kp_trace_check.hpp kelpie_amd/csrc/kp_marks_check.hpp kelpie_amd/csrc/kp_cx_plan.hpp kelpie_amd/csrc/kp_cv_plan.hpp include/kelpie_hip.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -119,5 +119,18 @@ build/san/trace_check_asan: $(TRACE_CHECK_DEP)
 	@mkdir -p build/san
 	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
 
+# the epoch marks' check and plan (kp_marks_check.hpp, no HIP) alone in
+# tests/native/marks_check_driver.cpp, plain and under the host sanitizers; run by
+# tests/test_marks_check.py (CPU suite)
+MARKS_CHECK_DEP := tests/native/marks_check_driver.cpp kelpie_amd/csrc/kp_marks_check.hpp kelpie_amd/csrc/kp_trace_check.hpp include/kelpie_hip.h
+marks_check: build/san/marks_check
+marks_check_asan: build/san/marks_check_asan
+build/san/marks_check: $(MARKS_CHECK_DEP)
+	@mkdir -p build/san
+	$(CXX) -O2 -std=c++17 -Wall $< -o $@
+build/san/marks_check_asan: $(MARKS_CHECK_DEP)
+	@mkdir -p build/san
+	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
+
 .PHONY: asan tsan batch_asan attn_plan attn_plan_asan step_plan step_plan_asan probe_check probe_check_asan \
-        trace_check trace_check_asan
+        trace_check trace_check_asan marks_check marks_check_asan

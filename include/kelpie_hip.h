@@ -269,6 +269,43 @@ typedef struct {
 int kp_posttrain_rank_trace(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
                             float* out_scores, const kp_probes* probes, const kp_trace* trace);
 
+/* ---- Epoch marks: score and rank of every post-training after chosen epochs ----
+ * A call carries one strictly increasing list of epochs 0 <= e_0 < ... < e_{n-1} <= hp->epochs,
+ * 1 <= n <= 16.  Mark j of slot s is what kp_posttrain_rank returns for that slot on the same
+ * batch with hp->epochs = e_j: the kelpie row after e_j epochs, scored, masked, counted and
+ * converted exactly as the slot's own target (get_triple_results, post_training_engine.py:
+ * 101-125, on the model under training).  Every family's draws are laid out epoch-major or
+ * step-major, so the shorter run reads a prefix of the same draws.  Hence mark 0 is the result
+ * of x0, mark hp->epochs is the slot's own out_score and out_x row bit for bit and its
+ * out_rank, a slot without rows has x0's result at every mark, and ConvE marks are ranked on
+ * the eval-mode forward as the final row is.
+ * It is NOT the reference started with epochs = e_j from the same seed: that run draws fewer
+ * numbers per post-training, so every post-training after the first starts elsewhere in the
+ * random stream.
+ *   epochs      [n]                strictly increasing, in [0, hp->epochs]
+ *   out_score   [n_slots][n]       the marks' target scores, converted as kp_batch.out_score
+ *   out_rank    [n_slots][n]       their filtered ranks
+ *   out_x       [n_slots][n][dim]  the kelpie rows at the marks (may be NULL) */
+typedef struct {
+  int32_t n;
+  const int32_t* epochs;
+  float* out_score;
+  int64_t* out_rank;
+  float* out_x;
+} kp_marks;
+
+/* kp_posttrain_rank_trace, plus the marks of every slot.  out_x, out_score, out_rank, the
+ * top-k lists, the probes' results and the trace are bit for bit those without marks; the
+ * lists and the probes stay on the final row.  marks == NULL is kp_posttrain_rank_trace.
+ * KP_EINVAL (after the batch, probe and trace checks, before any upload) for malformed marks;
+ * KP_ENOTSUP with marks when the context ranks in fp32 (KP_TE_RANK=f32, KP_CV_RANK=f32).
+ * The rows are captured by the step kernels themselves (no launch is added to the step path)
+ * and ranked after the slots, in chunks of whole 16-row groups whose fp64 query rows and
+ * filter bitmaps stay within 64 MiB (KP_MARKS_CHUNK=n, a diagnostic, forces n rows). */
+int kp_posttrain_rank_marks(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
+                            float* out_scores, const kp_probes* probes, const kp_trace* trace,
+                            const kp_marks* marks);
+
 /* Model.all_scores (model.py:19; transe.py:48-65, complex.py:88-112,
  * conve.py:133-158) for n (head, relation) pairs over the frozen entities:
  * out[n][n_ent].  The RelevanceEngine.select_entities_to_convert sweep

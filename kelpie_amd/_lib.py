@@ -30,7 +30,7 @@ EXPORTS = ["kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_posttrain_ran
            "kp_gather_i32", "kp_rng_transe_calls_async", "kp_rng_torch_take", "kp_conve_train_begin",
            "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free", "kp_ctx_set_inflight",
            "kp_last_attn_plan", "kp_posttrain_rank_topk", "kp_posttrain_rank_probes", "kp_trace_steps",
-           "kp_posttrain_rank_trace"]
+           "kp_posttrain_rank_trace", "kp_posttrain_rank_marks"]
 
 
 class ModelDesc(C.Structure):
@@ -66,6 +66,35 @@ class Trace(C.Structure):
     _fields_ = [("trace_off", C.c_void_p), ("out_loss", C.c_void_p)]
 
 
+class Marks(C.Structure):
+    _fields_ = [("n", C.c_int32), ("epochs", C.c_void_p), ("out_score", C.c_void_p), ("out_rank", C.c_void_p),
+                ("out_x", C.c_void_p)]
+
+
+MARKS_MAX = 16  # kp_marks.n
+
+
+def check_marks(epochs, hp_epochs=None):
+    """The mark list of kp_posttrain_rank_marks as an int32 array: 1 to 16 strictly increasing
+    epochs in [0, hp_epochs] (include/kelpie_hip.h, "Epoch marks").  TypeError for a value
+    that is no integer, ValueError for a list that breaks a rule; host work only."""
+    if isinstance(epochs, (str, bytes)) or not hasattr(epochs, "__iter__"):
+        raise TypeError(f"marks: a list of epochs is needed, got {type(epochs).__name__}")
+    vals = list(epochs)
+    for e in vals:
+        if isinstance(e, (bool, np.bool_)) or not isinstance(e, (int, np.integer)):
+            raise TypeError(f"marks: epochs must be integers, got {type(e).__name__}")
+    if not 1 <= len(vals) <= MARKS_MAX:
+        raise ValueError(f"marks: 1 to {MARKS_MAX} epochs are needed, got {len(vals)}")
+    if vals[0] < 0:
+        raise ValueError("marks: negative epoch")
+    if any(b <= a for a, b in zip(vals, vals[1:])):
+        raise ValueError("marks: epochs must be strictly increasing")
+    if hp_epochs is not None and vals[-1] > hp_epochs:
+        raise ValueError(f"marks: epoch {vals[-1]} beyond the post-training's {hp_epochs} epochs")
+    return np.asarray(vals, dtype=np.int32)
+
+
 class KelpieHipError(RuntimeError):
     pass
 
@@ -96,6 +125,9 @@ def lib():
             L.kp_posttrain_rank_trace.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
                                                   C.c_void_p, C.POINTER(Probes), C.POINTER(Trace)]
             L.kp_trace_steps.argtypes = [C.c_int32, C.POINTER(HP), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "kp_posttrain_rank_marks"):  # KELPIE_HIP_LIB may name a build from before the marks
+            L.kp_posttrain_rank_marks.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.POINTER(Probes), C.POINTER(Trace), C.POINTER(Marks)]
         L.kp_all_scores.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kp_convertible.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
@@ -403,7 +435,7 @@ class Context:
             pass
 
     def posttrain_rank(self, hp: HP, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False, topk=0,
-                       probes=None, trace=False):
+                       probes=None, trace=False, marks=None):
         """kp_posttrain_rank: (target scores, ranks, final rows or None).  With ``topk`` > 0
         (kp_posttrain_rank_topk) a fourth element: (ids int32 [n][topk], scores float32
         [n][topk]), the slots' best unmasked tails, -1 / 0 past the last one.  With ``probes``
@@ -411,7 +443,10 @@ class Context:
         (kp_posttrain_rank_probes) a further element: (scores float32 [m], ranks int64 [m]).
         With ``trace`` (kp_posttrain_rank_trace) a last element: the slots' loss arrays, one
         float32 array per slot with the loss of every optimizer step (sized by
-        kp_trace_steps)."""
+        kp_trace_steps).  With ``marks`` = a list of epochs (kp_posttrain_rank_marks) a last
+        element after that: (scores float32 [n][m], ranks int64 [n][m], rows float32
+        [n][m][dim] or None without ``want_x``), every slot's result after each marked epoch:
+        what this call returns for the slot with ``hp.epochs`` set to that epoch."""
         topk = int(topk)
         if not 0 <= topk <= 32:
             raise ValueError(f"topk must be in [0, 32], got {topk}")
@@ -429,43 +464,55 @@ class Context:
         out_r = np.zeros(n, np.int64)
         b = Batch(n, _ptr(x0), _ptr(row_off), _ptr(rows), _ptr(rng_off), _ptr(rng), _ptr(pred), _ptr(filt_off),
                   _ptr(filt), _ptr(out_x), _ptr(out_s), _ptr(out_r))
-        if topk == 0 and probes is None and not trace:
+        if topk == 0 and probes is None and not trace and marks is None:
             check(lib().kp_posttrain_rank(self.h, C.byref(hp), C.byref(b)), self.h)
             return out_s, out_r, out_x
+        # the optional requests, each marshalled once; the entry point is the first that takes
+        # all of those asked for (a later one takes NULL for every request before its own)
         ids = np.full((n, topk), -1, np.int32) if topk else None
         top = np.zeros((n, topk), np.float32) if topk else None
         ret = (out_s, out_r, out_x) + (((ids, top),) if topk else ())
-        if probes is None and not trace:
-            check(lib().kp_posttrain_rank_topk(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top)), self.h)
-            return ret
+        pr = tr = mk = None
+        if probes is not None:
+            p_off, p_tr, pf_off, pf = probes
+            p_off = np.ascontiguousarray(p_off, dtype=np.int32)
+            p_tr = np.ascontiguousarray(np.asarray(p_tr, dtype=np.int32).reshape(-1, 2))
+            pf_off = np.ascontiguousarray(pf_off, dtype=np.int32)
+            pf = np.ascontiguousarray(pf, dtype=np.int32) if len(pf) else np.zeros(1, np.int32)
+            m = len(p_tr)
+            if len(p_off) != n + 1 or len(pf_off) != m + 1:
+                raise ValueError("probes: probe_off needs one entry per slot plus one, filt_off one per probe plus one")
+            p_s = np.zeros(m, np.float32)
+            p_r = np.zeros(m, np.int64)
+            pr = Probes(m, _ptr(p_off), _ptr(p_tr), _ptr(pf_off), _ptr(pf), _ptr(p_s), _ptr(p_r))
+            ret += ((p_s, p_r),)
         if trace:
             t_off = np.zeros(n + 1, np.int32)
             np.cumsum(trace_steps(self.model_name, hp, row_off, rows), out=t_off[1:])
             loss = np.zeros(max(1, int(t_off[-1])), np.float32)
             tr = Trace(_ptr(t_off), _ptr(loss))
-            losses = [loss[t_off[i]:t_off[i + 1]] for i in range(n)]
-        if probes is None:
-            check(lib().kp_posttrain_rank_trace(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top), None,
-                                                C.byref(tr)), self.h)
-            return ret + (losses,)
-        p_off, p_tr, pf_off, pf = probes
-        p_off = np.ascontiguousarray(p_off, dtype=np.int32)
-        p_tr = np.ascontiguousarray(np.asarray(p_tr, dtype=np.int32).reshape(-1, 2))
-        pf_off = np.ascontiguousarray(pf_off, dtype=np.int32)
-        pf = np.ascontiguousarray(pf, dtype=np.int32) if len(pf) else np.zeros(1, np.int32)
-        m = len(p_tr)
-        if len(p_off) != n + 1 or len(pf_off) != m + 1:
-            raise ValueError("probes: probe_off needs one entry per slot plus one, filt_off one per probe plus one")
-        p_s = np.zeros(m, np.float32)
-        p_r = np.zeros(m, np.int64)
-        pr = Probes(m, _ptr(p_off), _ptr(p_tr), _ptr(pf_off), _ptr(pf), _ptr(p_s), _ptr(p_r))
-        if trace:
-            check(lib().kp_posttrain_rank_trace(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top),
-                                                C.byref(pr), C.byref(tr)), self.h)
-            return ret + ((p_s, p_r), losses)
-        check(lib().kp_posttrain_rank_probes(self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top),
-                                             C.byref(pr)), self.h)
-        return ret + ((p_s, p_r),)
+            ret += ([loss[t_off[i]:t_off[i + 1]] for i in range(n)],)
+        if marks is not None:
+            # the list as given: the library checks its rules against hp.epochs
+            ep = np.ascontiguousarray(marks, dtype=np.int32).reshape(-1)
+            nm = len(ep)
+            m_s = np.zeros((n, nm), np.float32)
+            m_r = np.zeros((n, nm), np.int64)
+            m_x = np.zeros((n, nm, self.dim), np.float32) if want_x else None
+            mk = Marks(nm, _ptr(ep), _ptr(m_s), _ptr(m_r), _ptr(m_x))
+            ret += ((m_s, m_r, m_x),)
+        ref = lambda st: C.byref(st) if st is not None else None  # noqa: E731
+        head = (self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top))
+        if mk is not None:
+            rc = lib().kp_posttrain_rank_marks(*head, ref(pr), ref(tr), ref(mk))
+        elif tr is not None:
+            rc = lib().kp_posttrain_rank_trace(*head, ref(pr), ref(tr))
+        elif pr is not None:
+            rc = lib().kp_posttrain_rank_probes(*head, ref(pr))
+        else:
+            rc = lib().kp_posttrain_rank_topk(*head)
+        check(rc, self.h)
+        return ret
 
     def all_scores(self, heads, rels):
         heads = np.ascontiguousarray(heads, dtype=np.int32)

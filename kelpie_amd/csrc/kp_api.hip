@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "kp_common.hpp"
+#include "kp_marks_check.hpp"
 #include "kp_trace_check.hpp"
 
 int cx_pick_db(int dim);
@@ -213,10 +214,14 @@ static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, co
     if (b->n_slots == 0) {
       KP_REQUIRE(tk.k >= 0 && tk.k <= 32, "kp_posttrain_rank_topk: k must be in [0, 32]");
       KP_REQUIRE(tk.n_probes() == 0, "kp_posttrain_rank_probes: probes without a slot");
+      static const char* const names[] = {"TransE", "ComplEx", "ConvE", "DistMult"};
       if (tk.trace) {  // the same rule and message as with slots (kp_trace_check.hpp handles n_slots == 0)
-        static const char* const names[] = {"TransE", "ComplEx", "ConvE", "DistMult"};
         if (const char* why = kp_check_trace(c->model, hp, 0, b->row_off, b->rows, tk.trace))
           throw KpError{KP_EINVAL, std::string(names[c->model]) + ": trace: " + why};
+      }
+      if (tk.marks) {  // the same rule and message as with slots
+        if (const char* why = kp_check_marks(hp, tk.marks))
+          throw KpError{KP_EINVAL, std::string(names[c->model]) + ": marks: " + why};
       }
       return;
     }
@@ -266,6 +271,21 @@ int kp_posttrain_rank_trace(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32
   tk.scores = out_scores;
   tk.probes = probes;
   tk.trace = trace;
+  return posttrain_rank_call(c, hp, b, tk);
+}
+
+// kp_posttrain_rank_trace with every slot's score, rank and row after the marked epochs:
+// get_triple_results (post_training_engine.py:101-125) on the model under training
+int kp_posttrain_rank_marks(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k, int32_t* out_ids,
+                            float* out_scores, const kp_probes* probes, const kp_trace* trace,
+                            const kp_marks* marks) {
+  TopkOut tk;
+  tk.k = k;
+  tk.ids = out_ids;
+  tk.scores = out_scores;
+  tk.probes = probes;
+  tk.trace = trace;
+  tk.marks = marks;
   return posttrain_rank_call(c, hp, b, tk);
 }
 

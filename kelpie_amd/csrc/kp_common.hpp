@@ -137,11 +137,18 @@ struct RankWs {
   DevBuf p_trip, p_po, p_filt_off, p_filt;
   DevBuf p_target, p_rank;
   DevBuf p_q64, p_t64, p_bits;
+  // kp_posttrain_rank_marks (kp_posttrain.hpp fills them): the mark rows' (row, p, o) [m][3],
+  // objects [m], filter CSR and results [m], m = slots * marks; one chunk of rows' fp64
+  // queries, target | kelpie column scores and filter bitmaps, as the probes'
+  DevBuf m_trip, m_po, m_filt_off, m_filt;
+  DevBuf m_target, m_rank;
+  DevBuf m_q64, m_t64, m_bits;
   auto all() {
     return std::array{&pred,     &po,       &filt_off, &filt,       &target,     &rank,   &q64,
                       &t64,      &scores,   &bits,     &cand_key,   &cand_col,   &top_ids, &top_scores,
                       &p_trip,   &p_po,     &p_filt_off, &p_filt,   &p_target,   &p_rank, &p_q64,
-                      &p_t64,    &p_bits};
+                      &p_t64,    &p_bits,   &m_trip,   &m_po,       &m_filt_off, &m_filt, &m_target,
+                      &m_rank,   &m_q64,    &m_t64,    &m_bits};
   }
 };
 KP_WS_COMPLETE(RankWs);
@@ -161,10 +168,13 @@ struct ComplexWs {
   // regulariser factors [n_ent] / [n_rel2] (fp64, once per batch), the trace offsets
   // [ns + 1] and the losses [steps]
   DevBuf tr_term, tr_fe, tr_fr, tr_off, tr_loss;
+  // kp_posttrain_rank_marks: the mark rows [ns][marks][dp] and, per entry of acts, the mark
+  // row its update also stores (-1: none)
+  DevBuf marks, mark_row;
   auto all() {
     return std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
                       &tsum, &qpair, &lsef, &am, &al, &ao, &qs, &score_q, &score_out, &tr_term, &tr_fe, &tr_fr,
-                      &tr_off, &tr_loss};
+                      &tr_off, &tr_loss, &marks, &mark_row};
   }
 };
 KP_WS_COMPLETE(ComplexWs);
@@ -176,7 +186,10 @@ struct TranseWs {
   DevBuf order;             // slots, longest first
   DevBuf heads, rels;       // score queries: the ranked triples' (-1, relation), and transe_all_scores' pairs
   DevBuf tr_off, tr_loss;   // kp_posttrain_rank_trace: the trace offsets [ns + 1] and the losses [steps]
-  auto all() { return std::array{&x, &slots, &rows, &rng, &order, &heads, &rels, &tr_off, &tr_loss}; }
+  DevBuf marks, mark_ep;    // kp_posttrain_rank_marks: the mark rows [ns][marks][dp]; the header and the epochs' marks
+  auto all() {
+    return std::array{&x, &slots, &rows, &rng, &order, &heads, &rels, &tr_off, &tr_loss, &marks, &mark_ep};
+  }
 };
 KP_WS_COMPLETE(TranseWs);
 
@@ -207,11 +220,16 @@ struct ConveWs {
   // kp_posttrain_rank_trace: the trace offsets [ns + 1] and losses [steps]; a step's rows
   // [rows][dp], one chunk's logits [chunk][ld] and the rows' summed BCE terms (fp64)
   DevBuf tr_off, tr_loss, tr_rows, tr_scores, tr_rowloss;
+  // kp_posttrain_rank_marks: the mark rows [ns][marks][dp], per entry of the active lists the
+  // mark row its update also stores (-1: none), and a chunk of mark rows' encoder sources
+  // (-row - 1, p) and outputs [chunk][dp]
+  DevBuf marks, mark_row, mark_src, mark_q;
   auto all() {
     return std::array{&x, &s1, &s2, &kinst, &finst, &acts, &tails, &keep_bits, &fcf, &fpairs, &flat, &slab,
                       &relu, &g3, &sr_src, &sr_rng, &psr, &relu_s, &slab_l, &mid, &map_l, &map_m, &gs, &dls,
                       &q, &enc_src, &enc_bits, &fchunks, &fpart, &gscale, &o, &dfc, &gk, &dflat, &dl, &rank_src,
-                      &probe_src, &probe_q, &tr_off, &tr_loss, &tr_rows, &tr_scores, &tr_rowloss};
+                      &probe_src, &probe_q, &tr_off, &tr_loss, &tr_rows, &tr_scores, &tr_rowloss, &marks,
+                      &mark_row, &mark_src, &mark_q};
   }
 };
 KP_WS_COMPLETE(ConveWs);
@@ -352,6 +370,9 @@ struct TopkOut {
   int n_probes() const { return probes ? probes->n : 0; }
   // kp_posttrain_rank_trace's request (nullptr: no trace)
   const kp_trace* trace = nullptr;
+  // kp_posttrain_rank_marks' request (nullptr: no marks)
+  const kp_marks* marks = nullptr;
+  int n_marks() const { return marks ? marks->n : 0; }
 };
 void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
 // kp_complex.hip, product policy

@@ -394,13 +394,27 @@ __global__ __launch_bounds__(64) void kp_cx_trace_sum(int half, const int4* __re
 #ifndef KP_CX_UPD64
 #define KP_CX_UPD64 0
 #endif
+// kp_posttrain_rank_marks: per entry of the step's active list the mark row its update also
+// stores (-1: none), and the mark rows [slots][marks][DP].  Without the flag the struct is
+// empty and kp_cx_update is what it was.
+template <bool MARKS>
+struct CxMarkArgs {};
+template <>
+struct CxMarkArgs<true> {
+  const int32_t* row;  // [active slots of the step]
+  float* rows;
+};
+
 // Sum a slot's contributions, add the N3 term, apply the optimizer (torch op order).
 // (`half` is the policy's extent w, as in kp_cx_contrib)
-template <int DP, class Prod>
+// MARKS: the thread that stores an updated element stores it to the slot's mark row as well
+// when the plan marks this (slot, step); a plain vector store, no launch of its own
+template <int DP, class Prod, bool MARKS = false>
 __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __restrict__ act,
                                                     const CxPlan* __restrict__ plans, int nq,
                                                     const float* __restrict__ contrib, float* __restrict__ X,
-                                                    float* __restrict__ S1, float* __restrict__ S2, CxOpt opt) {
+                                                    float* __restrict__ S1, float* __restrict__ S2, CxOpt opt,
+                                                    CxMarkArgs<MARKS> mk) {
   constexpr int G = Prod::G;
   const int tid = threadIdx.x;
   const int4 a4 = act[blockIdx.x];  // slot, plan, qoff, toff
@@ -565,6 +579,10 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
         xd = xd + (-opt.lr) * gd;
       }
       x[d] = xd;
+      if constexpr (MARKS) {
+        const int mrow = mk.row[blockIdx.x];  // block-uniform
+        if (mrow >= 0) mk.rows[(size_t)mrow * DP + d] = xd;
+      }
     }
   }
 }
@@ -678,7 +696,8 @@ template <int DB, class Prod>
 void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, const CxQuery* pq,
                    const int4* stepq, int nq, const int4* stept, int nt, const float* tsum, const float* qpair,
                    const float* lsef, const float* am, const float* al, const float* aO, int n_split, float* contrib,
-                   float* X, float* S1, float* S2, const CxOpt& opt, const CxTraceDev& tr = {}, int step = 0) {
+                   float* X, float* S1, float* S2, const CxOpt& opt, const CxTraceDev& tr = {}, int step = 0,
+                   const CxMarkArgs<true>* mk = nullptr) {
   if (n_act <= 0) return;
   const int half = Prod::extent(c->dim);
   KP_REQUIRE(n_split >= 1 && n_split <= 64, "cx contrib: one attention split per lane");
@@ -699,8 +718,12 @@ void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, c
                        tr.off, step, tr.loss);
     KP_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq, contrib, X,
-                     S1, S2, opt);
+  if (mk)  // a step that ends a marked epoch of one of its slots: the MARKS form instead, not a further launch
+    hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod, true>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq,
+                       contrib, X, S1, S2, opt, *mk);
+  else
+    hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq, contrib,
+                       X, S1, S2, opt, CxMarkArgs<false>{});
   KP_HIP(hipGetLastError());
 }
 
@@ -753,6 +776,8 @@ struct CxDev {
   RankDev rk;
   ProbeDev probes;
   CxTraceDev trace;
+  MarksDev marks;
+  int32_t* mark_row = nullptr;  // [acts] the mark row an active entry's update also stores, or -1
   // the attention's: sized and planned by cx_preloop
   float *am = nullptr, *al = nullptr, *ao = nullptr, *qs = nullptr;
   std::vector<AttnPlan> step_plan;  // [T]
@@ -764,7 +789,8 @@ static_assert(sizeof(CxI4) == sizeof(int4) && alignof(CxI4) == alignof(int4), "C
 inline const int2* as_dev(const CxI2* p) { return reinterpret_cast<const int2*>(p); }
 inline const int4* as_dev(const CxI4* p) { return reinterpret_cast<const int4*>(p); }
 
-CxDev cx_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, const CxStepPlan& sp, std::vector<float>& xp) {
+CxDev cx_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk, const CxStepPlan& sp,
+                    std::vector<float>& xp) {
   const int ns = bt->n_slots, DP = c->dp;
   CxDev d;
   d.X = upload_x0(c, c->cx.x, bt, xp);
@@ -793,6 +819,12 @@ CxDev cx_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, const CxSt
   d.pred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
   d.rk = upload_rank_inputs(c, bt, tk);
   d.probes = upload_probes(c, bt, tk);
+  // kp_posttrain_rank_marks: the mark rows (each the padded x0 until a step captures it)
+  d.marks = upload_marks(c, c->cx.marks, hp, bt, tk, d.X);
+  if (d.marks.nm > 0) {
+    const std::vector<int32_t> mr = marks_act_rows(d.marks, sp.act_off, sp.T, [&](int i) { return sp.acts[i].x; });
+    d.mark_row = upload(c, c->cx.mark_row, mr.data(), mr.size());
+  }
   if (tk.trace) {  // the trace's offsets and workspaces, with the call's other uploads
     CxTraceDev& t = d.trace;
     t.total = tk.trace->trace_off[ns];
@@ -887,10 +919,11 @@ int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxD
     const AdamStep as = adam_step(hp, t);
     opt.step_size = as.step_size;
     opt.bc2_sqrt = as.bc2_sqrt;
+    const CxMarkArgs<true> mk{d.mark_row ? d.mark_row + sp.act_off[t] : nullptr, d.marks.X};
     CX_DISPATCH(DBV, launch_update<DB, Prod>(c, na, d.acts + sp.act_off[t], d.plans, d.pq, d.stepq + sp.q_off[t], nq,
                                              d.stept + sp.t_off[t], sp.t_off[t + 1] - sp.t_off[t], d.tsum, d.qpair,
                                              d.lsef, d.am, d.al, d.ao, sp_n, d.contrib, d.X, d.S1, d.S2, opt,
-                                             d.trace, t));
+                                             d.trace, t, marks_at_step(d.marks, t) ? &mk : nullptr));
     if (g_host_times) {
       if (t == 0) t_steps[0] = host_ms();
       if (t == 1) t_steps[1] = host_ms();
@@ -918,6 +951,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   require_topk(tk, true, Prod::name);
   require_probes(c, bt, tk, true, Prod::name);
   require_trace(c, hp, bt, tk, Prod::name);
+  require_marks(hp, tk, true, Prod::name);
   const CxOpt opt = make_opt(hp, who);
 
   CxStepPlan sp;
@@ -926,7 +960,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   const double t_plan = g_host_times ? host_ms() : 0.0;
 
   std::vector<float> xp;
-  CxDev d = cx_workspaces(c, bt, tk, sp, xp);
+  CxDev d = cx_workspaces(c, hp, bt, tk, sp, xp);
   cx_preloop<Prod>(c, sp, d, opt.reg_w, opt.reg_n2);
 
   // loop-interval events, destroyed on every exit path (a KP_HIP / KP_REQUIRE below throws)
@@ -953,11 +987,16 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   rank_probes(c, d.probes, RANK64_DOT, [&](int r0, int m) {
     CX_DISPATCH(c->dp / 16, launch_probeq64<DB, Prod>(c, d.X, d.probes, r0, m));
   });
+  // the marks: the probe form reads row trip[3 r] of the mark workspace instead of a slot's row
+  rank_probes(c, d.marks.rows, RANK64_DOT, [&](int r0, int m) {
+    CX_DISPATCH(c->dp / 16, launch_probeq64<DB, Prod>(c, d.marks.X, d.marks.rows, r0, m));
+  }, &c->rank.m_bits);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
 
   if (d.trace.total > 0)  // with the other downloads, ahead of download_results' one wait
     KP_HIP(hipMemcpyAsync(tk.trace->out_loss, d.trace.loss, sizeof(float) * (size_t)d.trace.total,
                           hipMemcpyDeviceToHost, c->stream));
+  download_marks(c, bt, tk, d.marks);
   const double t_enq = download_results(c, bt, d.X, d.rk, xp, tk, d.probes);
   const double t_done = g_host_times ? host_ms() : 0.0;
   if (g_host_times)

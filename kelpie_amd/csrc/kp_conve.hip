@@ -483,13 +483,27 @@ __global__ __launch_bounds__(256) void kp_cv_fgrad(CvConst k, const int4* __rest
     fpart[(size_t)blockIdx.x * k.dim + d] = (gw_s[0][d] + gw_s[1][d]) + (gw_s[2][d] + gw_s[3][d]);
 }
 
+// kp_posttrain_rank_marks: per entry of the step's active list the mark row its update also
+// stores (-1: none), and the mark rows [slots][marks][dp].  Without the flag the struct is
+// empty and kp_cv_update is what it was.
+template <bool MARKS>
+struct CvMarkArgs {};
+template <>
+struct CvMarkArgs<true> {
+  const int32_t* row;  // [active slots of the step]
+  float* rows;
+};
+
 // gradient assembly + Adam, one workgroup per active slot; its frozen-head pairs' part is
 // the sum of its kp_cv_fgrad chunks (A.pad0: first chunk of the step, A.pad1: count)
+// MARKS: the thread that stores an updated element stores it to the slot's mark row as well
+// when the plan marks this (slot, step); a plain vector store, no launch of its own
+template <bool MARKS = false>
 __global__ __launch_bounds__(256) void kp_cv_update(CvConst k, const CvAct* __restrict__ act,
                                                     const float* __restrict__ Q, const float* __restrict__ gk,
                                                     const float* __restrict__ dl, const float* __restrict__ fpart,
                                                     float* __restrict__ X, float* __restrict__ S1,
-                                                    float* __restrict__ S2, CvOpt opt) {
+                                                    float* __restrict__ S2, CvOpt opt, CvMarkArgs<MARKS> mk) {
   __shared__ float xs[640];
   const CvAct A = act[blockIdx.x];
   const int tid = threadIdx.x;
@@ -547,7 +561,12 @@ __global__ __launch_bounds__(256) void kp_cv_update(CvConst k, const CvAct* __re
     v2 = v2 * opt.b2;
     v2 = v2 + (opt.one_minus_b2 * gd) * gd;
     const float den = sqrtf(v2) / opt.bc2_sqrt + opt.eps;
-    x[d] = xs[d] + (-opt.step_size * m1) / den;
+    const float xd = xs[d] + (-opt.step_size * m1) / den;
+    x[d] = xd;
+    if constexpr (MARKS) {
+      const int mrow = mk.row[blockIdx.x];  // block-uniform
+      if (mrow >= 0) mk.rows[(size_t)mrow * k.dp + d] = xd;
+    }
     S1[o] = m1;
     S2[o] = v2;
   }
@@ -823,17 +842,21 @@ namespace {
 // the plan's element types are the HIP vector types' layout: their arrays are uploaded as such
 static_assert(sizeof(CvI2) == sizeof(int2) && alignof(CvI2) == alignof(int2), "CvI2 is int2");
 static_assert(sizeof(CvI4) == sizeof(int4) && alignof(CvI4) == alignof(int4), "CvI4 is int4");
-// a plan list on the device, at least one element long (an empty list sizes the buffer only)
+// a plan list on the device, at least one element long (an empty list sizes the buffer only:
+// a call without a step, hp.epochs == 0 or no slot with rows, has nothing to copy)
+template <class D, class T>
+D* upload_list(kp_ctx* c, DevBuf& b, const std::vector<T>& v) {
+  static_assert(sizeof(D) == sizeof(T), "the list's device type has the host type's layout");
+  D* d = reinterpret_cast<D*>(b.ensure(sizeof(D) * std::max<size_t>(1, v.size())));
+  if (!v.empty()) KP_HIP(hipMemcpyAsync(d, v.data(), sizeof(D) * v.size(), hipMemcpyHostToDevice, c->stream));
+  return d;
+}
 template <class T>
 T* upload1(kp_ctx* c, DevBuf& b, const std::vector<T>& v) {
-  return upload(c, b, v.data(), std::max<size_t>(1, v.size()));
+  return upload_list<T>(c, b, v);
 }
-int2* upload1(kp_ctx* c, DevBuf& b, const std::vector<CvI2>& v) {
-  return upload(c, b, reinterpret_cast<const int2*>(v.data()), std::max<size_t>(1, v.size()));
-}
-int4* upload1(kp_ctx* c, DevBuf& b, const std::vector<CvI4>& v) {
-  return upload(c, b, reinterpret_cast<const int4*>(v.data()), std::max<size_t>(1, v.size()));
-}
+int2* upload1(kp_ctx* c, DevBuf& b, const std::vector<CvI2>& v) { return upload_list<int2>(c, b, v); }
+int4* upload1(kp_ctx* c, DevBuf& b, const std::vector<CvI4>& v) { return upload_list<int4>(c, b, v); }
 template <class T>
 T* ensure_n(DevBuf& b, size_t n) {
   return reinterpret_cast<T*>(b.ensure(sizeof(T) * n));
@@ -869,6 +892,8 @@ struct CvDev {
   CvBits* enc_bits;
   float* gscale;
   std::vector<AttnPlan> step_plan;  // [T]
+  MarksDev marks;               // kp_posttrain_rank_marks
+  int32_t* mark_row = nullptr;  // [acts] the mark row an active entry's update also stores, or -1
   float *O, *dfc, *gk, *dflat, *dl, *wt;
   float s_in, s_fm;  // the masks' multipliers as the fused kernels take them (1: not drawn)
 };
@@ -1166,8 +1191,12 @@ void cv_update(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, const CvDev& 
                        c->d_bn_b, d.X, d.fpart);
     KP_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(kp_cv_update, dim3(st.na), dim3(256), 0, c->stream, kc, d.act + sp.act_off[t], d.Q, d.gk, d.dl,
-                     d.fpart, d.X, d.S1, d.S2, opt);
+  if (marks_at_step(d.marks, t))  // the step ends a marked epoch of one of its slots: the MARKS form instead
+    hipLaunchKernelGGL(kp_cv_update<true>, dim3(st.na), dim3(256), 0, c->stream, kc, d.act + sp.act_off[t], d.Q, d.gk,
+                       d.dl, d.fpart, d.X, d.S1, d.S2, opt, CvMarkArgs<true>{d.mark_row + sp.act_off[t], d.marks.X});
+  else
+    hipLaunchKernelGGL(kp_cv_update<false>, dim3(st.na), dim3(256), 0, c->stream, kc, d.act + sp.act_off[t], d.Q, d.gk,
+                       d.dl, d.fpart, d.X, d.S1, d.S2, opt, CvMarkArgs<false>{});
   KP_HIP(hipGetLastError());
 }
 
@@ -1278,6 +1307,23 @@ ProbeDev cv_probe_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk) {
   return pd;
 }
 
+// the marks' uploads and buffers (ahead of the step loop), as the probes': the shared ones,
+// the encoder sources (-mark row - 1, p) of every mark row and one chunk's encoder rows
+void cv_mark_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk, const CvStepPlan& sp,
+                        CvDev& d) {
+  const size_t enc_row = sizeof(float) * ((size_t)c->hidden + c->dim + c->dp);
+  d.marks = upload_marks(c, c->cv.marks, hp, bt, tk, d.X, enc_row);
+  if (d.marks.nm == 0) return;
+  const int nm = d.marks.nm;
+  std::vector<int2> src((size_t)d.marks.rows.n);
+  for (int s = 0; s < bt->n_slots; ++s)
+    for (int j = 0; j < nm; ++j) src[(size_t)s * nm + j] = make_int2(-(s * nm + j) - 1, bt->pred[3 * s + 1]);
+  upload(c, c->cv.mark_src, src.data(), src.size());
+  ensure_n<float>(c->cv.mark_q, (size_t)d.marks.rows.chunk * c->dp);
+  const std::vector<int32_t> mr = marks_act_rows(d.marks, sp.act_off, sp.T, [&](int i) { return sp.acts[i].slot; });
+  d.mark_row = upload(c, c->cv.mark_row, mr.data(), mr.size());
+}
+
 // rank: sigmoid(enc(x, R_p) . E_e), kelpie column, maximizer
 RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const TopkOut& tk, const CvDev& d,
                 const ProbeDev& pd) {
@@ -1302,6 +1348,15 @@ RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const TopkOut&
                          DP, pd.trip + 3 * (size_t)r0, m, pd.q, pd.t, pd.kcol);
       KP_HIP(hipGetLastError());
     });
+    // the marks: the mark rows through the encoder (eval mode) from the mark workspace, then
+    // the probe form on "row trip[3 r] of the mark workspace"
+    const ProbeDev& mr = d.marks.rows;
+    rank_probes(c, mr, RANK64_SIGMOID, [&](int r0, int m) {
+      encode_eval(c, m, c->cv.mark_src.as<int2>() + r0, d.marks.X, c->cv.mark_q.as<float>());
+      hipLaunchKernelGGL(kp_cv_rankq64<true>, dim3(m), dim3(64), 0, c->stream, c->cv.mark_q.as<float>(), d.marks.X, c->dE,
+                         K, DP, mr.trip + 3 * (size_t)r0, m, mr.q, mr.t, mr.kcol);
+      KP_HIP(hipGetLastError());
+    }, &c->rank.m_bits);
   } else {
     const int ld = round_up(K + 1, 4);
     float* dScores = ensure_n<float>(c->rank.scores, (size_t)ns * ld);
@@ -1324,6 +1379,7 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   require_probes(c, bt, tk, c->cv_rank64 != 0, "ConvE");
   KP_REQUIRE(hp->batch_size >= 1 && hp->epochs >= 0, "ConvE: bad hyper-parameters");
   require_trace(c, hp, bt, tk, "ConvE");
+  require_marks(hp, tk, c->cv_rank64 != 0, "ConvE");
   const CvConst kc = make_const(c, hp);
 
   CvStepPlan sp;
@@ -1336,6 +1392,7 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   CvDev d = cv_workspaces(c, bt, sp, xp);
   const ProbeDev pd = cv_probe_workspaces(c, bt, tk);
   const CvTraceDev tr = cv_trace_workspaces(c, bt, tk, sp);
+  cv_mark_workspaces(c, hp, bt, tk, sp, d);
   const double t_up = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipEventRecord(c->ev0, c->stream));
   const int nfp = cv_frozen_fc(c, kc, sp, d);
@@ -1349,6 +1406,7 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   if (tr.total > 0)  // with the other downloads, ahead of download_results' one wait
     KP_HIP(hipMemcpyAsync(tk.trace->out_loss, tr.loss, sizeof(float) * (size_t)tr.total, hipMemcpyDeviceToHost,
                           c->stream));
+  download_marks(c, bt, tk, d.marks);
   download_results(c, bt, d.X, rk, xp, tk, pd);
   if (g_host_times)
     std::fprintf(stderr, "[kp_cv] slots %d steps %d pairs %zu: plan %.2f ms, uploads %.2f ms, loop enqueue %.2f ms, "

@@ -13,6 +13,7 @@
 
 #include "kp_batch_check.hpp"
 #include "kp_common.hpp"
+#include "kp_marks_check.hpp"
 #include "kp_probe_check.hpp"
 #include "kp_trace_check.hpp"
 
@@ -175,14 +176,117 @@ inline ProbeDev upload_probes(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, 
 // rank the probe rows, chunk by chunk: `queries(r0, m)` enqueues the model's probe form of
 // its query kernel for the probes [r0, r0 + m) (their fp64 rows, target and kelpie column
 // scores into d.q / d.t / d.kcol), then the slots' own count runs over those rows (k = 0)
+// (`bits`: the chunk's filter bitmaps; the mark rows, ranked the same way, bring their own)
 template <class F>
-inline void rank_probes(kp_ctx* c, const ProbeDev& d, int act, F&& queries) {
+inline void rank_probes(kp_ctx* c, const ProbeDev& d, int act, F&& queries, DevBuf* bits = nullptr) {
   for (int r0 = 0; r0 < d.n; r0 += d.chunk) {
     const int m = std::min(d.chunk, d.n - r0);
     queries(r0, m);
     launch_rank_f64(c, m, d.q, d.t, d.kcol, d.po + r0, d.filt_off + r0, d.filt, d.target + r0, d.rank + r0, act, 0,
-                    nullptr, nullptr, &c->rank.p_bits);
+                    nullptr, nullptr, bits ? bits : &c->rank.p_bits);
   }
+}
+
+// kp_posttrain_rank_marks' request (kp_marks_check.hpp), checked after the batch, the probes
+// and the trace and before the first upload; like the lists and the probes the marks need the
+// fp64 rank
+inline void require_marks(const kp_hp* hp, const TopkOut& tk, bool rank64, const char* model) {
+  if (!tk.marks) return;
+  if (const char* why = kp_check_marks(hp, tk.marks))
+    throw KpError{KP_EINVAL, std::string(model) + ": marks: " + why};
+  if (!rank64)
+    throw KpError{KP_ENOTSUP, std::string(model) + ": marks need the fp64 rank (the fp32 rank switch is set)"};
+}
+
+// the marks on the device: the mark rows X [ns][nm][dp] in the family's workspace (every row
+// the padded x0 until a step captures it) and, in c->rank.m_*, the rows as rank rows in the
+// probes' layout -- row s * nm + j is (row, p, o) of slot s with the slot's filter list -- so
+// the probe form of the family's query kernel reads "row trip[3 r] of X" from the mark
+// workspace and rank_probes counts them
+struct MarksDev {
+  int nm = 0;         // marks per slot (0: no marks)
+  float* X = nullptr;
+  ProbeDev rows;      // n = ns * nm
+  KpMarkPlan plan;
+};
+
+// plan the marks, size every mark buffer, upload the rank rows and start every mark row as
+// its slot's padded x0 (dX, already uploaded on the stream); with the call's other uploads,
+// ahead of the step loop.  `ws`: the family's mark workspace; `extra_row_bytes` as upload_probes'
+inline MarksDev upload_marks(kp_ctx* c, DevBuf& ws, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk,
+                             const float* dX, size_t extra_row_bytes = 0) {
+  MarksDev d;
+  if (!tk.marks) return d;
+  const int ns = bt->n_slots, nm = tk.marks->n, n = ns * nm;
+  if (const char* why = kp_marks_plan(c->model, hp, ns, bt->row_off, bt->rows, tk.marks, d.plan))
+    throw KpError{KP_EINVAL, std::string("marks: ") + why};
+  KP_REQUIRE((int64_t)ns * nm <= INT32_MAX / 4, "marks: too many mark rows");
+  d.nm = nm;
+  d.X = reinterpret_cast<float*>(ws.ensure(sizeof(float) * (size_t)n * c->dp));
+  for (int j = 0; j < nm; ++j)
+    KP_HIP(hipMemcpy2DAsync(d.X + (size_t)j * c->dp, sizeof(float) * (size_t)nm * c->dp, dX, sizeof(float) * c->dp,
+                            sizeof(float) * c->dp, ns, hipMemcpyDeviceToDevice, c->stream));
+  std::vector<int32_t> trip((size_t)n * 3), po(n), fo((size_t)n + 1, 0);
+  int64_t nf = 0;
+  for (int s = 0; s < ns; ++s) nf += (int64_t)nm * (bt->filt_off[s + 1] - bt->filt_off[s]);
+  KP_REQUIRE(nf <= INT32_MAX, "marks: the mark rows' filter lists exceed 2^31 - 1 entries");
+  std::vector<int32_t> filt((size_t)std::max<int64_t>(1, nf));
+  for (int s = 0; s < ns; ++s)
+    for (int j = 0; j < nm; ++j) {
+      const size_t r = (size_t)s * nm + j;
+      trip[3 * r] = (int32_t)r;
+      trip[3 * r + 1] = bt->pred[3 * s + 1];
+      trip[3 * r + 2] = po[r] = bt->pred[3 * s + 2];
+      const int len = bt->filt_off[s + 1] - bt->filt_off[s];
+      if (len > 0) std::memcpy(&filt[fo[r]], bt->filt + bt->filt_off[s], sizeof(int32_t) * len);
+      fo[r + 1] = fo[r] + len;
+    }
+  const int nwords = (c->n_ent + 1 + 31) / 32;
+  int forced = 0;
+  if (const char* a = std::getenv("KP_MARKS_CHUNK")) forced = std::max(0, std::atoi(a));
+  ProbeDev& p = d.rows;
+  p.n = n;
+  p.chunk = kp_probe_chunk(n, sizeof(double) * c->dp + sizeof(uint32_t) * nwords + extra_row_bytes, PROBE_WS_BYTES,
+                           PROBE_GROUP, forced);
+  p.trip = upload(c, c->rank.m_trip, trip.data(), trip.size());
+  p.po = upload(c, c->rank.m_po, po.data(), po.size());
+  p.filt_off = upload(c, c->rank.m_filt_off, fo.data(), fo.size());
+  p.filt = upload(c, c->rank.m_filt, filt.data(), filt.size());
+  p.target = reinterpret_cast<float*>(c->rank.m_target.ensure(sizeof(float) * (size_t)n));
+  p.rank = reinterpret_cast<int64_t*>(c->rank.m_rank.ensure(sizeof(int64_t) * (size_t)n));
+  p.q = reinterpret_cast<double*>(c->rank.m_q64.ensure(sizeof(double) * (size_t)p.chunk * c->dp));
+  p.t = reinterpret_cast<double*>(c->rank.m_t64.ensure(sizeof(double) * 2 * (size_t)p.chunk));
+  p.kcol = p.t + p.chunk;
+  (void)c->rank.m_bits.ensure(sizeof(uint32_t) * (size_t)p.chunk * nwords);
+  // the uploads above read host vectors that end with this call: pageable copies are staged
+  // before hipMemcpyAsync returns
+  return d;
+}
+
+// per entry of a host-driven step loop's active lists (entry i of step t is slot slot_of(i)):
+// the mark row its update also stores, or -1
+template <class SlotOf>
+inline std::vector<int32_t> marks_act_rows(const MarksDev& d, const std::vector<int>& act_off, int T, SlotOf&& slot_of) {
+  std::vector<int32_t> rows(std::max(1, act_off.empty() ? 0 : act_off[T]), -1);
+  for (int t = 0; t < T && t < d.plan.T; ++t)
+    for (int i = act_off[t]; i < act_off[t + 1]; ++i) rows[i] = kp_marks_row_at(d.plan, slot_of(i), t);
+  return rows;
+}
+
+// does step t capture a mark row
+inline bool marks_at_step(const MarksDev& d, int t) {
+  return d.nm > 0 && t < d.plan.T && d.plan.step_off[t + 1] > d.plan.step_off[t];
+}
+
+// enqueue the downloads of the marks' results, ahead of download_results' one wait
+inline void download_marks(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, const MarksDev& d) {
+  if (d.nm == 0) return;
+  const size_t n = (size_t)d.rows.n;
+  KP_HIP(hipMemcpyAsync(tk.marks->out_score, d.rows.target, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipMemcpyAsync(tk.marks->out_rank, d.rows.rank, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
+  if (tk.marks->out_x)
+    KP_HIP(hipMemcpy2DAsync(tk.marks->out_x, sizeof(float) * c->dim, d.X, sizeof(float) * c->dp, sizeof(float) * c->dim,
+                            n, hipMemcpyDeviceToHost, c->stream));
 }
 
 // the tail of a call: enqueue the downloads of the kelpie rows (when out_x is set), the

@@ -143,6 +143,25 @@ struct TeTraceArgs<true> {
   const int32_t* off;  // [ns + 1]
   float* loss;         // [off[ns]]
 };
+// kp_posttrain_rank_marks: one pointer to the call's mark header (TeMarkHdr, then per epoch e
+// of the call the mark taken when it ends, or -1), read where it is used so that nothing of it
+// stays in registers across the item loop.  Without the flag the struct is empty and
+// kp_te_posttrain is what it was.
+struct TeMarkHdr {
+  float* rows;  // the mark rows [slots][n][dp]
+  int32_t n, pad;
+};
+constexpr int TE_MARK_HDR = sizeof(TeMarkHdr) / sizeof(int32_t);
+template <bool MARKS>
+struct TeMarkArgs {};
+template <>
+struct TeMarkArgs<true> {
+  // TeMarkHdr | mark_of_epoch [epochs].  volatile for one purpose only: it keeps the loads
+  // at their use, once per epoch, where hoisted loads would hold registers across the item
+  // loop; nothing else writes the header during the launch.  The register counts of DESIGN
+  // section 5 rest on it: compare `make resources` again after a compiler change
+  const volatile int32_t* hdr;
+};
 __device__ __forceinline__ float sq4(float4 v) { return fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, v.w * v.w))); }
 // the TRACE forms' per-wave partials [hinge | squares], summed by one thread in wave order
 template <int NW>
@@ -301,14 +320,18 @@ __device__ __forceinline__ void te_item(const int4* rec, const float* __restrict
 // TRACE (kp_posttrain_rank_trace): every step also stores its loss before the update --
 // the waves' fp64 hinge and squared-row partials meet in LDS with the gradient partials and
 // one thread sums them in wave order, rounds once to fp32 and stores
-template <int VPL, int NT, bool STAGED, bool L1, bool TRACE = false>  // VPL float4 per lane: dp <= 256 * VPL
+// MARKS (kp_posttrain_rank_marks): behind the barrier that ends a marked epoch's last step, x
+// goes from LDS to the slot's mark row of that epoch as well (plain vector stores; the next
+// step only reads x until its own closing barriers, so no barrier is added)
+template <int VPL, int NT, bool STAGED, bool L1, bool TRACE = false, bool MARKS = false>  // VPL float4 per lane: dp <= 256 * VPL
 __global__ __launch_bounds__(NT) void kp_te_posttrain(int n_ent, int dp, int d, const float* __restrict__ E,
                                                           const float* __restrict__ Rt,
                                                           const TeSlot* __restrict__ slots,
                                                           const int32_t* __restrict__ slot_of_block,
                                                           const int32_t* __restrict__ rows,
                                                           const int32_t* __restrict__ rng, TeHp hp,
-                                                          float* __restrict__ X, TeTraceArgs<TRACE> tr) {
+                                                          float* __restrict__ X, TeTraceArgs<TRACE> tr,
+                                                          TeMarkArgs<MARKS> mk) {
   constexpr int TE_NW = NT / 64;  // waves
   constexpr int PF = 4;           // prefetched draw words per thread (STAGED: 3 R <= PF * NT)
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -478,6 +501,14 @@ __global__ __launch_bounds__(NT) void kp_te_posttrain(int n_ent, int dp, int d, 
       if (tid == 0) loop_max_s = 0;
 #endif
     }
+    if constexpr (MARKS) {
+      const int mark_j = mk.hdr[TE_MARK_HDR + e];  // block-uniform; a mark of epoch 0 is the x0 its row starts as
+      if (mark_j >= 0) {
+        const volatile TeMarkHdr* h = reinterpret_cast<const volatile TeMarkHdr*>(mk.hdr);
+        float* mrow = h->rows + ((size_t)slot * h->n + mark_j) * dp;
+        if (tid < dp) mrow[tid] = xs[tid];  // dp <= NT, as Adam's update above has it
+      }
+    }
   }
   for (int i = tid; i < dp; i += NT) x[i] = xs[i];
 #ifdef KP_TE_STAMPS
@@ -611,6 +642,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   require_topk(tk, c->te_rank64 != 0, "TransE");
   require_probes(c, bt, tk, c->te_rank64 != 0, "TransE");
   require_trace(c, hp, bt, tk, "TransE");
+  require_marks(hp, tk, c->te_rank64 != 0, "TransE");
   // before the first upload: the buffers below are sized by DP, the kernels hold DP / 256 float4 per lane
   KP_REQUIRE(DP <= 512, "TransE: dimension > 512 not supported");
   KP_REQUIRE(hp->neg_ratio >= 1 && hp->batch_size >= 1 && hp->epochs >= 0, "TransE: bad hyper-parameters");
@@ -629,6 +661,17 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   const int64_t nrng = bt->rng_off[ns];
   int32_t* dRng = upload(c, c->te.rng, bt->rng, (size_t)std::max<int64_t>(1, nrng));
   const ProbeDev pd = upload_probes(c, bt, tk);
+  // kp_posttrain_rank_marks: the mark rows (each the padded x0 until its epoch ends) and the epochs
+  const MarksDev md = upload_marks(c, c->te.marks, hp, bt, tk, dX);
+  TeMarkArgs<true> mkd{nullptr};
+  if (md.nm > 0) {
+    std::vector<int32_t> hdr(TE_MARK_HDR + (size_t)hp->epochs, -1);
+    const TeMarkHdr h{md.X, md.nm, 0};
+    std::memcpy(hdr.data(), &h, sizeof(h));
+    for (int j = 0; j < md.nm; ++j)
+      if (tk.marks->epochs[j] > 0) hdr[TE_MARK_HDR + tk.marks->epochs[j] - 1] = j;
+    mkd.hdr = upload(c, c->te.mark_ep, hdr.data(), hdr.size());
+  }
   // kp_posttrain_rank_trace: the offsets and the losses, with the call's other uploads
   const int n_trace = tk.trace ? tk.trace->trace_off[ns] : 0;
   TeTraceArgs<true> trd{nullptr, nullptr};
@@ -671,12 +714,18 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   KP_HIP(hipEventRecord(ea, c->stream));
   const int vpl = (DP + 255) / 256;
 #define TE_LAUNCH(V, T, ST, L)                                                                                      \
-  if (tk.trace)                                                                                                    \
+  if (md.nm > 0 && tk.trace)                                                                                       \
+    hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L, true, true>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP,  \
+                       c->dim, c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, trd, mkd);                         \
+  else if (md.nm > 0)                                                                                              \
+    hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L, false, true>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP, \
+                       c->dim, c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, TeTraceArgs<false>{}, mkd);        \
+  else if (tk.trace)                                                                                                \
     hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L, true>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP, c->dim, \
-                       c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, trd);                                      \
+                       c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, trd, TeMarkArgs<false>{});                 \
   else                                                                                                             \
     hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP, c->dim,      \
-                       c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, TeTraceArgs<false>{})
+                       c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, TeTraceArgs<false>{}, TeMarkArgs<false>{})
 #define TE_NORM(V, T, ST)       \
   if (l1) {                     \
     TE_LAUNCH(V, T, ST, true);  \
@@ -724,6 +773,12 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
                          pd.trip + 3 * (size_t)r0, m, pd.q, pd.t, pd.kcol, l1 ? 1 : 0);
       KP_HIP(hipGetLastError());
     });
+    // the marks: the probe form reads row trip[3 r] of the mark workspace instead of a slot's row
+    rank_probes(c, md.rows, l1 ? RANK64_DIST1 : RANK64_DIST, [&](int r0, int m) {
+      hipLaunchKernelGGL(kp_te_rankq64<true>, dim3(m), dim3(64), 0, c->stream, md.X, c->dR, c->dE, c->n_ent, DP,
+                         md.rows.trip + 3 * (size_t)r0, m, md.rows.q, md.rows.t, md.rows.kcol, l1 ? 1 : 0);
+      KP_HIP(hipGetLastError());
+    }, &c->rank.m_bits);
   } else {
     float* dScores = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)ns * ld));
     launch_te_scores(c, ns, dH, dRl, dX, dScores, ld, c->n_ent);
@@ -733,6 +788,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   if (n_trace > 0)  // with the other downloads, ahead of download_results' one wait
     KP_HIP(hipMemcpyAsync(tk.trace->out_loss, trd.loss, sizeof(float) * (size_t)n_trace, hipMemcpyDeviceToHost,
                           c->stream));
+  download_marks(c, bt, tk, md);
   download_results(c, bt, dX, rk, xp, tk, pd);
   float ms_all = 0.f, ms_hot = 0.f;
   KP_HIP(hipEventElapsedTime(&ms_all, c->ev0, c->ev1));

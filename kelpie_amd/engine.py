@@ -180,8 +180,10 @@ class PostTrainingEngine(RelevanceEngine):
         self._probe_req = None
         self._cur_probes = None
         self._trace = False
+        self._marks = None
 
     _trace = False
+    _marks = None  # the epochs after which every post-training is also ranked (marks), int32 array or None
     TOP_K_MAX = 32  # kp_posttrain_rank_topk's largest k
     _top_k = 0
     PROBES_MAX = 64  # probes per slot
@@ -257,6 +259,24 @@ class PostTrainingEngine(RelevanceEngine):
         if not isinstance(on, (bool, np.bool_)):
             raise TypeError(f"trace must be a bool, got {on!r}")
         self._trace = bool(on)
+
+    @property
+    def marks(self):
+        """The epochs after which every post-training is also scored and ranked (None: the
+        default): one strictly increasing list of 1 to 16 epochs in [0, the hp's epochs].
+        Mark ``e`` of a post-training is what the device returns for it on the same batch with
+        ``epochs = e``: the kelpie row after ``e`` epochs, ranked as ``get_triple_results``
+        ranks the final row (post_training_engine.py:101-125; ConvE in eval mode) -- a shorter
+        run reads a prefix of the same draws.  It is not the reference started with
+        ``epochs = e`` from the same seed: that run draws fewer numbers per post-training, so
+        every post-training after the first starts elsewhere in the random stream.  Every
+        slot's result gains ``"marks"``: [{"epoch", "score", "rank"}].  The relevances, the
+        draws and the batches are those of ``marks`` = None."""
+        return None if self._marks is None else [int(e) for e in self._marks]
+
+    @marks.setter
+    def marks(self, epochs):
+        self._marks = None if epochs is None else _lib.check_marks(epochs, int(self._kp_hp.epochs))
 
     @property
     def top_k(self):
@@ -578,6 +598,9 @@ class PostTrainingEngine(RelevanceEngine):
         if self._trace and self._sharded():
             # before any draw, as the lists and the probes
             raise NotImplementedError("trace with a slot sharding: the losses are not gathered across ranks")
+        if self._marks is not None and self._sharded():
+            # before any draw, as the lists, the probes and the trace
+            raise NotImplementedError("marks with a slot sharding: their results are not gathered across ranks")
         self._sched = None  # this batch's natively assembled slots (TransE), made on first use
         if self._sharded():
             # ComplEx / ConvE: every rank owns one contiguous run of the batch's slots, so it
@@ -777,7 +800,12 @@ class PostTrainingEngine(RelevanceEngine):
         traced = self._trace
         if traced:
             kw["trace"] = True
+        marks = self._marks
+        if marks is not None:
+            kw["marks"] = marks
         out = ctx.posttrain_rank(self._kp_hp, *packed, **kw)
+        if marks is not None:  # the last element; what is before it is the call's without marks
+            (m_score, m_rank, _), out = out[-1], out[:-1]
         score, rank = out[0], out[1]
         if k:
             top_ids, top_scores = out[3]
@@ -785,6 +813,10 @@ class PostTrainingEngine(RelevanceEngine):
         if fill:
             for i, s in enumerate(slots):
                 s.result = {"target_score": float(score[i]), "target_rank": int(rank[i])}
+            if marks is not None:
+                for i, s in enumerate(slots):
+                    s.result["marks"] = [{"epoch": int(e), "score": float(m_score[i][j]), "rank": int(m_rank[i][j])}
+                                         for j, e in enumerate(marks)]
             if traced:
                 for s, loss in zip(slots, out[-1]):
                     s.result["loss"] = [float(v) for v in loss]
@@ -929,6 +961,53 @@ class PostTrainingEngine(RelevanceEngine):
         finally:
             self._trace = old
         return [self._tr_rule(rel, det) for rel, det in zip(rels, self.last_results)]
+
+    @staticmethod
+    def _mk_side(res, epochs):
+        """One post-training of a curve report: its target score and rank and its marks
+        [{"epoch", "score", "rank"}], None when the result was cached without these marks."""
+        marks = res.get("marks")
+        if marks is not None and [m["epoch"] for m in marks] != epochs:
+            marks = None
+        return {"score": res["target_score"], "rank": res["target_rank"],
+                "marks": None if marks is None else [dict(m) for m in marks]}
+
+    def _rel_of(self, base, pt):
+        """The engine's relevance formula on one (base, post-trained) pair of {"score", "rank"}."""
+        raise NotImplementedError
+
+    def _curve(self, base, post):
+        """The relevance formula at every mark of a (base, post) pair of _mk_side results."""
+        if base["marks"] is None or post["marks"] is None:
+            return None
+        return [self._rel_of(b, p) for b, p in zip(base["marks"], post["marks"])]
+
+    def _mk_rule(self, relevance, detail, epochs):
+        raise NotImplementedError
+
+    def compute_curves(self, pred, rules, epochs):
+        """``compute_relevance_batch(pred, rules)`` -- the same schedule, draws, batches and
+        relevances, the generators left where it leaves them -- that also reports what every
+        post-training had reached after the ``epochs`` (:attr:`marks`): per rule
+        ``{"relevance", "epochs", "curve", "base", "post"}`` (the sufficient engine:
+        ``{"relevance", "epochs", "curve", "conversions": [{"entity", "base", "post"}, ...]}``
+        with a ``curve`` of means), ``base`` / ``post`` = ``{"score", "rank", "marks":
+        [{"epoch", "score", "rank"}, ...]}``.  ``curve[j]`` is the engine's own relevance
+        formula on the base and post results at mark j: what an engine with ``epochs`` =
+        ``epochs[j]`` returns for the same draws per post-training (not the reference started
+        with that budget from the same seed, whose later post-trainings draw from elsewhere in
+        the stream).  No post-training runs for the sake of a mark: a base result cached
+        without these marks reports ``"marks": None`` and a ``curve`` of None.  TypeError /
+        ValueError for a bad ``epochs``, before any draw."""
+        ep = _lib.check_marks(epochs, int(self._kp_hp.epochs))
+        old = self._marks
+        self._marks = ep
+        try:
+            rels = self.compute_relevance_batch(pred, rules)
+        finally:
+            self._marks = old
+        ep = [int(e) for e in ep]
+        return [self._mk_rule(rel, det, ep) for rel, det in zip(rels, self.last_results)]
 
     def _schedule_multi(self, items, checkpoints):
         raise NotImplementedError
@@ -1382,6 +1461,19 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
         pt, base = detail
         return {"relevance": relevance, "base": self._tr_side(base), "post": self._tr_side(pt)}
 
+    def _rel_of(self, base, pt):
+        # _finalize_multi's formula, in its scalar form (the same bits)
+        if self.model.is_minimizer():
+            score_worsening = pt["score"] - base["score"]
+        else:
+            score_worsening = base["score"] - pt["score"]
+        return float(np.float32(pt["rank"] - base["rank"]) + np.float32(_sigmoid(score_worsening)))
+
+    def _mk_rule(self, relevance, detail, epochs):
+        pt, base = detail
+        b, p = self._mk_side(base, epochs), self._mk_side(pt, epochs)
+        return {"relevance": relevance, "epochs": list(epochs), "curve": self._curve(b, p), "base": b, "post": p}
+
 
 class SufficientPostTrainingEngine(PostTrainingEngine):
     """post_training_engine.py:160-207."""
@@ -1401,6 +1493,25 @@ class SufficientPostTrainingEngine(PostTrainingEngine):
         return {"relevance": relevance,
                 "conversions": [{"entity": int(e), "base": self._tr_side(base), "post": self._tr_side(pt)}
                                 for e, (pt, base) in zip(self.entities_to_convert, detail)]}
+
+    def _rel_of(self, base, pt):
+        # _finalize_multi's formula for one conversion entity
+        rank_improvement = base["rank"] - pt["rank"]
+        if self.model.is_minimizer():
+            score_improvement = base["score"] - pt["score"]
+        else:
+            score_improvement = pt["score"] - base["score"]
+        rel = float(np.float32(np.float32(rank_improvement) + np.float32(_sigmoid(score_improvement))))
+        return rel / float(base["rank"])
+
+    def _mk_rule(self, relevance, detail, epochs):
+        conv = [{"entity": int(e), "base": self._mk_side(base, epochs), "post": self._mk_side(pt, epochs)}
+                for e, (pt, base) in zip(self.entities_to_convert, detail)]
+        curves = [self._curve(c["base"], c["post"]) for c in conv]
+        curve = None
+        if curves and all(c is not None for c in curves):  # the mean over the conversions, as the relevance
+            curve = [sum(c[j] for c in curves) / len(curves) for j in range(len(epochs))]
+        return {"relevance": relevance, "epochs": list(epochs), "curve": curve, "conversions": conv}
 
     def __init__(self, model, dataset, hp, rng=None):
         super().__init__(model, dataset, hp, rng)
