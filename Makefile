@@ -11,7 +11,7 @@ LIB := kelpie_amd/libkelpie_hip.so
 
 all: $(LIB)
 
-build/%.o: kelpie_amd/csrc/%.hip kelpie_amd/csrc/kp_common.hpp kelpie_amd/csrc/kp_attn.hpp kelpie_amd/csrc/kp_attn_plan.hpp kelpie_amd/csrc/kp_attn3.hpp kelpie_amd/csrc/kp_cv_fused.hpp kelpie_amd/csrc/kp_posttrain.hpp kelpie_amd/csrc/kp_batch_check.hpp kelpie_amd/csrc/kp_probe_check.hpp kelpie_amd/csrc/kp_trace_check.hpp kelpie_amd/csrc/kp_marks_check.hpp kelpie_amd/csrc/kp_cx_plan.hpp kelpie_amd/csrc/kp_cv_plan.hpp include/kelpie_hip.h
+build/%.o: kelpie_amd/csrc/%.hip $(wildcard kelpie_amd/csrc/*.hpp) include/kelpie_hip.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -62,75 +62,24 @@ build/san/host_tsan: $(SAN_SRC) include/kelpie_hip.h
 	@mkdir -p build/san
 	$(CXX) $(SAN_FLAGS) -fsanitize=thread $(SAN_SRC) -o $@
 
-# the post-training batch check (kp_batch_check.hpp, no HIP) alone in
-# tests/native/batch_check_driver.cpp; run by tests/test_batch_check.py (CPU suite)
+# The pure-host headers (no HIP) alone in a driver of their own, tests/native/X_driver.cpp,
+# plain (build/san/X) and under the host sanitizers (build/san/X_asan); each pair is run by
+# tests/test_X.py (CPU suite), or by hand: make X X_asan
+#   batch_check  the post-training batch check (kp_batch_check.hpp; its target is batch_asan)
+#   attn_plan    the attention planners (kp_attn_plan.hpp)
+#   step_plan    the post-training step planners (kp_cx_plan.hpp, kp_cv_plan.hpp)
+#   probe_check  the probes' check, rank rows and chunking (kp_probe_check.hpp)
+#   trace_check  the trace's step counts and check (kp_trace_check.hpp)
+#   marks_check  the epoch marks' check, plan and rank rows (kp_marks_check.hpp)
+DRIVERS := batch_check attn_plan step_plan probe_check trace_check marks_check
+DRIVER_DEP := $(wildcard kelpie_amd/csrc/kp_*_check.hpp kelpie_amd/csrc/kp_*_plan.hpp) include/kelpie_hip.h
+$(DRIVERS) $(DRIVERS:%=%_asan): %: build/san/%
 batch_asan: build/san/batch_check_asan
-build/san/batch_check_asan: tests/native/batch_check_driver.cpp kelpie_amd/csrc/kp_batch_check.hpp include/kelpie_hip.h
-	@mkdir -p build/san
-	$(CXX) -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
-
-# the attention planners (kp_attn_plan.hpp, no HIP) alone in tests/native/attn_plan_driver.cpp,
-# plain and under the host sanitizers; run by tests/test_attn_plan.py (CPU suite)
-attn_plan: build/san/attn_plan
-attn_plan_asan: build/san/attn_plan_asan
-build/san/attn_plan: tests/native/attn_plan_driver.cpp kelpie_amd/csrc/kp_attn_plan.hpp
-	@mkdir -p build/san
-	$(CXX) -O2 -std=c++17 -Wall $< -o $@
-build/san/attn_plan_asan: tests/native/attn_plan_driver.cpp kelpie_amd/csrc/kp_attn_plan.hpp
+build/san/%_asan: tests/native/%_driver.cpp $(DRIVER_DEP)
 	@mkdir -p build/san
 	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
-
-# the post-training step planners (kp_cx_plan.hpp, kp_cv_plan.hpp, no HIP) alone in
-# tests/native/step_plan_driver.cpp, plain and under the host sanitizers; run by
-# tests/test_step_plan.py (CPU suite)
-STEP_PLAN_DEP := tests/native/step_plan_driver.cpp kelpie_amd/csrc/kp_cx_plan.hpp kelpie_amd/csrc/kp_cv_plan.hpp include/kelpie_hip.h
-step_plan: build/san/step_plan
-step_plan_asan: build/san/step_plan_asan
-build/san/step_plan: $(STEP_PLAN_DEP)
+build/san/%: tests/native/%_driver.cpp $(DRIVER_DEP)
 	@mkdir -p build/san
 	$(CXX) -O2 -std=c++17 -Wall $< -o $@
-build/san/step_plan_asan: $(STEP_PLAN_DEP)
-	@mkdir -p build/san
-	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
 
-# the probes' check and chunking (kp_probe_check.hpp, no HIP) alone in
-# tests/native/probe_check_driver.cpp, plain and under the host sanitizers; run by
-# tests/test_probe_check.py (CPU suite)
-PROBE_CHECK_DEP := tests/native/probe_check_driver.cpp kelpie_amd/csrc/kp_probe_check.hpp include/kelpie_hip.h
-probe_check: build/san/probe_check
-probe_check_asan: build/san/probe_check_asan
-build/san/probe_check: $(PROBE_CHECK_DEP)
-	@mkdir -p build/san
-	$(CXX) -O2 -std=c++17 -Wall $< -o $@
-build/san/probe_check_asan: $(PROBE_CHECK_DEP)
-	@mkdir -p build/san
-	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
-
-# the trace's step counts and check (kp_trace_check.hpp, no HIP) alone in
-# tests/native/trace_check_driver.cpp, plain and under the host sanitizers; run by
-# tests/test_trace_check.py (CPU suite)
-TRACE_CHECK_DEP := tests/native/trace_check_driver.cpp kelpie_amd/csrc/kp_trace_check.hpp include/kelpie_hip.h
-trace_check: build/san/trace_check
-trace_check_asan: build/san/trace_check_asan
-build/san/trace_check: $(TRACE_CHECK_DEP)
-	@mkdir -p build/san
-	$(CXX) -O2 -std=c++17 -Wall $< -o $@
-build/san/trace_check_asan: $(TRACE_CHECK_DEP)
-	@mkdir -p build/san
-	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
-
-# the epoch marks' check and plan (kp_marks_check.hpp, no HIP) alone in
-# tests/native/marks_check_driver.cpp, plain and under the host sanitizers; run by
-# tests/test_marks_check.py (CPU suite)
-MARKS_CHECK_DEP := tests/native/marks_check_driver.cpp kelpie_amd/csrc/kp_marks_check.hpp kelpie_amd/csrc/kp_trace_check.hpp include/kelpie_hip.h
-marks_check: build/san/marks_check
-marks_check_asan: build/san/marks_check_asan
-build/san/marks_check: $(MARKS_CHECK_DEP)
-	@mkdir -p build/san
-	$(CXX) -O2 -std=c++17 -Wall $< -o $@
-build/san/marks_check_asan: $(MARKS_CHECK_DEP)
-	@mkdir -p build/san
-	$(CXX) -O1 -g -std=c++17 -Wall -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined $< -o $@
-
-.PHONY: asan tsan batch_asan attn_plan attn_plan_asan step_plan step_plan_asan probe_check probe_check_asan \
-        trace_check trace_check_asan marks_check marks_check_asan
+.PHONY: asan tsan batch_asan $(DRIVERS) $(DRIVERS:%=%_asan)

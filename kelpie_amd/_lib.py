@@ -9,6 +9,7 @@ import ctypes as C
 import os
 import sys
 import weakref
+from typing import NamedTuple
 
 import numpy as np
 
@@ -396,6 +397,29 @@ def conve_masks(torch_state: np.ndarray, rows_per_step, segs) -> np.ndarray:
     check(lib().kp_rng_conve_masks(_ptr(torch_state), torch_state.size, len(rows), _ptr(rows), len(e), _ptr(e),
                                    _ptr(k), _ptr(out)))
     return out[:words]
+
+
+class RankResult(NamedTuple):
+    """The fields of a ``posttrain_rank`` tuple by name; a request not made is None."""
+    score: object
+    rank: object
+    x: object
+    top: object = None     # (ids, scores)
+    probes: object = None  # (scores, ranks)
+    loss: object = None    # one array per slot
+    marks: object = None   # (scores, ranks, rows or None)
+
+
+def split_rank_result(out, topk=0, probes=None, trace=False, marks=None) -> RankResult:
+    """``Context.posttrain_rank``'s tuple (of a context or of a stand-in that follows its
+    convention) by name, given the requests the call was made with: the optional elements
+    follow (scores, ranks, rows) in the order topk, probes, trace, marks, each only when asked
+    for."""
+    asked = (bool(topk), probes is not None, bool(trace), marks is not None)
+    if len(out) != 3 + sum(asked):
+        raise ValueError(f"posttrain_rank returned {len(out)} elements for {sum(asked)} optional requests")
+    rest = iter(out[3:])
+    return RankResult(*out[:3], *(next(rest) if a else None for a in asked))
 
 
 class Context:

@@ -3,9 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "kp_common.hpp"
-#include "kp_marks_check.hpp"
-#include "kp_trace_check.hpp"
+#include "kp_posttrain.hpp"
 
 int cx_pick_db(int dim);
 
@@ -204,60 +202,48 @@ int kp_ctx_destroy(kp_ctx* c) {
   return KP_OK;
 }
 
-// kp_posttrain_rank, kp_posttrain_rank_topk (tk.k == 0: no lists) and kp_posttrain_rank_probes
-// (tk.probes null or empty: no probes).  The model's function checks k, the list outputs and
-// the probes itself, after the batch check and before its first upload.
-static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk) {
+// Every kp_posttrain_rank* entry point: the request is what the entry point takes beyond
+// kp_posttrain_rank (k == 0: no lists; a null pointer: no probes / trace / marks).  The
+// model's function checks the request itself (require_request), after the batch check and
+// before its first upload; a batch without slots is checked here and runs nothing.
+static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k = 0, int32_t* out_ids = nullptr,
+                               float* out_scores = nullptr, const kp_probes* probes = nullptr,
+                               const kp_trace* trace = nullptr, const kp_marks* marks = nullptr) {
   if (!c || !hp || !b) return KP_EINVAL;
+  PostReq rq;
+  rq.k = k;
+  rq.ids = out_ids;
+  rq.scores = out_scores;
+  rq.probes = probes;
+  rq.trace = trace;
+  rq.marks = marks;
   return guarded(c, [&] {
     KP_REQUIRE(b->n_slots >= 0, "kp_posttrain_rank: negative n_slots");
-    if (b->n_slots == 0) {
-      KP_REQUIRE(tk.k >= 0 && tk.k <= 32, "kp_posttrain_rank_topk: k must be in [0, 32]");
-      KP_REQUIRE(tk.n_probes() == 0, "kp_posttrain_rank_probes: probes without a slot");
-      static const char* const names[] = {"TransE", "ComplEx", "ConvE", "DistMult"};
-      if (tk.trace) {  // the same rule and message as with slots (kp_trace_check.hpp handles n_slots == 0)
-        if (const char* why = kp_check_trace(c->model, hp, 0, b->row_off, b->rows, tk.trace))
-          throw KpError{KP_EINVAL, std::string(names[c->model]) + ": trace: " + why};
-      }
-      if (tk.marks) {  // the same rule and message as with slots
-        if (const char* why = kp_check_marks(hp, tk.marks))
-          throw KpError{KP_EINVAL, std::string(names[c->model]) + ": marks: " + why};
-      }
-      return;
-    }
+    if (b->n_slots == 0) return require_request(c, hp, b, rq, true, kp_model_name(c->model));
     KP_REQUIRE(b->x0 && b->row_off && b->pred && b->filt_off && b->out_score && b->out_rank,
                "kp_posttrain_rank: missing buffer");
     KP_HIP(hipSetDevice(c->device));
     switch (c->model) {
-      case KP_MODEL_COMPLEX: complex_posttrain_rank(c, hp, b, tk); break;
-      case KP_MODEL_DISTMULT: distmult_posttrain_rank(c, hp, b, tk); break;
-      case KP_MODEL_TRANSE: transe_posttrain_rank(c, hp, b, tk); break;
-      case KP_MODEL_CONVE: conve_posttrain_rank(c, hp, b, tk); break;
+      case KP_MODEL_COMPLEX: complex_posttrain_rank(c, hp, b, rq); break;
+      case KP_MODEL_DISTMULT: distmult_posttrain_rank(c, hp, b, rq); break;
+      case KP_MODEL_TRANSE: transe_posttrain_rank(c, hp, b, rq); break;
+      case KP_MODEL_CONVE: conve_posttrain_rank(c, hp, b, rq); break;
     }
   });
 }
 
-int kp_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b) { return posttrain_rank_call(c, hp, b, {}); }
+int kp_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b) { return posttrain_rank_call(c, hp, b); }
 
 int kp_posttrain_rank_topk(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k, int32_t* out_ids,
                            float* out_scores) {
-  TopkOut tk;
-  tk.k = k;
-  tk.ids = out_ids;
-  tk.scores = out_scores;
-  return posttrain_rank_call(c, hp, b, tk);
+  return posttrain_rank_call(c, hp, b, k, out_ids, out_scores);
 }
 
 // get_triple_results (post_training_engine.py:101-125) on every slot's post-trained model,
 // for its probes as well as its own target
 int kp_posttrain_rank_probes(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k, int32_t* out_ids,
                              float* out_scores, const kp_probes* probes) {
-  TopkOut tk;
-  tk.k = k;
-  tk.ids = out_ids;
-  tk.scores = out_scores;
-  tk.probes = probes;
-  return posttrain_rank_call(c, hp, b, tk);
+  return posttrain_rank_call(c, hp, b, k, out_ids, out_scores, probes);
 }
 
 // kp_posttrain_rank_probes with the optimizer's loss of every step of every slot
@@ -265,13 +251,7 @@ int kp_posttrain_rank_probes(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int3
 // pairwise_ranking_optimizer.py:165-203, bce_optimizer.py:167-208)
 int kp_posttrain_rank_trace(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k, int32_t* out_ids,
                             float* out_scores, const kp_probes* probes, const kp_trace* trace) {
-  TopkOut tk;
-  tk.k = k;
-  tk.ids = out_ids;
-  tk.scores = out_scores;
-  tk.probes = probes;
-  tk.trace = trace;
-  return posttrain_rank_call(c, hp, b, tk);
+  return posttrain_rank_call(c, hp, b, k, out_ids, out_scores, probes, trace);
 }
 
 // kp_posttrain_rank_trace with every slot's score, rank and row after the marked epochs:
@@ -279,14 +259,7 @@ int kp_posttrain_rank_trace(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32
 int kp_posttrain_rank_marks(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k, int32_t* out_ids,
                             float* out_scores, const kp_probes* probes, const kp_trace* trace,
                             const kp_marks* marks) {
-  TopkOut tk;
-  tk.k = k;
-  tk.ids = out_ids;
-  tk.scores = out_scores;
-  tk.probes = probes;
-  tk.trace = trace;
-  tk.marks = marks;
-  return posttrain_rank_call(c, hp, b, tk);
+  return posttrain_rank_call(c, hp, b, k, out_ids, out_scores, probes, trace, marks);
 }
 
 // the steps of every slot (kp_trace_check.hpp): host work only
@@ -330,7 +303,7 @@ int kp_convertible(kp_ctx* c, int32_t n, const int32_t* heads, int32_t rel, int3
     const int ld = c->n_ent;
     std::vector<int32_t> rels(chunk, rel), fo(chunk + 1);
     DevBuf bS, bH, bR, bFo, bF, bK;
-    float* dS = reinterpret_cast<float*>(bS.ensure(sizeof(float) * (size_t)chunk * ld));
+    float* dS = ensure_n<float>(bS, (size_t)chunk * ld);
     const bool minimizer = (c->model == KP_MODEL_TRANSE);
     for (int i0 = 0; i0 < n; i0 += chunk) {
       const int m = std::min(chunk, n - i0);
@@ -427,7 +400,7 @@ int kp_predict_tails(kp_ctx* c, int32_t n, const int32_t* triples, const int32_t
     const bool minimizer = (c->model == KP_MODEL_TRANSE);
     std::vector<int32_t> h(chunk), r(chunk), o(chunk), fo(chunk + 1);
     DevBuf bS, bH, bR, bO, bFo, bF, bT, bK;
-    float* dS = reinterpret_cast<float*>(bS.ensure(sizeof(float) * (size_t)chunk * ld));
+    float* dS = ensure_n<float>(bS, (size_t)chunk * ld);
     for (int i0 = 0; i0 < n; i0 += chunk) {
       const int m = std::min(chunk, n - i0);
       for (int j = 0; j < m; ++j) {
@@ -441,8 +414,8 @@ int kp_predict_tails(kp_ctx* c, int32_t n, const int32_t* triples, const int32_t
       int32_t* dO = upload(c, bO, o.data(), (size_t)m);
       int32_t* dFo = upload(c, bFo, fo.data(), (size_t)m + 1);
       int32_t* dF = upload(c, bF, filt + filt_off[i0], (size_t)std::max(1, fo[m]));
-      float* dT = reinterpret_cast<float*>(bT.ensure(sizeof(float) * (size_t)m));
-      int64_t* dK = reinterpret_cast<int64_t*>(bK.ensure(sizeof(int64_t) * (size_t)m));
+      float* dT = ensure_n<float>(bT, (size_t)m);
+      int64_t* dK = ensure_n<int64_t>(bK, (size_t)m);
       switch (c->model) {
         case KP_MODEL_COMPLEX:
         case KP_MODEL_DISTMULT: complex_scores_dev(c, m, dH, dR, dS, ld); break;

@@ -113,7 +113,31 @@ struct ImageBufs {
 };
 KP_WS_COMPLETE(ImageBufs);
 
-// the rank of the post-trained rows (every *_posttrain_rank; kp_posttrain.hpp fills it).
+// join the buffer lists of a struct's own members and of its member structs
+template <size_t... N>
+inline auto kp_join(const std::array<DevBuf*, N>&... lists) {
+  std::array<DevBuf*, (N + ...)> out{};
+  size_t i = 0;
+  ((std::copy(lists.begin(), lists.end(), out.begin() + i), i += N), ...);
+  return out;
+}
+
+// one set of rank rows (kp_posttrain.hpp's RankRows: upload_rank_rows fills it, rank_rows
+// counts it): the rows' (row, p, o) [n][3], objects [n], filter CSR and results [n]; one chunk
+// of rows' fp64 queries [chunk][dp], target | kelpie column scores [2][chunk] and filter
+// bitmaps; ConvE: the rows' encoder sources (-row - 1, p) [n] and one chunk's encoder output
+// [chunk][dp]
+struct RankRowsWs {
+  DevBuf trip, po, filt_off, filt;
+  DevBuf target, rank;
+  DevBuf q64, t64, bits;
+  DevBuf enc_src, enc_q;
+  auto all() { return std::array{&trip, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &bits, &enc_src, &enc_q}; }
+};
+KP_WS_COMPLETE(RankRowsWs);
+
+// what every *_posttrain_rank shares (kp_posttrain.hpp fills it): the rank of the
+// post-trained rows, the two sets of rank rows and the trace.
 // Two borrowers outside a post-training call, kept so that a context allocates what it
 // always did: complex_all_scores uploads its heads / relations into pred / po, and
 // transe_all_scores writes its score matrix into scores.
@@ -130,25 +154,16 @@ struct RankWs {
   // final lists [ns][k]
   DevBuf cand_key, cand_col;
   DevBuf top_ids, top_scores;
-  // kp_posttrain_rank_probes (kp_posttrain.hpp fills them): the probes' (slot, p, o) [n][3],
-  // objects [n], filter CSR and results [n]; one chunk of probe rows' fp64 queries
-  // [chunk][dp], target | kelpie column scores [2][chunk] and filter bitmaps.  The slots' own
-  // buffers above are not reused: their downloads are still pending when the probes run
-  DevBuf p_trip, p_po, p_filt_off, p_filt;
-  DevBuf p_target, p_rank;
-  DevBuf p_q64, p_t64, p_bits;
-  // kp_posttrain_rank_marks (kp_posttrain.hpp fills them): the mark rows' (row, p, o) [m][3],
-  // objects [m], filter CSR and results [m], m = slots * marks; one chunk of rows' fp64
-  // queries, target | kelpie column scores and filter bitmaps, as the probes'
-  DevBuf m_trip, m_po, m_filt_off, m_filt;
-  DevBuf m_target, m_rank;
-  DevBuf m_q64, m_t64, m_bits;
+  DevBuf tr_off, tr_loss;  // kp_posttrain_rank_trace: the trace offsets [ns + 1] and the losses [steps]
+  // kp_posttrain_rank_probes: row r is probe r, (slot, p, o), on the slots' kelpie rows; and
+  // kp_posttrain_rank_marks: row s * marks + j is (row, p, o) of slot s on the family's mark
+  // workspace [ns][marks][dp], with the slot's filter list.  Neither set reuses the slots'
+  // buffers above or the other's: the earlier downloads are still pending when a set ranks
+  RankRowsWs probes, marks;
   auto all() {
-    return std::array{&pred,     &po,       &filt_off, &filt,       &target,     &rank,   &q64,
-                      &t64,      &scores,   &bits,     &cand_key,   &cand_col,   &top_ids, &top_scores,
-                      &p_trip,   &p_po,     &p_filt_off, &p_filt,   &p_target,   &p_rank, &p_q64,
-                      &p_t64,    &p_bits,   &m_trip,   &m_po,       &m_filt_off, &m_filt, &m_target,
-                      &m_rank,   &m_q64,    &m_t64,    &m_bits};
+    return kp_join(std::array{&pred, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &scores, &bits, &cand_key,
+                              &cand_col, &top_ids, &top_scores, &tr_off, &tr_loss},
+                   probes.all(), marks.all());
   }
 };
 KP_WS_COMPLETE(RankWs);
@@ -164,17 +179,16 @@ struct ComplexWs {
   DevBuf am, al, ao;               // attention split results (max, sum, output)
   DevBuf qs;                       // the step's queries [nq][dp]
   DevBuf score_q, score_out;       // complex_scores_dev's queries, complex_all_scores' scores
-  // kp_posttrain_rank_trace: the step's fp64 loss term per item [items], the frozen rows'
-  // regulariser factors [n_ent] / [n_rel2] (fp64, once per batch), the trace offsets
-  // [ns + 1] and the losses [steps]
-  DevBuf tr_term, tr_fe, tr_fr, tr_off, tr_loss;
+  // kp_posttrain_rank_trace: the step's fp64 loss term per item [items] and the frozen rows'
+  // regulariser factors [n_ent] / [n_rel2] (fp64, once per batch)
+  DevBuf tr_term, tr_fe, tr_fr;
   // kp_posttrain_rank_marks: the mark rows [ns][marks][dp] and, per entry of acts, the mark
   // row its update also stores (-1: none)
   DevBuf marks, mark_row;
   auto all() {
     return std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
                       &tsum, &qpair, &lsef, &am, &al, &ao, &qs, &score_q, &score_out, &tr_term, &tr_fe, &tr_fr,
-                      &tr_off, &tr_loss, &marks, &mark_row};
+                      &marks, &mark_row};
   }
 };
 KP_WS_COMPLETE(ComplexWs);
@@ -185,10 +199,9 @@ struct TranseWs {
   DevBuf slots, rows, rng;  // TeSlot, the batch's training rows and draws
   DevBuf order;             // slots, longest first
   DevBuf heads, rels;       // score queries: the ranked triples' (-1, relation), and transe_all_scores' pairs
-  DevBuf tr_off, tr_loss;   // kp_posttrain_rank_trace: the trace offsets [ns + 1] and the losses [steps]
   DevBuf marks, mark_ep;    // kp_posttrain_rank_marks: the mark rows [ns][marks][dp]; the header and the epochs' marks
   auto all() {
-    return std::array{&x, &slots, &rows, &rng, &order, &heads, &rels, &tr_off, &tr_loss, &marks, &mark_ep};
+    return std::array{&x, &slots, &rows, &rng, &order, &heads, &rels, &marks, &mark_ep};
   }
 };
 KP_WS_COMPLETE(TranseWs);
@@ -216,20 +229,18 @@ struct ConveWs {
   DevBuf o;                       // attention output [rows * splits][dp]
   DevBuf dfc, gk, dflat, dl;      // backward: dL/dfc, g . x, dL/dflat (unfused), lhs image gradient
   DevBuf rank_src;                // the ranked triples' encoder sources
-  DevBuf probe_src, probe_q;      // a chunk of probes' encoder sources (-slot - 1, p) and outputs [chunk][dp]
-  // kp_posttrain_rank_trace: the trace offsets [ns + 1] and losses [steps]; a step's rows
-  // [rows][dp], one chunk's logits [chunk][ld] and the rows' summed BCE terms (fp64)
-  DevBuf tr_off, tr_loss, tr_rows, tr_scores, tr_rowloss;
-  // kp_posttrain_rank_marks: the mark rows [ns][marks][dp], per entry of the active lists the
-  // mark row its update also stores (-1: none), and a chunk of mark rows' encoder sources
-  // (-row - 1, p) and outputs [chunk][dp]
-  DevBuf marks, mark_row, mark_src, mark_q;
+  // kp_posttrain_rank_trace: a step's rows [rows][dp], one chunk's logits [chunk][ld] and the
+  // rows' summed BCE terms (fp64)
+  DevBuf tr_rows, tr_scores, tr_rowloss;
+  // kp_posttrain_rank_marks: the mark rows [ns][marks][dp] and, per entry of the active lists,
+  // the mark row its update also stores (-1: none).  (The probes' and the mark rows' encoder
+  // sources and outputs are with their rank rows, RankRowsWs.)
+  DevBuf marks, mark_row;
   auto all() {
     return std::array{&x, &s1, &s2, &kinst, &finst, &acts, &tails, &keep_bits, &fcf, &fpairs, &flat, &slab,
                       &relu, &g3, &sr_src, &sr_rng, &psr, &relu_s, &slab_l, &mid, &map_l, &map_m, &gs, &dls,
                       &q, &enc_src, &enc_bits, &fchunks, &fpart, &gscale, &o, &dfc, &gk, &dflat, &dl, &rank_src,
-                      &probe_src, &probe_q, &tr_off, &tr_loss, &tr_rows, &tr_scores, &tr_rowloss, &marks,
-                      &mark_row, &mark_src, &mark_q};
+                      &tr_rows, &tr_scores, &tr_rowloss, &marks, &mark_row};
   }
 };
 KP_WS_COMPLETE(ConveWs);
@@ -323,10 +334,16 @@ struct kp_ctx : ImageBufs {
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// room for n elements of T in `b`
+template <class T>
+static inline T* ensure_n(DevBuf& b, size_t n) {
+  return reinterpret_cast<T*>(b.ensure(sizeof(T) * n));
+}
+
 // upload helper
 template <class T>
 static inline T* upload(kp_ctx* c, DevBuf& b, const T* src, size_t n) {
-  T* d = reinterpret_cast<T*>(b.ensure(n * sizeof(T)));
+  T* d = ensure_n<T>(b, n);
   if (n) KP_HIP(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
   return d;
 }
@@ -359,9 +376,17 @@ __device__ __forceinline__ float wave_max(float v) {
 // ----------------------------------------------------------------------------
 // entry points implemented per model family
 // ----------------------------------------------------------------------------
-// kp_posttrain_rank_topk's request: the k best unmasked columns of every slot into the
-// caller's ids / scores [n_slots][k]; k == 0 (no lists) is kp_posttrain_rank
-struct TopkOut {
+// the names the families' messages carry, by kp_model_desc.model
+inline const char* kp_model_name(int model) {
+  static const char* const names[] = {"TransE", "ComplEx", "ConvE", "DistMult"};
+  return names[model];
+}
+
+// what a post-training call asks for besides its slots' scores and ranks (kp_api.hip builds
+// it from the entry point's arguments; all absent: kp_posttrain_rank)
+struct PostReq {
+  // kp_posttrain_rank_topk: the k best unmasked columns of every slot into the caller's
+  // ids / scores [n_slots][k]; k == 0: no lists
   int k = 0;
   int32_t* ids = nullptr;
   float* scores = nullptr;
@@ -374,9 +399,9 @@ struct TopkOut {
   const kp_marks* marks = nullptr;
   int n_marks() const { return marks ? marks->n : 0; }
 };
-void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
+void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const PostReq& rq = {});
 // kp_complex.hip, product policy
-void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
+void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const PostReq& rq = {});
 void complex_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rels, float* out);
 // scores of n (head, rel) pairs over the frozen entities into a device buffer [n][ld]
 // (complex_*: ComplEx and DistMult contexts, by the context's product)
@@ -385,9 +410,9 @@ void transe_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* 
 void conve_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* d_rels, float* d_out, int ld);
 void launch_convertible_reduce(kp_ctx* c, int n, const float* d_scores, int ld, int obj, const int32_t* d_fo,
                                const int32_t* d_f, int minimizer, uint8_t* d_keep);
-void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
+void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const PostReq& rq = {});
 void transe_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rels, float* out);
-void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const TopkOut& tk = {});
+void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const PostReq& rq = {});
 void conve_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rels, float* out);
 // ConvE encoder output (eval mode) of n (lhs, rel) pairs -> [n][dp] (criage_first_step, conve.py:102-124)
 void conve_encode_dev(kp_ctx* c, int n, const int2* d_src, float* d_out);

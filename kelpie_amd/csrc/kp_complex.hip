@@ -61,7 +61,6 @@ __device__ __forceinline__ double cx_q64(const float* __restrict__ lhs, const fl
 // ----------------------------------------------------------------------------
 struct CxProd {  // ComplEx (complex.py:59-112)
   static constexpr int G = 2;
-  static constexpr const char* name = "ComplEx";
   static int extent(int dim) { return dim / 2; }
   static __device__ __forceinline__ float q(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
                                             int w) {
@@ -89,7 +88,6 @@ struct CxProd {  // ComplEx (complex.py:59-112)
 
 struct DmProd {  // DistMult (distmult.py:38-68): plain [d] rows, q = lhs * rel
   static constexpr int G = 1;
-  static constexpr const char* name = "DistMult";
   static int extent(int dim) { return dim; }
   static __device__ __forceinline__ float q(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
                                             int w) {
@@ -682,14 +680,12 @@ void launch_attn(kp_ctx* c, bool with_o, const float* Q, int nq, const AttnPlan&
   KP_HIP(hipGetLastError());
 }
 
-// kp_posttrain_rank_trace's device side (loss == nullptr: no trace)
-struct CxTraceDev {
+// kp_posttrain_rank_trace's device side (loss == nullptr: no trace): the common part and
+// ComplEx's own workspaces
+struct CxTraceDev : TraceDev {
   double *term = nullptr, *freg_e = nullptr, *freg_r = nullptr;
   const int32_t* targets = nullptr;
   const int2* pairs = nullptr;
-  int32_t* off = nullptr;  // [ns + 1]
-  float* loss = nullptr;   // [total]
-  int total = 0;
 };
 
 template <int DB, class Prod>
@@ -735,11 +731,11 @@ void launch_rankq64(kp_ctx* c, const float* X, const int32_t* pred, int n, doubl
   KP_HIP(hipGetLastError());
 }
 
-// the probe form: the probes [r0, r0 + m) of pd into its chunk buffers
+// the probe form: the rows [r0, r0 + m) of a set of rank rows into its chunk buffers
 template <int DB, class Prod>
-void launch_probeq64(kp_ctx* c, const float* X, const ProbeDev& pd, int r0, int m) {
-  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod, true>), dim3(m), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
-                     Prod::extent(c->dim), pd.trip + 3 * (size_t)r0, m, pd.q, pd.t, pd.kcol);
+void launch_probeq64(kp_ctx* c, const RankRows& rr, int r0, int m) {
+  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod, true>), dim3(m), dim3(64), 0, c->stream, rr.X, c->dR, c->dE, c->n_ent,
+                     Prod::extent(c->dim), rr.trip + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol);
   KP_HIP(hipGetLastError());
 }
 
@@ -774,7 +770,7 @@ struct CxDev {
   Rank64Dev r64;
   int32_t* pred;
   RankDev rk;
-  ProbeDev probes;
+  RankRows probes;
   CxTraceDev trace;
   MarksDev marks;
   int32_t* mark_row = nullptr;  // [acts] the mark row an active entry's update also stores, or -1
@@ -789,13 +785,13 @@ static_assert(sizeof(CxI4) == sizeof(int4) && alignof(CxI4) == alignof(int4), "C
 inline const int2* as_dev(const CxI2* p) { return reinterpret_cast<const int2*>(p); }
 inline const int4* as_dev(const CxI4* p) { return reinterpret_cast<const int4*>(p); }
 
-CxDev cx_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk, const CxStepPlan& sp,
+CxDev cx_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq, const CxStepPlan& sp,
                     std::vector<float>& xp) {
   const int ns = bt->n_slots, DP = c->dp;
   CxDev d;
   d.X = upload_x0(c, c->cx.x, bt, xp);
-  d.S1 = reinterpret_cast<float*>(c->cx.s1.ensure(sizeof(float) * (size_t)ns * DP));
-  d.S2 = reinterpret_cast<float*>(c->cx.s2.ensure(sizeof(float) * (size_t)ns * DP));
+  d.S1 = ensure_n<float>(c->cx.s1, (size_t)ns * DP);
+  d.S2 = ensure_n<float>(c->cx.s2, (size_t)ns * DP);
   KP_HIP(hipMemsetAsync(d.S1, 0, sizeof(float) * (size_t)ns * DP, c->stream));
   KP_HIP(hipMemsetAsync(d.S2, 0, sizeof(float) * (size_t)ns * DP, c->stream));
   d.plans = upload(c, c->cx.plans, sp.plans.data(), sp.plans.size());
@@ -806,33 +802,31 @@ CxDev cx_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   // (empty without a step, epochs == 0: upload() then only sizes the buffer)
   d.stepq = upload(c, c->cx.stepq, as_dev(sp.stepq.data()), sp.stepq.size());
   d.stept = upload(c, c->cx.stept, as_dev(sp.stept.data()), sp.stept.size());
-  d.contrib = reinterpret_cast<float*>(c->cx.contrib.ensure(sizeof(float) * (size_t)std::max(1, sp.max_items) * DP));
+  d.contrib = ensure_n<float>(c->cx.contrib, (size_t)std::max(1, sp.max_items) * DP);
   const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
-  d.tsum = reinterpret_cast<float*>(c->cx.tsum.ensure(sizeof(float) * (size_t)std::max(npq, 1) * DP));
-  d.qpair = reinterpret_cast<float*>(c->cx.qpair.ensure(sizeof(float) * (size_t)std::max(npairs, 1) * DP));
-  d.lsef = reinterpret_cast<float*>(c->cx.lsef.ensure(sizeof(float) * (size_t)std::max(npairs, 1)));
+  d.tsum = ensure_n<float>(c->cx.tsum, (size_t)std::max(npq, 1) * DP);
+  d.qpair = ensure_n<float>(c->cx.qpair, (size_t)std::max(npairs, 1) * DP);
+  d.lsef = ensure_n<float>(c->cx.lsef, (size_t)std::max(npairs, 1));
 
   // the ranking's inputs and buffers now, ahead of the step loop: an upload from pageable
   // memory after the loop waited for the whole loop on the device, so the rank kernels
   // were enqueued only then (a host round trip per batch with the context idle)
   d.r64 = rank64_buffers(c, ns);
   d.pred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
-  d.rk = upload_rank_inputs(c, bt, tk);
-  d.probes = upload_probes(c, bt, tk);
+  d.rk = upload_rank_inputs(c, bt, rq);
+  d.probes = upload_probes(c, bt, rq, d.X);
   // kp_posttrain_rank_marks: the mark rows (each the padded x0 until a step captures it)
-  d.marks = upload_marks(c, c->cx.marks, hp, bt, tk, d.X);
+  d.marks = upload_marks(c, c->cx.marks, hp, bt, rq, d.X);
   if (d.marks.nm > 0) {
     const std::vector<int32_t> mr = marks_act_rows(d.marks, sp.act_off, sp.T, [&](int i) { return sp.acts[i].x; });
     d.mark_row = upload(c, c->cx.mark_row, mr.data(), mr.size());
   }
-  if (tk.trace) {  // the trace's offsets and workspaces, with the call's other uploads
+  if (rq.trace) {  // the trace's offsets and workspaces, with the call's other uploads
     CxTraceDev& t = d.trace;
-    t.total = tk.trace->trace_off[ns];
-    t.off = upload(c, c->cx.tr_off, tk.trace->trace_off, (size_t)ns + 1);
-    t.loss = reinterpret_cast<float*>(c->cx.tr_loss.ensure(sizeof(float) * (size_t)std::max(1, t.total)));
-    t.term = reinterpret_cast<double*>(c->cx.tr_term.ensure(sizeof(double) * (size_t)std::max(1, sp.max_items)));
-    t.freg_e = reinterpret_cast<double*>(c->cx.tr_fe.ensure(sizeof(double) * (size_t)c->n_ent));
-    t.freg_r = reinterpret_cast<double*>(c->cx.tr_fr.ensure(sizeof(double) * (size_t)c->n_rel2));
+    static_cast<TraceDev&>(t) = upload_trace(c, bt, rq);
+    t.term = ensure_n<double>(c->cx.tr_term, (size_t)std::max(1, sp.max_items));
+    t.freg_e = ensure_n<double>(c->cx.tr_fe, (size_t)c->n_ent);
+    t.freg_r = ensure_n<double>(c->cx.tr_fr, (size_t)c->n_rel2);
     t.targets = d.tg;
     t.pairs = d.pairs;
   }
@@ -872,10 +866,10 @@ void cx_preloop(kp_ctx* c, const CxStepPlan& sp, CxDev& d, float reg_w, int reg_
     if (nq > 0) attn_plan_note(c, d.step_plan[t], nq, true);
     att_rows = std::max(att_rows, (size_t)nq * d.step_plan[t].wk.n_parts);
   }
-  d.am = reinterpret_cast<float*>(c->cx.am.ensure(sizeof(float) * att_rows));
-  d.al = reinterpret_cast<float*>(c->cx.al.ensure(sizeof(float) * att_rows));
-  d.ao = reinterpret_cast<float*>(c->cx.ao.ensure(sizeof(float) * att_rows * DP));
-  d.qs = reinterpret_cast<float*>(c->cx.qs.ensure(sizeof(float) * (size_t)std::max(sp.max_nq, 1) * DP));
+  d.am = ensure_n<float>(c->cx.am, att_rows);
+  d.al = ensure_n<float>(c->cx.al, att_rows);
+  d.ao = ensure_n<float>(c->cx.ao, att_rows * DP);
+  d.qs = ensure_n<float>(c->cx.qs, (size_t)std::max(sp.max_nq, 1) * DP);
   if (npairs > 0) {
     hipLaunchKernelGGL(kp_cx_qpair<Prod>, dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP, Prod::extent(c->dim),
                        d.pairs, npairs, d.qpair);
@@ -940,18 +934,14 @@ int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxD
 // KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time before the first upload (checks
 // and planning), up to the last launch enqueued, and waiting for the device
 template <class Prod>
-void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
-  const std::string who = Prod::name;
+void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq) {
+  const std::string who = kp_model_name(c->model);
   const double t_in = g_host_times ? host_ms() : 0.0;
   const int ns = bt->n_slots;
   KP_REQUIRE(hp->batch_size > 0 && hp->epochs >= 0, who + ": bad batch_size/epochs");
   // every id is checked before it indexes a host vector or a device table, as in every
   // model family (kp_batch_check.hpp)
-  require_batch(c, bt, Prod::name);
-  require_topk(tk, true, Prod::name);
-  require_probes(c, bt, tk, true, Prod::name);
-  require_trace(c, hp, bt, tk, Prod::name);
-  require_marks(hp, tk, true, Prod::name);
+  require_request(c, hp, bt, rq, true, kp_model_name(c->model));
   const CxOpt opt = make_opt(hp, who);
 
   CxStepPlan sp;
@@ -960,7 +950,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   const double t_plan = g_host_times ? host_ms() : 0.0;
 
   std::vector<float> xp;
-  CxDev d = cx_workspaces(c, hp, bt, tk, sp, xp);
+  CxDev d = cx_workspaces(c, hp, bt, rq, sp, xp);
   cx_preloop<Prod>(c, sp, d, opt.reg_w, opt.reg_n2);
 
   // loop-interval events, destroyed on every exit path (a KP_HIP / KP_REQUIRE below throws)
@@ -983,21 +973,16 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOu
   // (launch_rank_f64: at the reference init the target's neighbours are ~1e-5 relative away)
   CX_DISPATCH(c->dp / 16, launch_rankq64<DB, Prod>(c, d.X, d.pred, ns, d.r64.q, d.r64.t, d.r64.kcol));
   launch_rank_f64(c, ns, d.r64.q, d.r64.t, d.r64.kcol, d.rk.po, d.rk.filt_off, d.rk.filt, d.rk.target, d.rk.rank,
-                  RANK64_DOT, tk.k, d.rk.top_ids, d.rk.top_scores);
-  rank_probes(c, d.probes, RANK64_DOT, [&](int r0, int m) {
-    CX_DISPATCH(c->dp / 16, launch_probeq64<DB, Prod>(c, d.X, d.probes, r0, m));
-  });
-  // the marks: the probe form reads row trip[3 r] of the mark workspace instead of a slot's row
-  rank_probes(c, d.marks.rows, RANK64_DOT, [&](int r0, int m) {
-    CX_DISPATCH(c->dp / 16, launch_probeq64<DB, Prod>(c, d.marks.X, d.marks.rows, r0, m));
-  }, &c->rank.m_bits);
+                  RANK64_DOT, rq.k, d.rk.top_ids, d.rk.top_scores);
+  // the probes on the slots' rows, then the marks on the mark workspace
+  const auto probe_queries = [c](const RankRows& rr, int r0, int m) {
+    CX_DISPATCH(c->dp / 16, launch_probeq64<DB, Prod>(c, rr, r0, m));
+  };
+  rank_rows(c, d.probes, RANK64_DOT, probe_queries);
+  rank_rows(c, d.marks.rows, RANK64_DOT, probe_queries);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
 
-  if (d.trace.total > 0)  // with the other downloads, ahead of download_results' one wait
-    KP_HIP(hipMemcpyAsync(tk.trace->out_loss, d.trace.loss, sizeof(float) * (size_t)d.trace.total,
-                          hipMemcpyDeviceToHost, c->stream));
-  download_marks(c, bt, tk, d.marks);
-  const double t_enq = download_results(c, bt, d.X, d.rk, xp, tk, d.probes);
+  const double t_enq = download_results(c, bt, d.X, d.rk, xp, rq, d.probes, d.trace, d.marks);
   const double t_done = g_host_times ? host_ms() : 0.0;
   if (g_host_times)
     std::fprintf(stderr,
@@ -1017,18 +1002,18 @@ int cx_pick_db(int dim) {
   return -1;
 }
 
-void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
-  posttrain_rank<CxProd>(c, hp, bt, tk);
+void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq) {
+  posttrain_rank<CxProd>(c, hp, bt, rq);
 }
-void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
-  posttrain_rank<DmProd>(c, hp, bt, tk);
+void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq) {
+  posttrain_rank<DmProd>(c, hp, bt, rq);
 }
 
 // scores of (head, relation) pairs against every entity; ComplEx and DistMult contexts
 void complex_scores_dev(kp_ctx* c, int n, const int32_t* dh, const int32_t* dr, float* dS, int ld) {
   if (n <= 0) return;
   const int DP = c->dp;
-  float* dQ = reinterpret_cast<float*>(c->cx.score_q.ensure(sizeof(float) * (size_t)n * DP));
+  float* dQ = ensure_n<float>(c->cx.score_q, (size_t)n * DP);
   if (c->model == KP_MODEL_DISTMULT)
     hipLaunchKernelGGL(kp_cx_scoreq<DmProd>, dim3(n), dim3(128), 0, c->stream, c->dE, c->dR, DP,
                        DmProd::extent(c->dim), dh, dr, n, dQ);
@@ -1045,7 +1030,7 @@ void complex_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* r
   // rather than two of their own, which keeps the context's device allocations as they were
   int32_t* dh = upload(c, c->rank.pred, heads, (size_t)n);
   int32_t* dr = upload(c, c->rank.po, rels, (size_t)n);
-  float* dS = reinterpret_cast<float*>(c->cx.score_out.ensure(sizeof(float) * (size_t)n * c->n_ent));
+  float* dS = ensure_n<float>(c->cx.score_out, (size_t)n * c->n_ent);
   complex_scores_dev(c, n, dh, dr, dS, c->n_ent);
   KP_HIP(hipMemcpyAsync(out, dS, sizeof(float) * (size_t)n * c->n_ent, hipMemcpyDeviceToHost, c->stream));
   KP_HIP(hipStreamSynchronize(c->stream));

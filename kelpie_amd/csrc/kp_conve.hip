@@ -762,8 +762,8 @@ CvConst make_const(kp_ctx* c, const kp_hp* hp) {
 void encode_eval(kp_ctx* c, int n, const int2* dsrc, const float* dX, float* dQ) {
   if (n <= 0) return;
   CvConst k = make_const(c, nullptr);
-  float* dflat = reinterpret_cast<float*>(c->cv.flat.ensure(sizeof(float) * (size_t)n * c->hidden));
-  float* dfc = reinterpret_cast<float*>(c->cv.slab.ensure(sizeof(float) * (size_t)n * c->dim));
+  float* dflat = ensure_n<float>(c->cv.flat, (size_t)n * c->hidden);
+  float* dfc = ensure_n<float>(c->cv.slab, (size_t)n * c->dim);
   KP_CONV_FWD(dim3(n), dim3(256), 0, c->stream, n, dsrc, c->dE, dX, c->dR, k, c->d_conv_w,
                      c->d_conv_b, c->d_bn_a, c->d_bn_b, nullptr, nullptr, dflat);
   KP_HIP(hipGetLastError());
@@ -802,13 +802,13 @@ static void conve_fused_images(kp_ctx* c, const __bf16** fw, const __bf16** bw) 
 static void conve_shared_setup(kp_ctx* c, const __bf16* cvf_fw, const float* dX, const int32_t* dBits) {
   if (c->cv_shared_ready) return;
   constexpr int NB_L = 24;
-  float* wtm = reinterpret_cast<float*>(c->cv_wtm.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NMID));
+  float* wtm = ensure_n<float>(c->cv_wtm, (size_t)c->dim * kpcvf::NMID);
   hipLaunchKernelGGL(kpcvf::kp_cv_mid_wt, dim3((c->dim * kpcvf::NMID + 255) / 256), dim3(256), 0, c->stream,
                      c->d_fc_w, c->dim, wtm);
   KP_HIP(hipGetLastError());
-  float* wtl = reinterpret_cast<float*>(c->cv_wtl.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NLHS));
-  float* wlc = reinterpret_cast<float*>(c->cv_wlc.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NLHS));
-  float* wfm = reinterpret_cast<float*>(c->cv_wfm.ensure(sizeof(float) * (size_t)c->dim * kpcvf::NMID));
+  float* wtl = ensure_n<float>(c->cv_wtl, (size_t)c->dim * kpcvf::NLHS);
+  float* wlc = ensure_n<float>(c->cv_wlc, (size_t)c->dim * kpcvf::NLHS);
+  float* wfm = ensure_n<float>(c->cv_wfm, (size_t)c->dim * kpcvf::NMID);
   const int nw = (kpcvf::NLHS + kpcvf::NMID) * c->dim;
   hipLaunchKernelGGL(kpcvf::kp_cv_lhs_wt, dim3((nw + 255) / 256), dim3(256), 0, c->stream, c->d_fc_w, c->dim, wlc,
                      wtl, wfm);
@@ -818,14 +818,14 @@ static void conve_shared_setup(kp_ctx* c, const __bf16* cvf_fw, const float* dX,
   for (int r = 0; r < nr; ++r) rs[r] = make_int2(0, r);
   DevBuf bs, bo;
   int2* dRs = upload(c, bs, rs.data(), rs.size());
-  float* sl = reinterpret_cast<float*>(bo.ensure(sizeof(float) * (size_t)NB_L * nr * c->dim));
+  float* sl = ensure_n<float>(bo, (size_t)NB_L * nr * c->dim);
   const int g = NB_L * ((nr + kpcvf::MT - 1) / kpcvf::MT);
   hipLaunchKernelGGL(kpcvf::kp_cv_fwd_fused<false>, dim3(g), dim3(512), kpcvf::FWD_LDS, c->stream, nr, dRs, c->dE,
                      dX, c->dR, c->dp, c->d_conv_w, c->d_conv_b, c->d_bn_a, c->d_bn_b, cvf_fw, nullptr, c->dim,
                      nullptr, dBits, 1.0f, 1.0f, sl, nullptr, 8 * (kpcvf::MID_Y + 2),
                      8 * (kpcvf::FR - kpcvf::MID_Y - 2), NB_L, 2);
   KP_HIP(hipGetLastError());
-  float* tr = reinterpret_cast<float*>(c->cv_trel.ensure(sizeof(float) * (size_t)nr * c->dim));
+  float* tr = ensure_n<float>(c->cv_trel, (size_t)nr * c->dim);
   hipLaunchKernelGGL(kpcvf::kp_cv_slab_sum, dim3((nr * c->dim + 255) / 256), dim3(256), 0, c->stream, nr, NB_L,
                      c->dim, sl, tr);
   KP_HIP(hipGetLastError());
@@ -847,7 +847,7 @@ static_assert(sizeof(CvI4) == sizeof(int4) && alignof(CvI4) == alignof(int4), "C
 template <class D, class T>
 D* upload_list(kp_ctx* c, DevBuf& b, const std::vector<T>& v) {
   static_assert(sizeof(D) == sizeof(T), "the list's device type has the host type's layout");
-  D* d = reinterpret_cast<D*>(b.ensure(sizeof(D) * std::max<size_t>(1, v.size())));
+  D* d = ensure_n<D>(b, std::max<size_t>(1, v.size()));
   if (!v.empty()) KP_HIP(hipMemcpyAsync(d, v.data(), sizeof(D) * v.size(), hipMemcpyHostToDevice, c->stream));
   return d;
 }
@@ -857,10 +857,6 @@ T* upload1(kp_ctx* c, DevBuf& b, const std::vector<T>& v) {
 }
 int2* upload1(kp_ctx* c, DevBuf& b, const std::vector<CvI2>& v) { return upload_list<int2>(c, b, v); }
 int4* upload1(kp_ctx* c, DevBuf& b, const std::vector<CvI4>& v) { return upload_list<int4>(c, b, v); }
-template <class T>
-T* ensure_n(DevBuf& b, size_t n) {
-  return reinterpret_cast<T*>(b.ensure(sizeof(T) * n));
-}
 
 // the device side of one call (c->cv): the plan's uploads (cv_workspaces), the frozen-head
 // pairs' FC rows (cv_frozen_fc) and the step workspaces (cv_step_workspaces)
@@ -892,6 +888,7 @@ struct CvDev {
   CvBits* enc_bits;
   float* gscale;
   std::vector<AttnPlan> step_plan;  // [T]
+  RankRows probes;              // kp_posttrain_rank_probes
   MarksDev marks;               // kp_posttrain_rank_marks
   int32_t* mark_row = nullptr;  // [acts] the mark row an active entry's update also stores, or -1
   float *O, *dfc, *gk, *dflat, *dl, *wt;
@@ -1200,31 +1197,26 @@ void cv_update(kp_ctx* c, const CvConst& kc, const CvStepPlan& sp, const CvDev& 
   KP_HIP(hipGetLastError());
 }
 
-// kp_posttrain_rank_trace's device side (loss == nullptr: no trace): the trace offsets and
-// losses, the step's rows, one chunk's logits [chunk][ld] and the rows' summed terms
+// kp_posttrain_rank_trace's device side (loss == nullptr: no trace): the common part, and
+// ConvE's own: the step's rows, one chunk's logits [chunk][ld] and the rows' summed terms
 constexpr size_t TRACE_WS_BYTES = (size_t)64 << 20;  // a chunk's logits, as TOPK_WS_BYTES
-struct CvTraceDev {
-  int32_t* off = nullptr;
-  float* loss = nullptr;
+struct CvTraceDev : TraceDev {
   float *rows = nullptr, *scores = nullptr;
   double* rowloss = nullptr;
-  int total = 0, chunk = 0, ld = 0;
+  int chunk = 0, ld = 0;
 };
 
-CvTraceDev cv_trace_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, const CvStepPlan& sp) {
+CvTraceDev cv_trace_workspaces(kp_ctx* c, const kp_batch* bt, const PostReq& rq, const CvStepPlan& sp) {
   CvTraceDev t;
-  if (!tk.trace) return t;
-  const int ns = bt->n_slots;
+  if (!rq.trace) return t;
   int max_rows = 1;
   for (int s = 0; s < sp.T; ++s)
     max_rows = std::max(max_rows, (sp.kin_off[s + 1] - sp.kin_off[s]) + (sp.fin_off[s + 1] - sp.fin_off[s]));
-  t.total = tk.trace->trace_off[ns];
   t.ld = round_up(c->n_ent, 4);
   t.chunk = (int)std::min<size_t>((size_t)max_rows, std::max<size_t>(1, TRACE_WS_BYTES / (sizeof(float) * t.ld)));
   if (const char* e = std::getenv("KP_TRACE_CHUNK"))  // diagnostic: n rows per chunk, as KP_PROBE_CHUNK
     t.chunk = std::min(max_rows, std::max(1, std::atoi(e)));
-  t.off = upload(c, c->cv.tr_off, tk.trace->trace_off, (size_t)ns + 1);
-  t.loss = ensure_n<float>(c->cv.tr_loss, (size_t)std::max(1, t.total));
+  static_cast<TraceDev&>(t) = upload_trace(c, bt, rq);
   t.rows = ensure_n<float>(c->cv.tr_rows, (size_t)max_rows * c->dp);
   t.scores = ensure_n<float>(c->cv.tr_scores, (size_t)t.chunk * t.ld);
   t.rowloss = ensure_n<double>(c->cv.tr_rowloss, (size_t)max_rows);
@@ -1291,72 +1283,50 @@ int64_t cv_step_loop(kp_ctx* c, const kp_hp* hp, const CvConst& kc, const CvStep
   return launches;
 }
 
-// the probes' uploads and buffers (ahead of the step loop): the shared ones, the encoder
-// sources (-slot - 1, p) of every probe and one chunk's encoder rows.  A chunk's rows also
-// pass through encode_eval's feature maps and FC output, counted into the chunk's budget
-ProbeDev cv_probe_workspaces(kp_ctx* c, const kp_batch* bt, const TopkOut& tk) {
+// the optional requests' uploads and buffers (ahead of the step loop), in the order the stream
+// has always seen them: the probes, the trace, the marks.  A chunk's rank rows also pass
+// through encode_eval's feature maps and FC output, counted into the chunk's budget (which
+// makes upload_rank_rows upload the rows' encoder sources as well); with the marks, per entry
+// of the active lists the mark row its update also stores
+CvTraceDev cv_request_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq,
+                                 const CvStepPlan& sp, CvDev& d) {
   const size_t enc_row = sizeof(float) * ((size_t)c->hidden + c->dim + c->dp);
-  const ProbeDev pd = upload_probes(c, bt, tk, enc_row);
-  if (pd.n == 0) return pd;
-  const kp_probes* pr = tk.probes;
-  std::vector<int2> src(pd.n);
-  for (int s = 0; s < bt->n_slots; ++s)
-    for (int i = pr->probe_off[s]; i < pr->probe_off[s + 1]; ++i) src[i] = make_int2(-s - 1, pr->probes[2 * (size_t)i]);
-  upload(c, c->cv.probe_src, src.data(), src.size());
-  ensure_n<float>(c->cv.probe_q, (size_t)pd.chunk * c->dp);
-  return pd;
-}
-
-// the marks' uploads and buffers (ahead of the step loop), as the probes': the shared ones,
-// the encoder sources (-mark row - 1, p) of every mark row and one chunk's encoder rows
-void cv_mark_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk, const CvStepPlan& sp,
-                        CvDev& d) {
-  const size_t enc_row = sizeof(float) * ((size_t)c->hidden + c->dim + c->dp);
-  d.marks = upload_marks(c, c->cv.marks, hp, bt, tk, d.X, enc_row);
-  if (d.marks.nm == 0) return;
-  const int nm = d.marks.nm;
-  std::vector<int2> src((size_t)d.marks.rows.n);
-  for (int s = 0; s < bt->n_slots; ++s)
-    for (int j = 0; j < nm; ++j) src[(size_t)s * nm + j] = make_int2(-(s * nm + j) - 1, bt->pred[3 * s + 1]);
-  upload(c, c->cv.mark_src, src.data(), src.size());
-  ensure_n<float>(c->cv.mark_q, (size_t)d.marks.rows.chunk * c->dp);
-  const std::vector<int32_t> mr = marks_act_rows(d.marks, sp.act_off, sp.T, [&](int i) { return sp.acts[i].slot; });
-  d.mark_row = upload(c, c->cv.mark_row, mr.data(), mr.size());
+  d.probes = upload_probes(c, bt, rq, d.X, enc_row);
+  const CvTraceDev tr = cv_trace_workspaces(c, bt, rq, sp);
+  d.marks = upload_marks(c, c->cv.marks, hp, bt, rq, d.X, enc_row);
+  if (d.marks.nm > 0) {
+    const std::vector<int32_t> mr = marks_act_rows(d.marks, sp.act_off, sp.T, [&](int i) { return sp.acts[i].slot; });
+    d.mark_row = upload(c, c->cv.mark_row, mr.data(), mr.size());
+  }
+  return tr;
 }
 
 // rank: sigmoid(enc(x, R_p) . E_e), kelpie column, maximizer
-RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const TopkOut& tk, const CvDev& d,
-                const ProbeDev& pd) {
+RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const PostReq& rq, const CvDev& d) {
   const int ns = bt->n_slots, K = c->n_ent, DP = c->dp;
   std::vector<int2> rsrc(ns);
   for (int s = 0; s < ns; ++s) rsrc[s] = make_int2(-s - 1, bt->pred[3 * s + 1]);
   int2* dRsrc = upload(c, c->cv.rank_src, rsrc.data(), rsrc.size());
   float* dQr = ensure_n<float>(c->cv.q, (size_t)std::max(ns, d.mk) * DP);
   encode_eval(c, ns, dRsrc, d.X, dQr);
-  const RankDev rk = upload_rank_inputs(c, bt, tk);
+  const RankDev rk = upload_rank_inputs(c, bt, rq);
   if (c->cv_rank64) {
     const Rank64Dev r64 = rank64_buffers(c, ns);
     hipLaunchKernelGGL(kp_cv_rankq64<false>, dim3(ns), dim3(64), 0, c->stream, dQr, d.X, c->dE, K, DP, rk.po, ns, r64.q,
                        r64.t, r64.kcol);
     KP_HIP(hipGetLastError());
     launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_SIGMOID,
-                    tk.k, rk.top_ids, rk.top_scores);
-    // the probes: a chunk's rows through the encoder on their slots' kelpie rows, then the count
-    rank_probes(c, pd, RANK64_SIGMOID, [&](int r0, int m) {
-      encode_eval(c, m, c->cv.probe_src.as<int2>() + r0, d.X, c->cv.probe_q.as<float>());
-      hipLaunchKernelGGL(kp_cv_rankq64<true>, dim3(m), dim3(64), 0, c->stream, c->cv.probe_q.as<float>(), d.X, c->dE, K,
-                         DP, pd.trip + 3 * (size_t)r0, m, pd.q, pd.t, pd.kcol);
+                    rq.k, rk.top_ids, rk.top_scores);
+    // the probes on the slots' rows, then the marks on the mark workspace: a chunk's rows
+    // through the encoder (eval mode) on the set's rows, then the probe form and the count
+    const auto probe_queries = [c, K, DP](const RankRows& rr, int r0, int m) {
+      encode_eval(c, m, rr.enc_src + r0, rr.X, rr.enc_q);
+      hipLaunchKernelGGL(kp_cv_rankq64<true>, dim3(m), dim3(64), 0, c->stream, rr.enc_q, rr.X, c->dE, K, DP,
+                         rr.trip + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol);
       KP_HIP(hipGetLastError());
-    });
-    // the marks: the mark rows through the encoder (eval mode) from the mark workspace, then
-    // the probe form on "row trip[3 r] of the mark workspace"
-    const ProbeDev& mr = d.marks.rows;
-    rank_probes(c, mr, RANK64_SIGMOID, [&](int r0, int m) {
-      encode_eval(c, m, c->cv.mark_src.as<int2>() + r0, d.marks.X, c->cv.mark_q.as<float>());
-      hipLaunchKernelGGL(kp_cv_rankq64<true>, dim3(m), dim3(64), 0, c->stream, c->cv.mark_q.as<float>(), d.marks.X, c->dE,
-                         K, DP, mr.trip + 3 * (size_t)r0, m, mr.q, mr.t, mr.kcol);
-      KP_HIP(hipGetLastError());
-    }, &c->rank.m_bits);
+    };
+    rank_rows(c, d.probes, RANK64_SIGMOID, probe_queries);
+    rank_rows(c, d.marks.rows, RANK64_SIGMOID, probe_queries);
   } else {
     const int ld = round_up(K + 1, 4);
     float* dScores = ensure_n<float>(c->rank.scores, (size_t)ns * ld);
@@ -1372,14 +1342,10 @@ RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const TopkOut&
 
 // KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time of the planning (kp_cv_plan.hpp),
 // the uploads, enqueueing the step loop, and the rank with the final wait
-void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
+void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq) {
   const double t_in = g_host_times ? host_ms() : 0.0;
-  require_batch(c, bt, "ConvE");
-  require_topk(tk, c->cv_rank64 != 0, "ConvE");
-  require_probes(c, bt, tk, c->cv_rank64 != 0, "ConvE");
-  KP_REQUIRE(hp->batch_size >= 1 && hp->epochs >= 0, "ConvE: bad hyper-parameters");
-  require_trace(c, hp, bt, tk, "ConvE");
-  require_marks(hp, tk, c->cv_rank64 != 0, "ConvE");
+  // (with ConvE's hyper-parameter check at its place among the request's)
+  require_request(c, hp, bt, rq, c->cv_rank64 != 0, kp_model_name(c->model));
   const CvConst kc = make_const(c, hp);
 
   CvStepPlan sp;
@@ -1390,9 +1356,7 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
 
   std::vector<float> xp;
   CvDev d = cv_workspaces(c, bt, sp, xp);
-  const ProbeDev pd = cv_probe_workspaces(c, bt, tk);
-  const CvTraceDev tr = cv_trace_workspaces(c, bt, tk, sp);
-  cv_mark_workspaces(c, hp, bt, tk, sp, d);
+  const CvTraceDev tr = cv_request_workspaces(c, hp, bt, rq, sp, d);
   const double t_up = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipEventRecord(c->ev0, c->stream));
   const int nfp = cv_frozen_fc(c, kc, sp, d);
@@ -1401,13 +1365,9 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   const int64_t launches = cv_step_loop(c, hp, kc, sp, d, tr);
   const double t_loop = g_host_times ? host_ms() : 0.0;
 
-  const RankDev rk = cv_rank(c, kc, bt, tk, d, pd);
+  const RankDev rk = cv_rank(c, kc, bt, rq, d);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
-  if (tr.total > 0)  // with the other downloads, ahead of download_results' one wait
-    KP_HIP(hipMemcpyAsync(tk.trace->out_loss, tr.loss, sizeof(float) * (size_t)tr.total, hipMemcpyDeviceToHost,
-                          c->stream));
-  download_marks(c, bt, tk, d.marks);
-  download_results(c, bt, d.X, rk, xp, tk, pd);
+  download_results(c, bt, d.X, rk, xp, rq, d.probes, tr, d.marks);
   if (g_host_times)
     std::fprintf(stderr, "[kp_cv] slots %d steps %d pairs %zu: plan %.2f ms, uploads %.2f ms, loop enqueue %.2f ms, "
                  "rank + wait %.2f ms\n", bt->n_slots, sp.T, sp.kinst.size(), t_plan - t_in, t_up - t_plan,
@@ -1438,7 +1398,7 @@ void conve_scores_dev(kp_ctx* c, int n, const int32_t* d_heads, const int32_t* d
   for (int i = 0; i < n; ++i) src[i] = make_int2(h[i], r[i]);
   DevBuf bs, bq;
   int2* dsrc = upload(c, bs, src.data(), src.size());
-  float* dQ = reinterpret_cast<float*>(bq.ensure(sizeof(float) * (size_t)n * c->dp));
+  float* dQ = ensure_n<float>(bq, (size_t)n * c->dp);
   encode_eval(c, n, dsrc, nullptr, dQ);
   launch_gemm_abt(c, dQ, c->dp, n, c->dE, c->dp, c->n_ent, c->dp, d_out, ld, nullptr, 1, 1);
   KP_HIP(hipStreamSynchronize(c->stream));
@@ -1451,7 +1411,7 @@ void conve_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* rel
   DevBuf bh, br, bs;
   int32_t* dh = upload(c, bh, heads, (size_t)n);
   int32_t* dr = upload(c, br, rels, (size_t)n);
-  float* dS = reinterpret_cast<float*>(bs.ensure(sizeof(float) * (size_t)n * c->n_ent));
+  float* dS = ensure_n<float>(bs, (size_t)n * c->n_ent);
   conve_scores_dev(c, n, dh, dr, dS, c->n_ent);
   KP_HIP(hipMemcpyAsync(out, dS, sizeof(float) * (size_t)n * c->n_ent, hipMemcpyDeviceToHost, c->stream));
   KP_HIP(hipStreamSynchronize(c->stream));

@@ -1,12 +1,13 @@
 // kp_marks_check.hpp -- the epoch marks of kp_posttrain_rank_marks (include/kelpie_hip.h,
-// "Epoch marks"): the structural check of a call's kp_marks and the mark plan, as pure host
-// functions (no HIP: tests/native/marks_check_driver.cpp builds this header alone under the
+// "Epoch marks"): the structural check of a call's kp_marks, the mark plan and the marks'
+// expansion into rank rows, as pure host functions (no HIP: tests/native/marks_check_driver.cpp builds this header alone under the
 // host sanitizers).
 #pragma once
 
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "../../include/kelpie_hip.h"
@@ -99,4 +100,34 @@ inline int kp_marks_row_at(const KpMarkPlan& plan, int s, int t) {
   for (int j = 0; j < plan.n; ++j)
     if (plan.slot_step[(size_t)s * plan.n + j] == t + 1) return s * plan.n + j;
   return -1;
+}
+
+// The marks of a batch the batch check accepted as rank rows (kp_posttrain.hpp's RankRows):
+// row r = s * nm + j is trip[3 r ..] = (r, p, o) of slot s (pred [n_slots][3]), po[r] its
+// object, and its filter list [fo[r], fo[r + 1]) of `f` a copy of the slot's (`f` holds at
+// least one entry).  nullptr, or the bound the rows exceed: nothing is written then, and
+// `filt` is not read before the entry count is known to fit an int32.
+inline const char* kp_mark_rows(int n_slots, int nm, const int32_t* pred, const int32_t* filt_off, const int32_t* filt,
+                                std::vector<int32_t>& trip, std::vector<int32_t>& po, std::vector<int32_t>& fo,
+                                std::vector<int32_t>& f) {
+  if ((int64_t)n_slots * nm > INT32_MAX / 4) return "too many mark rows";
+  int64_t nf = 0;
+  for (int s = 0; s < n_slots; ++s) nf += (int64_t)nm * (filt_off[s + 1] - filt_off[s]);
+  if (nf > INT32_MAX) return "the mark rows' filter lists exceed 2^31 - 1 entries";
+  const size_t n = (size_t)n_slots * nm;
+  trip.assign(n * 3, 0);
+  po.assign(n, 0);
+  fo.assign(n + 1, 0);
+  f.assign((size_t)std::max<int64_t>(1, nf), 0);
+  for (int s = 0; s < n_slots; ++s)
+    for (int j = 0; j < nm; ++j) {
+      const size_t r = (size_t)s * nm + j;
+      trip[3 * r] = (int32_t)r;
+      trip[3 * r + 1] = pred[3 * s + 1];
+      trip[3 * r + 2] = po[r] = pred[3 * s + 2];
+      const int len = filt_off[s + 1] - filt_off[s];
+      if (len > 0) std::memcpy(&f[fo[r]], filt + filt_off[s], sizeof(int32_t) * len);
+      fo[r + 1] = fo[r] + len;
+    }
+  return nullptr;
 }

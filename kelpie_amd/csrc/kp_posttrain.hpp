@@ -1,9 +1,13 @@
-// kp_posttrain.hpp -- the host work the three *_posttrain_rank functions share: the batch
-// check, Adam's step scalars, the kelpie rows' padding, the rank inputs, the result download
-// and the hot-launch timing.  The model-specific step planning is pure host code in headers
-// of its own (kp_cx_plan.hpp: ComplEx / DistMult; kp_cv_plan.hpp: ConvE; TransE's schedule
-// is kp_sched.cpp); the launches, and where in the call the rank inputs are uploaded, stay
-// in kp_complex.hip / kp_transe.hip / kp_conve.hip.
+// kp_posttrain.hpp -- the host work the three *_posttrain_rank functions share: the check of
+// the batch and of the request (require_request), Adam's step scalars, the kelpie rows'
+// padding, the rank inputs, the rank rows (RankRows: the probes and the mark rows, one upload
+// and one chunked count for both), the trace's offsets and losses (TraceDev), the download of
+// every result and the hot-launch timing.  The model-specific step planning is pure host code
+// in headers of its own (kp_cx_plan.hpp: ComplEx / DistMult; kp_cv_plan.hpp: ConvE; TransE's
+// schedule is kp_sched.cpp), as are the request's checks and its expansion into rank rows
+// (kp_batch_check.hpp, kp_probe_check.hpp, kp_trace_check.hpp, kp_marks_check.hpp); the
+// launches, and where in the call each upload happens, stay in kp_complex.hip / kp_transe.hip
+// / kp_conve.hip.
 #pragma once
 
 #include <chrono>
@@ -24,40 +28,46 @@ inline double host_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// the structural checks of kp_batch_check.hpp, thrown as KP_EINVAL under the model's name;
-// first thing in every *_posttrain_rank, so a malformed batch leaves no device work in flight
-inline void require_batch(const kp_ctx* c, const kp_batch* bt, const char* model) {
-  if (const char* why = kp_check_batch(c->n_ent, c->n_rel2, c->dim, bt))
-    throw KpError{KP_EINVAL, std::string(model) + ": " + why};
-}
-
-// kp_posttrain_rank_topk's k and outputs, checked right after the batch and before the first
-// upload.  `rank64`: the call ranks on launch_rank_f64's fp64 operands; the fp32 diagnostic
-// rank (KP_TE_RANK / KP_CV_RANK = f32) has none to select from
-inline void require_topk(const TopkOut& tk, bool rank64, const char* model) {
-  if (tk.k < 0 || tk.k > 32) throw KpError{KP_EINVAL, std::string(model) + ": top-k: k must be in [0, 32]"};
-  if (tk.k > 0 && (!tk.ids || !tk.scores)) throw KpError{KP_EINVAL, std::string(model) + ": top-k: missing output"};
-  if (tk.k > 0 && !rank64)
-    throw KpError{KP_ENOTSUP, std::string(model) + ": top-k needs the fp64 rank (the fp32 rank switch is set)"};
-}
-
-// kp_posttrain_rank_probes' probes (kp_probe_check.hpp), checked right after the batch and
-// the top-k request and before the first upload; like the lists they need the fp64 rank
-inline void require_probes(const kp_ctx* c, const kp_batch* bt, const TopkOut& tk, bool rank64, const char* model) {
-  if (!tk.probes) return;
-  if (const char* why = kp_check_probes(c->n_ent, c->n_rel2, bt->n_slots, tk.probes))
-    throw KpError{KP_EINVAL, std::string(model) + ": probes: " + why};
-  if (tk.probes->n > 0 && !rank64)
-    throw KpError{KP_ENOTSUP, std::string(model) + ": probes need the fp64 rank (the fp32 rank switch is set)"};
-}
-
-// kp_posttrain_rank_trace's request (kp_trace_check.hpp), checked after the batch and the
-// probes and before the first upload.  The trace does not depend on the rank, so the fp32
-// rank switches are no reason to refuse it
-inline void require_trace(const kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk, const char* model) {
-  if (!tk.trace) return;
-  if (const char* why = kp_check_trace(c->model, hp, bt->n_slots, bt->row_off, bt->rows, tk.trace))
-    throw KpError{KP_EINVAL, std::string(model) + ": trace: " + why};
+// The checks of a call, first thing in every *_posttrain_rank, so that a malformed call
+// leaves no device work in flight; the first rule broken is the one reported, as KP_EINVAL
+// under the model's name: the batch (kp_batch_check.hpp), the top-k request, the probes
+// (kp_probe_check.hpp), the trace (kp_trace_check.hpp), the marks (kp_marks_check.hpp).
+// `rank64`: the call ranks on launch_rank_f64's fp64 operands; the lists, the probes and the
+// marks need them (KP_ENOTSUP under the fp32 diagnostic ranks, KP_TE_RANK / KP_CV_RANK = f32,
+// once well formed), the trace does not depend on the rank.
+// A batch without slots (kp_api.hip, which then calls no family; rank64 = true) has nothing
+// to check a list or a probe against: k and the probe count are refused under the entry
+// points' names, the trace and the marks by their own rules.
+inline void require_request(const kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq, bool rank64,
+                            const char* model) {
+  const std::string who = model;
+  if (bt->n_slots == 0) {
+    KP_REQUIRE(rq.k >= 0 && rq.k <= 32, "kp_posttrain_rank_topk: k must be in [0, 32]");
+    KP_REQUIRE(rq.n_probes() == 0, "kp_posttrain_rank_probes: probes without a slot");
+  } else {
+    if (const char* why = kp_check_batch(c->n_ent, c->n_rel2, c->dim, bt)) throw KpError{KP_EINVAL, who + ": " + why};
+    KP_REQUIRE(rq.k >= 0 && rq.k <= 32, who + ": top-k: k must be in [0, 32]");
+    KP_REQUIRE(rq.k == 0 || (rq.ids && rq.scores), who + ": top-k: missing output");
+    if (rq.k > 0 && !rank64)
+      throw KpError{KP_ENOTSUP, who + ": top-k needs the fp64 rank (the fp32 rank switch is set)"};
+    if (rq.probes) {
+      if (const char* why = kp_check_probes(c->n_ent, c->n_rel2, bt->n_slots, rq.probes))
+        throw KpError{KP_EINVAL, who + ": probes: " + why};
+      if (rq.probes->n > 0 && !rank64)
+        throw KpError{KP_ENOTSUP, who + ": probes need the fp64 rank (the fp32 rank switch is set)"};
+    }
+    // ConvE refuses its hyper-parameters here, ahead of the trace's own batch_size rule
+    // (ComplEx / DistMult refuse theirs before this function, TransE after it)
+    if (c->model == KP_MODEL_CONVE)
+      KP_REQUIRE(hp->batch_size >= 1 && hp->epochs >= 0, "ConvE: bad hyper-parameters");
+  }
+  if (rq.trace)
+    if (const char* why = kp_check_trace(c->model, hp, bt->n_slots, bt->row_off, bt->rows, rq.trace))
+      throw KpError{KP_EINVAL, who + ": trace: " + why};
+  if (rq.marks) {
+    if (const char* why = kp_check_marks(hp, rq.marks)) throw KpError{KP_EINVAL, who + ": marks: " + why};
+    if (!rank64) throw KpError{KP_ENOTSUP, who + ": marks need the fp64 rank (the fp32 rank switch is set)"};
+  }
 }
 
 // Adam's per-step scalars at step t (0-based) of a call: lr / (1 - beta1^(t+1)) and
@@ -94,7 +104,7 @@ struct RankDev {
 
 // upload the ranked objects and the filter CSR, size the result buffers.  The caller
 // chooses where in its call this happens: an upload's position decides what it overlaps.
-inline RankDev upload_rank_inputs(kp_ctx* c, const kp_batch* bt, const TopkOut& tk = {}) {
+inline RankDev upload_rank_inputs(kp_ctx* c, const kp_batch* bt, const PostReq& rq = {}) {
   const int ns = bt->n_slots;
   std::vector<int32_t> po(ns);
   for (int s = 0; s < ns; ++s) po[s] = bt->pred[3 * s + 2];
@@ -102,11 +112,11 @@ inline RankDev upload_rank_inputs(kp_ctx* c, const kp_batch* bt, const TopkOut& 
   r.po = upload(c, c->rank.po, po.data(), po.size());
   r.filt_off = upload(c, c->rank.filt_off, bt->filt_off, (size_t)ns + 1);
   r.filt = upload(c, c->rank.filt, bt->filt, (size_t)bt->filt_off[ns]);
-  r.target = reinterpret_cast<float*>(c->rank.target.ensure(sizeof(float) * (size_t)ns));
-  r.rank = reinterpret_cast<int64_t*>(c->rank.rank.ensure(sizeof(int64_t) * (size_t)ns));
-  if (tk.k > 0) {
-    r.top_ids = reinterpret_cast<int32_t*>(c->rank.top_ids.ensure(sizeof(int32_t) * (size_t)ns * tk.k));
-    r.top_scores = reinterpret_cast<float*>(c->rank.top_scores.ensure(sizeof(float) * (size_t)ns * tk.k));
+  r.target = ensure_n<float>(c->rank.target, (size_t)ns);
+  r.rank = ensure_n<int64_t>(c->rank.rank, (size_t)ns);
+  if (rq.k > 0) {
+    r.top_ids = ensure_n<int32_t>(c->rank.top_ids, (size_t)ns * rq.k);
+    r.top_scores = ensure_n<float>(c->rank.top_scores, (size_t)ns * rq.k);
   }
   return r;
 }
@@ -118,149 +128,147 @@ struct Rank64Dev {
 };
 inline Rank64Dev rank64_buffers(kp_ctx* c, int ns) {
   Rank64Dev r;
-  r.q = reinterpret_cast<double*>(c->rank.q64.ensure(sizeof(double) * (size_t)ns * c->dp));
-  r.t = reinterpret_cast<double*>(c->rank.t64.ensure(sizeof(double) * 2 * (size_t)ns));
+  r.q = ensure_n<double>(c->rank.q64, (size_t)ns * c->dp);
+  r.t = ensure_n<double>(c->rank.t64, 2 * (size_t)ns);
   r.kcol = r.t + ns;
   return r;
 }
 
-// the probes on the device (c->rank.p_*): inputs and results of all n probes, and the fp64
-// operands of one chunk of probe rows (the chunks run one after the other on the stream)
+// A set of rank rows on the device (c->rank.probes, c->rank.marks): rows ranked like the
+// slots, each naming the kelpie row it stands on.  Row r is (row, p, o): the probe form of the
+// family's query kernel reads "row trip[3 r] of X" where the slot form reads row r.  The
+// inputs and results of all n rows, and the fp64 operands of one chunk of rows (the chunks run
+// one after the other on the stream).
+//   the probes: row r is probe r, (slot, p, o), X the slots' kelpie rows;
+//   the marks:  row s * nm + j is (s * nm + j, p, o) of slot s with the slot's filter list,
+//               X the family's mark workspace [ns][nm][dp].
 constexpr size_t PROBE_WS_BYTES = (size_t)64 << 20;  // a chunk's query rows and bitmaps, as TOPK_WS_BYTES
 constexpr int PROBE_GROUP = 16;                      // kp_rank_f64_count's rows per workgroup row (RQ)
-struct ProbeDev {
+struct RankRows {
   int n = 0, chunk = 0;
-  int32_t* trip = nullptr;  // [n][3] (slot, p, o)
-  int32_t* po = nullptr;    // [n]
+  const float* X = nullptr;  // the rows trip[3 r] indexes
+  int32_t* trip = nullptr;   // [n][3] (row, p, o)
+  int32_t* po = nullptr;     // [n]
   int32_t* filt_off = nullptr;
   int32_t* filt = nullptr;
   float* target = nullptr;  // [n]
   int64_t* rank = nullptr;  // [n]
   double *q = nullptr, *t = nullptr, *kcol = nullptr;  // [chunk][dp], [chunk], [chunk]
+  DevBuf* bits = nullptr;                              // the chunk's filter bitmaps (launch_rank_f64 sizes them)
+  int2* enc_src = nullptr;                             // ConvE: [n] the rows' encoder sources (-row - 1, p)
+  float* enc_q = nullptr;                              // ConvE: [chunk][dp] the chunk's encoder output
 };
 
-// upload the probes and size every probe buffer; called with the call's other uploads,
-// ahead of the step loop.  `extra_row_bytes`: what else the model holds per probe row of a
-// chunk (ConvE: the encoder's rows), counted into the chunk's budget
-inline ProbeDev upload_probes(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, size_t extra_row_bytes = 0) {
-  ProbeDev d;
-  const int n = tk.n_probes();
+// upload a set of rank rows (kp_probe_check.hpp's / kp_marks_check.hpp's expansion) and size
+// every buffer of `ws`; called with the call's other uploads, ahead of the step loop.
+// `chunk_env`: the diagnostic variable that forces the rows per chunk.  `enc_row_bytes` (ConvE,
+// else 0): what a chunk row's pass through the encoder holds, counted into the chunk's budget;
+// the rows' encoder sources are then uploaded and the chunk's encoder output sized as well.
+// The uploads read host vectors that end with the caller: pageable copies are staged before
+// hipMemcpyAsync returns.
+inline RankRows upload_rank_rows(kp_ctx* c, RankRowsWs& ws, const char* chunk_env, const float* X,
+                                 const std::vector<int32_t>& trip, const std::vector<int32_t>& po,
+                                 const int32_t* filt_off, const int32_t* filt, size_t n_filt,
+                                 size_t enc_row_bytes = 0) {
+  RankRows d;
+  const int n = (int)po.size();
   if (n == 0) return d;
-  const kp_probes* pr = tk.probes;
-  std::vector<int32_t> trip((size_t)n * 3), po(n);
-  for (int s = 0; s < bt->n_slots; ++s)
-    for (int i = pr->probe_off[s]; i < pr->probe_off[s + 1]; ++i) {
-      trip[3 * (size_t)i] = s;
-      trip[3 * (size_t)i + 1] = pr->probes[2 * (size_t)i];
-      trip[3 * (size_t)i + 2] = po[i] = pr->probes[2 * (size_t)i + 1];
-    }
   const int nwords = (c->n_ent + 1 + 31) / 32;
   int forced = 0;
-  if (const char* a = std::getenv("KP_PROBE_CHUNK")) forced = std::max(0, std::atoi(a));
+  if (const char* a = std::getenv(chunk_env)) forced = std::max(0, std::atoi(a));
   d.n = n;
-  d.chunk = kp_probe_chunk(n, sizeof(double) * c->dp + sizeof(uint32_t) * nwords + extra_row_bytes, PROBE_WS_BYTES,
+  d.chunk = kp_probe_chunk(n, sizeof(double) * c->dp + sizeof(uint32_t) * nwords + enc_row_bytes, PROBE_WS_BYTES,
                            PROBE_GROUP, forced);
-  d.trip = upload(c, c->rank.p_trip, trip.data(), trip.size());
-  d.po = upload(c, c->rank.p_po, po.data(), po.size());
-  d.filt_off = upload(c, c->rank.p_filt_off, pr->filt_off, (size_t)n + 1);
-  d.filt = upload(c, c->rank.p_filt, pr->filt, (size_t)pr->filt_off[n]);
-  d.target = reinterpret_cast<float*>(c->rank.p_target.ensure(sizeof(float) * (size_t)n));
-  d.rank = reinterpret_cast<int64_t*>(c->rank.p_rank.ensure(sizeof(int64_t) * (size_t)n));
-  d.q = reinterpret_cast<double*>(c->rank.p_q64.ensure(sizeof(double) * (size_t)d.chunk * c->dp));
-  d.t = reinterpret_cast<double*>(c->rank.p_t64.ensure(sizeof(double) * 2 * (size_t)d.chunk));
+  d.X = X;
+  d.trip = upload(c, ws.trip, trip.data(), trip.size());
+  d.po = upload(c, ws.po, po.data(), po.size());
+  d.filt_off = upload(c, ws.filt_off, filt_off, (size_t)n + 1);
+  d.filt = upload(c, ws.filt, filt, n_filt);
+  d.target = ensure_n<float>(ws.target, (size_t)n);
+  d.rank = ensure_n<int64_t>(ws.rank, (size_t)n);
+  d.q = ensure_n<double>(ws.q64, (size_t)d.chunk * c->dp);
+  d.t = ensure_n<double>(ws.t64, 2 * (size_t)d.chunk);
   d.kcol = d.t + d.chunk;
-  (void)c->rank.p_bits.ensure(sizeof(uint32_t) * (size_t)d.chunk * nwords);
+  d.bits = &ws.bits;
+  (void)ws.bits.ensure(sizeof(uint32_t) * (size_t)d.chunk * nwords);
+  if (enc_row_bytes > 0) {
+    std::vector<int2> src((size_t)n);
+    for (int r = 0; r < n; ++r) src[r] = make_int2(-trip[3 * (size_t)r] - 1, trip[3 * (size_t)r + 1]);
+    d.enc_src = upload(c, ws.enc_src, src.data(), src.size());
+    d.enc_q = ensure_n<float>(ws.enc_q, (size_t)d.chunk * c->dp);
+  }
   return d;
 }
 
-// rank the probe rows, chunk by chunk: `queries(r0, m)` enqueues the model's probe form of
-// its query kernel for the probes [r0, r0 + m) (their fp64 rows, target and kelpie column
-// scores into d.q / d.t / d.kcol), then the slots' own count runs over those rows (k = 0)
-// (`bits`: the chunk's filter bitmaps; the mark rows, ranked the same way, bring their own)
+// the probes as rank rows on the slots' kelpie rows dX
+inline RankRows upload_probes(kp_ctx* c, const kp_batch* bt, const PostReq& rq, const float* dX,
+                              size_t enc_row_bytes = 0) {
+  if (rq.n_probes() == 0) return {};
+  std::vector<int32_t> trip, po;
+  kp_probe_rows(bt->n_slots, rq.probes, trip, po);
+  return upload_rank_rows(c, c->rank.probes, "KP_PROBE_CHUNK", dX, trip, po, rq.probes->filt_off, rq.probes->filt,
+                          (size_t)rq.probes->filt_off[rq.probes->n], enc_row_bytes);
+}
+
+// rank a set of rows, chunk by chunk: `queries(d, r0, m)` enqueues the model's probe form of
+// its query kernel for the rows [r0, r0 + m) (their fp64 rows, target and kelpie column scores
+// into d.q / d.t / d.kcol), then the slots' own count runs over those rows (k = 0)
 template <class F>
-inline void rank_probes(kp_ctx* c, const ProbeDev& d, int act, F&& queries, DevBuf* bits = nullptr) {
+inline void rank_rows(kp_ctx* c, const RankRows& d, int act, F&& queries) {
   for (int r0 = 0; r0 < d.n; r0 += d.chunk) {
     const int m = std::min(d.chunk, d.n - r0);
-    queries(r0, m);
+    queries(d, r0, m);
     launch_rank_f64(c, m, d.q, d.t, d.kcol, d.po + r0, d.filt_off + r0, d.filt, d.target + r0, d.rank + r0, act, 0,
-                    nullptr, nullptr, bits ? bits : &c->rank.p_bits);
+                    nullptr, nullptr, d.bits);
   }
 }
 
-// kp_posttrain_rank_marks' request (kp_marks_check.hpp), checked after the batch, the probes
-// and the trace and before the first upload; like the lists and the probes the marks need the
-// fp64 rank
-inline void require_marks(const kp_hp* hp, const TopkOut& tk, bool rank64, const char* model) {
-  if (!tk.marks) return;
-  if (const char* why = kp_check_marks(hp, tk.marks))
-    throw KpError{KP_EINVAL, std::string(model) + ": marks: " + why};
-  if (!rank64)
-    throw KpError{KP_ENOTSUP, std::string(model) + ": marks need the fp64 rank (the fp32 rank switch is set)"};
-}
-
 // the marks on the device: the mark rows X [ns][nm][dp] in the family's workspace (every row
-// the padded x0 until a step captures it) and, in c->rank.m_*, the rows as rank rows in the
-// probes' layout -- row s * nm + j is (row, p, o) of slot s with the slot's filter list -- so
-// the probe form of the family's query kernel reads "row trip[3 r] of X" from the mark
-// workspace and rank_probes counts them
+// the padded x0 until a step captures it), the rows as rank rows, and which step captures which
 struct MarksDev {
   int nm = 0;         // marks per slot (0: no marks)
   float* X = nullptr;
-  ProbeDev rows;      // n = ns * nm
+  RankRows rows;      // n = ns * nm
   KpMarkPlan plan;
 };
 
-// plan the marks, size every mark buffer, upload the rank rows and start every mark row as
-// its slot's padded x0 (dX, already uploaded on the stream); with the call's other uploads,
-// ahead of the step loop.  `ws`: the family's mark workspace; `extra_row_bytes` as upload_probes'
-inline MarksDev upload_marks(kp_ctx* c, DevBuf& ws, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk,
-                             const float* dX, size_t extra_row_bytes = 0) {
+// plan the marks, size the mark workspace `ws`, start every mark row as its slot's padded x0
+// (dX, already uploaded on the stream) and upload the rank rows; with the call's other
+// uploads, ahead of the step loop
+inline MarksDev upload_marks(kp_ctx* c, DevBuf& ws, const kp_hp* hp, const kp_batch* bt, const PostReq& rq,
+                             const float* dX, size_t enc_row_bytes = 0) {
   MarksDev d;
-  if (!tk.marks) return d;
-  const int ns = bt->n_slots, nm = tk.marks->n, n = ns * nm;
-  if (const char* why = kp_marks_plan(c->model, hp, ns, bt->row_off, bt->rows, tk.marks, d.plan))
-    throw KpError{KP_EINVAL, std::string("marks: ") + why};
-  KP_REQUIRE((int64_t)ns * nm <= INT32_MAX / 4, "marks: too many mark rows");
+  if (!rq.marks) return d;
+  const int ns = bt->n_slots, nm = rq.marks->n;
+  std::vector<int32_t> trip, po, fo, filt;
+  const char* why = kp_marks_plan(c->model, hp, ns, bt->row_off, bt->rows, rq.marks, d.plan);
+  if (!why) why = kp_mark_rows(ns, nm, bt->pred, bt->filt_off, bt->filt, trip, po, fo, filt);
+  if (why) throw KpError{KP_EINVAL, std::string("marks: ") + why};
   d.nm = nm;
-  d.X = reinterpret_cast<float*>(ws.ensure(sizeof(float) * (size_t)n * c->dp));
+  d.X = ensure_n<float>(ws, (size_t)ns * nm * c->dp);
   for (int j = 0; j < nm; ++j)
     KP_HIP(hipMemcpy2DAsync(d.X + (size_t)j * c->dp, sizeof(float) * (size_t)nm * c->dp, dX, sizeof(float) * c->dp,
                             sizeof(float) * c->dp, ns, hipMemcpyDeviceToDevice, c->stream));
-  std::vector<int32_t> trip((size_t)n * 3), po(n), fo((size_t)n + 1, 0);
-  int64_t nf = 0;
-  for (int s = 0; s < ns; ++s) nf += (int64_t)nm * (bt->filt_off[s + 1] - bt->filt_off[s]);
-  KP_REQUIRE(nf <= INT32_MAX, "marks: the mark rows' filter lists exceed 2^31 - 1 entries");
-  std::vector<int32_t> filt((size_t)std::max<int64_t>(1, nf));
-  for (int s = 0; s < ns; ++s)
-    for (int j = 0; j < nm; ++j) {
-      const size_t r = (size_t)s * nm + j;
-      trip[3 * r] = (int32_t)r;
-      trip[3 * r + 1] = bt->pred[3 * s + 1];
-      trip[3 * r + 2] = po[r] = bt->pred[3 * s + 2];
-      const int len = bt->filt_off[s + 1] - bt->filt_off[s];
-      if (len > 0) std::memcpy(&filt[fo[r]], bt->filt + bt->filt_off[s], sizeof(int32_t) * len);
-      fo[r + 1] = fo[r] + len;
-    }
-  const int nwords = (c->n_ent + 1 + 31) / 32;
-  int forced = 0;
-  if (const char* a = std::getenv("KP_MARKS_CHUNK")) forced = std::max(0, std::atoi(a));
-  ProbeDev& p = d.rows;
-  p.n = n;
-  p.chunk = kp_probe_chunk(n, sizeof(double) * c->dp + sizeof(uint32_t) * nwords + extra_row_bytes, PROBE_WS_BYTES,
-                           PROBE_GROUP, forced);
-  p.trip = upload(c, c->rank.m_trip, trip.data(), trip.size());
-  p.po = upload(c, c->rank.m_po, po.data(), po.size());
-  p.filt_off = upload(c, c->rank.m_filt_off, fo.data(), fo.size());
-  p.filt = upload(c, c->rank.m_filt, filt.data(), filt.size());
-  p.target = reinterpret_cast<float*>(c->rank.m_target.ensure(sizeof(float) * (size_t)n));
-  p.rank = reinterpret_cast<int64_t*>(c->rank.m_rank.ensure(sizeof(int64_t) * (size_t)n));
-  p.q = reinterpret_cast<double*>(c->rank.m_q64.ensure(sizeof(double) * (size_t)p.chunk * c->dp));
-  p.t = reinterpret_cast<double*>(c->rank.m_t64.ensure(sizeof(double) * 2 * (size_t)p.chunk));
-  p.kcol = p.t + p.chunk;
-  (void)c->rank.m_bits.ensure(sizeof(uint32_t) * (size_t)p.chunk * nwords);
-  // the uploads above read host vectors that end with this call: pageable copies are staged
-  // before hipMemcpyAsync returns
+  d.rows = upload_rank_rows(c, c->rank.marks, "KP_MARKS_CHUNK", d.X, trip, po, fo.data(), filt.data(), filt.size(),
+                            enc_row_bytes);
   return d;
+}
+
+// kp_posttrain_rank_trace's common part on the device (c->rank.tr_*; loss == nullptr: no
+// trace): the slots' offsets into the losses and the losses of every step
+struct TraceDev {
+  int32_t* off = nullptr;  // [ns + 1]
+  float* loss = nullptr;   // [total]
+  int total = 0;
+};
+inline TraceDev upload_trace(kp_ctx* c, const kp_batch* bt, const PostReq& rq) {
+  TraceDev t;
+  if (!rq.trace) return t;
+  const int ns = bt->n_slots;
+  t.total = rq.trace->trace_off[ns];
+  t.off = upload(c, c->rank.tr_off, rq.trace->trace_off, (size_t)ns + 1);
+  t.loss = ensure_n<float>(c->rank.tr_loss, (size_t)std::max(1, t.total));
+  return t;
 }
 
 // per entry of a host-driven step loop's active lists (entry i of step t is slot slot_of(i)):
@@ -278,35 +286,36 @@ inline bool marks_at_step(const MarksDev& d, int t) {
   return d.nm > 0 && t < d.plan.T && d.plan.step_off[t + 1] > d.plan.step_off[t];
 }
 
-// enqueue the downloads of the marks' results, ahead of download_results' one wait
-inline void download_marks(kp_ctx* c, const kp_batch* bt, const TopkOut& tk, const MarksDev& d) {
-  if (d.nm == 0) return;
-  const size_t n = (size_t)d.rows.n;
-  KP_HIP(hipMemcpyAsync(tk.marks->out_score, d.rows.target, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(tk.marks->out_rank, d.rows.rank, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
-  if (tk.marks->out_x)
-    KP_HIP(hipMemcpy2DAsync(tk.marks->out_x, sizeof(float) * c->dim, d.X, sizeof(float) * c->dp, sizeof(float) * c->dim,
-                            n, hipMemcpyDeviceToHost, c->stream));
-}
-
-// the tail of a call: enqueue the downloads of the kelpie rows (when out_x is set), the
-// target scores, the ranks, the top-k lists and the probes' results (when asked for), wait
-// for the stream once, unpad the rows into out_x.
+// the tail of a call: enqueue the downloads of the trace's losses, the marks' results, the
+// kelpie rows (when out_x is set), the target scores, the ranks, the top-k lists and the
+// probes' results (each when asked for), wait for the stream once, unpad the rows into out_x.
 // Returns the host time at which the wait began (0 unless KP_HOST_TIMES).
 inline double download_results(kp_ctx* c, const kp_batch* bt, const float* dX, const RankDev& r,
-                               std::vector<float>& xp, const TopkOut& tk = {}, const ProbeDev& pd = {}) {
+                               std::vector<float>& xp, const PostReq& rq = {}, const RankRows& pd = {},
+                               const TraceDev& tr = {}, const MarksDev& md = {}) {
   const int ns = bt->n_slots;
-  if (bt->out_x) KP_HIP(hipMemcpyAsync(xp.data(), dX, sizeof(float) * xp.size(), hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(bt->out_score, r.target, sizeof(float) * ns, hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(bt->out_rank, r.rank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
-  if (tk.k > 0) {
-    const size_t n = (size_t)ns * tk.k;
-    KP_HIP(hipMemcpyAsync(tk.ids, r.top_ids, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-    KP_HIP(hipMemcpyAsync(tk.scores, r.top_scores, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+  const auto to_host = [c](void* dst, const void* src, size_t bytes) {
+    KP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  };
+  if (tr.total > 0) to_host(rq.trace->out_loss, tr.loss, sizeof(float) * (size_t)tr.total);
+  if (md.nm > 0) {
+    const size_t n = (size_t)md.rows.n;
+    to_host(rq.marks->out_score, md.rows.target, sizeof(float) * n);
+    to_host(rq.marks->out_rank, md.rows.rank, sizeof(int64_t) * n);
+    if (rq.marks->out_x)
+      KP_HIP(hipMemcpy2DAsync(rq.marks->out_x, sizeof(float) * c->dim, md.X, sizeof(float) * c->dp,
+                              sizeof(float) * c->dim, n, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (bt->out_x) to_host(xp.data(), dX, sizeof(float) * xp.size());
+  to_host(bt->out_score, r.target, sizeof(float) * ns);
+  to_host(bt->out_rank, r.rank, sizeof(int64_t) * ns);
+  if (rq.k > 0) {
+    to_host(rq.ids, r.top_ids, sizeof(int32_t) * (size_t)ns * rq.k);
+    to_host(rq.scores, r.top_scores, sizeof(float) * (size_t)ns * rq.k);
   }
   if (pd.n > 0) {
-    KP_HIP(hipMemcpyAsync(tk.probes->out_score, pd.target, sizeof(float) * pd.n, hipMemcpyDeviceToHost, c->stream));
-    KP_HIP(hipMemcpyAsync(tk.probes->out_rank, pd.rank, sizeof(int64_t) * pd.n, hipMemcpyDeviceToHost, c->stream));
+    to_host(rq.probes->out_score, pd.target, sizeof(float) * pd.n);
+    to_host(rq.probes->out_rank, pd.rank, sizeof(int64_t) * pd.n);
   }
   const double t_wait = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipStreamSynchronize(c->stream));

@@ -1,11 +1,12 @@
 // kp_probe_check.hpp -- the structural checks of a batch's probes (kp_probes), as one pure
 // host function (no HIP: tests/native/probe_check_driver.cpp builds it alone under the
-// host sanitizers), and the chunking of the probe rows.
+// host sanitizers), the probes' expansion into rank rows and the chunking of rank rows.
 #pragma once
 
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "../../include/kelpie_hip.h"
 
@@ -42,10 +43,24 @@ inline const char* kp_check_probes(int n_ent, int n_rel2, int n_slots, const kp_
   return nullptr;
 }
 
-// Probe rows per chunk: whole rows of `row_bytes` (the fp64 query row, the filter bitmap and
+// The probes kp_check_probes accepted as rank rows (kp_posttrain.hpp's RankRows): row i is
+// trip[3 i ..] = (slot, p, o) of probe i, po[i] its object.  The probes' filter CSR is already
+// one list per row.
+inline void kp_probe_rows(int n_slots, const kp_probes* p, std::vector<int32_t>& trip, std::vector<int32_t>& po) {
+  trip.assign((size_t)p->n * 3, 0);
+  po.assign((size_t)p->n, 0);
+  for (int s = 0; s < n_slots; ++s)
+    for (int i = p->probe_off[s]; i < p->probe_off[s + 1]; ++i) {
+      trip[3 * (size_t)i] = s;
+      trip[3 * (size_t)i + 1] = p->probes[2 * (size_t)i];
+      trip[3 * (size_t)i + 2] = po[i] = p->probes[2 * (size_t)i + 1];
+    }
+}
+
+// Rank rows per chunk (the probes', the mark rows'): whole rows of `row_bytes` (the fp64 query row, the filter bitmap and
 // whatever else the model holds per row) within `budget` bytes, a multiple of `group` rows
 // when more than one group fits, at least one row and at most n.  `forced` > 0
-// (KP_PROBE_CHUNK) overrides the budget.
+// (KP_PROBE_CHUNK, KP_MARKS_CHUNK) overrides the budget.
 inline int kp_probe_chunk(int n, size_t row_bytes, size_t budget, int group, int forced) {
   if (n <= 0) return 0;
   if (forced > 0) return std::min(n, forced);

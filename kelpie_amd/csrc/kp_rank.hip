@@ -486,7 +486,7 @@ void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* 
   if (n_slots <= 0) return;
   const int ldt = (c->n_ent + 255) / 256 * 256;
   if (!c->eT_ready) {
-    float* ET = reinterpret_cast<float*>(c->eT.ensure(sizeof(float) * (size_t)c->dp * ldt));
+    float* ET = ensure_n<float>(c->eT, (size_t)c->dp * ldt);
     hipLaunchKernelGGL(kp_transpose_table, dim3(ldt / 32, (c->dp + 31) / 32), dim3(256), 0, c->stream, c->dE,
                        c->n_ent, c->dp, ET, ldt);
     KP_HIP(hipGetLastError());
@@ -495,7 +495,7 @@ void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* 
   const int n_cols = c->n_ent + 1;
   const int nwords = (n_cols + 31) / 32;
   DevBuf& bb = bits_buf ? *bits_buf : c->rank.bits;
-  uint32_t* bits = reinterpret_cast<uint32_t*>(bb.ensure(sizeof(uint32_t) * (size_t)n_slots * nwords));
+  uint32_t* bits = ensure_n<uint32_t>(bb, (size_t)n_slots * nwords);
   unsigned long long* rank = reinterpret_cast<unsigned long long*>(d_rank);
   hipLaunchKernelGGL(kp_rank_filter_bits, dim3(n_slots), dim3(256), 0, c->stream, n_slots, nwords, d_filt_off, d_filt,
                      n_cols, bits);
@@ -512,7 +512,7 @@ void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* 
     const int chunk = std::min(n_slots, rows_fit * RQ);
     unsigned long long* ck =
         reinterpret_cast<unsigned long long*>(c->rank.cand_key.ensure(sizeof(unsigned long long) * per_slot * chunk));
-    int32_t* cc = reinterpret_cast<int32_t*>(c->rank.cand_col.ensure(sizeof(int32_t) * per_slot * chunk));
+    int32_t* cc = ensure_n<int32_t>(c->rank.cand_col, per_slot * chunk);
     for (int s0 = 0; s0 < n_slots; s0 += chunk) {
       const int m = std::min(chunk, n_slots - s0);
       const dim3 grid(ldt / 256, (m + RQ - 1) / RQ);

@@ -634,15 +634,11 @@ __global__ void kp_te_rankq64(const float* __restrict__ X, const float* __restri
 
 }  // namespace
 
-void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const TopkOut& tk) {
+void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq) {
   const int ns = bt->n_slots;
   const int DP = c->dp;
   const bool l1 = c->te_norm == 1;
-  require_batch(c, bt, "TransE");
-  require_topk(tk, c->te_rank64 != 0, "TransE");
-  require_probes(c, bt, tk, c->te_rank64 != 0, "TransE");
-  require_trace(c, hp, bt, tk, "TransE");
-  require_marks(hp, tk, c->te_rank64 != 0, "TransE");
+  require_request(c, hp, bt, rq, c->te_rank64 != 0, kp_model_name(c->model));
   // before the first upload: the buffers below are sized by DP, the kernels hold DP / 256 float4 per lane
   KP_REQUIRE(DP <= 512, "TransE: dimension > 512 not supported");
   KP_REQUIRE(hp->neg_ratio >= 1 && hp->batch_size >= 1 && hp->epochs >= 0, "TransE: bad hyper-parameters");
@@ -660,25 +656,21 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   int32_t* dRows = upload(c, c->te.rows, bt->rows, (size_t)std::max(1, 3 * total_rows));
   const int64_t nrng = bt->rng_off[ns];
   int32_t* dRng = upload(c, c->te.rng, bt->rng, (size_t)std::max<int64_t>(1, nrng));
-  const ProbeDev pd = upload_probes(c, bt, tk);
+  const RankRows pd = upload_probes(c, bt, rq, dX);
   // kp_posttrain_rank_marks: the mark rows (each the padded x0 until its epoch ends) and the epochs
-  const MarksDev md = upload_marks(c, c->te.marks, hp, bt, tk, dX);
+  const MarksDev md = upload_marks(c, c->te.marks, hp, bt, rq, dX);
   TeMarkArgs<true> mkd{nullptr};
   if (md.nm > 0) {
     std::vector<int32_t> hdr(TE_MARK_HDR + (size_t)hp->epochs, -1);
     const TeMarkHdr h{md.X, md.nm, 0};
     std::memcpy(hdr.data(), &h, sizeof(h));
     for (int j = 0; j < md.nm; ++j)
-      if (tk.marks->epochs[j] > 0) hdr[TE_MARK_HDR + tk.marks->epochs[j] - 1] = j;
+      if (rq.marks->epochs[j] > 0) hdr[TE_MARK_HDR + rq.marks->epochs[j] - 1] = j;
     mkd.hdr = upload(c, c->te.mark_ep, hdr.data(), hdr.size());
   }
   // kp_posttrain_rank_trace: the offsets and the losses, with the call's other uploads
-  const int n_trace = tk.trace ? tk.trace->trace_off[ns] : 0;
-  TeTraceArgs<true> trd{nullptr, nullptr};
-  if (tk.trace) {
-    trd.off = upload(c, c->te.tr_off, tk.trace->trace_off, (size_t)ns + 1);
-    trd.loss = reinterpret_cast<float*>(c->te.tr_loss.ensure(sizeof(float) * (size_t)std::max(1, n_trace)));
-  }
+  const TraceDev tr = upload_trace(c, bt, rq);
+  const TeTraceArgs<true> trd{tr.off, tr.loss};
 
   TeHp h{};
   h.epochs = hp->epochs;
@@ -714,13 +706,13 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   KP_HIP(hipEventRecord(ea, c->stream));
   const int vpl = (DP + 255) / 256;
 #define TE_LAUNCH(V, T, ST, L)                                                                                      \
-  if (md.nm > 0 && tk.trace)                                                                                       \
+  if (md.nm > 0 && rq.trace)                                                                                       \
     hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L, true, true>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP,  \
                        c->dim, c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, trd, mkd);                         \
   else if (md.nm > 0)                                                                                              \
     hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L, false, true>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP, \
                        c->dim, c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, TeTraceArgs<false>{}, mkd);        \
-  else if (tk.trace)                                                                                                \
+  else if (rq.trace)                                                                                                \
     hipLaunchKernelGGL((kp_te_posttrain<V, T, ST, L, true>), dim3(ns), dim3(T), shm, c->stream, c->n_ent, DP, c->dim, \
                        c->dE, c->dR, dSlots, dOrder, dRows, dRng, h, dX, trd, TeMarkArgs<false>{});                 \
   else                                                                                                             \
@@ -759,7 +751,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   for (int s = 0; s < ns; ++s) rels[s] = bt->pred[3 * s + 1];
   int32_t* dH = upload(c, c->te.heads, heads.data(), heads.size());
   int32_t* dRl = upload(c, c->te.rels, rels.data(), rels.size());
-  const RankDev rk = upload_rank_inputs(c, bt, tk);
+  const RankDev rk = upload_rank_inputs(c, bt, rq);
   if (c->te_rank64) {
     int32_t* dPred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
     const Rank64Dev r64 = rank64_buffers(c, ns);
@@ -767,29 +759,23 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
                        ns, r64.q, r64.t, r64.kcol, l1 ? 1 : 0);
     KP_HIP(hipGetLastError());
     launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank,
-                    l1 ? RANK64_DIST1 : RANK64_DIST, tk.k, rk.top_ids, rk.top_scores);
-    rank_probes(c, pd, l1 ? RANK64_DIST1 : RANK64_DIST, [&](int r0, int m) {
-      hipLaunchKernelGGL(kp_te_rankq64<true>, dim3(m), dim3(64), 0, c->stream, dX, c->dR, c->dE, c->n_ent, DP,
-                         pd.trip + 3 * (size_t)r0, m, pd.q, pd.t, pd.kcol, l1 ? 1 : 0);
+                    l1 ? RANK64_DIST1 : RANK64_DIST, rq.k, rk.top_ids, rk.top_scores);
+    // the probes on the slots' rows, then the marks on the mark workspace: the probe form
+    // reads row trip[3 r] of the set's rows instead of row r
+    const auto probe_queries = [c, DP, l1](const RankRows& rr, int r0, int m) {
+      hipLaunchKernelGGL(kp_te_rankq64<true>, dim3(m), dim3(64), 0, c->stream, rr.X, c->dR, c->dE, c->n_ent, DP,
+                         rr.trip + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol, l1 ? 1 : 0);
       KP_HIP(hipGetLastError());
-    });
-    // the marks: the probe form reads row trip[3 r] of the mark workspace instead of a slot's row
-    rank_probes(c, md.rows, l1 ? RANK64_DIST1 : RANK64_DIST, [&](int r0, int m) {
-      hipLaunchKernelGGL(kp_te_rankq64<true>, dim3(m), dim3(64), 0, c->stream, md.X, c->dR, c->dE, c->n_ent, DP,
-                         md.rows.trip + 3 * (size_t)r0, m, md.rows.q, md.rows.t, md.rows.kcol, l1 ? 1 : 0);
-      KP_HIP(hipGetLastError());
-    }, &c->rank.m_bits);
+    };
+    rank_rows(c, pd, l1 ? RANK64_DIST1 : RANK64_DIST, probe_queries);
+    rank_rows(c, md.rows, l1 ? RANK64_DIST1 : RANK64_DIST, probe_queries);
   } else {
-    float* dScores = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)ns * ld));
+    float* dScores = ensure_n<float>(c->rank.scores, (size_t)ns * ld);
     launch_te_scores(c, ns, dH, dRl, dX, dScores, ld, c->n_ent);
     launch_rank_count(c, ns, dScores, ld, c->n_ent + 1, rk.po, rk.filt_off, rk.filt, 1, rk.target, rk.rank);
   }
   KP_HIP(hipEventRecord(c->ev1, c->stream));
-  if (n_trace > 0)  // with the other downloads, ahead of download_results' one wait
-    KP_HIP(hipMemcpyAsync(tk.trace->out_loss, trd.loss, sizeof(float) * (size_t)n_trace, hipMemcpyDeviceToHost,
-                          c->stream));
-  download_marks(c, bt, tk, md);
-  download_results(c, bt, dX, rk, xp, tk, pd);
+  download_results(c, bt, dX, rk, xp, rq, pd, tr, md);
   float ms_all = 0.f, ms_hot = 0.f;
   KP_HIP(hipEventElapsedTime(&ms_all, c->ev0, c->ev1));
   KP_HIP(hipEventElapsedTime(&ms_hot, ea, eb));
@@ -814,7 +800,7 @@ void transe_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* re
   int32_t* dr = upload(c, c->te.rels, rels, (size_t)n);
   // the rank's fp32 score matrix (idle outside transe_posttrain_rank) rather than one of its
   // own, which keeps the context's device allocations as they were
-  float* dS = reinterpret_cast<float*>(c->rank.scores.ensure(sizeof(float) * (size_t)n * c->n_ent));
+  float* dS = ensure_n<float>(c->rank.scores, (size_t)n * c->n_ent);
   transe_scores_dev(c, n, dh, dr, dS, c->n_ent);
   KP_HIP(hipMemcpyAsync(out, dS, sizeof(float) * (size_t)n * c->n_ent, hipMemcpyDeviceToHost, c->stream));
   KP_HIP(hipStreamSynchronize(c->stream));

@@ -803,32 +803,29 @@ class PostTrainingEngine(RelevanceEngine):
         marks = self._marks
         if marks is not None:
             kw["marks"] = marks
-        out = ctx.posttrain_rank(self._kp_hp, *packed, **kw)
-        if marks is not None:  # the last element; what is before it is the call's without marks
-            (m_score, m_rank, _), out = out[-1], out[:-1]
-        score, rank = out[0], out[1]
-        if k:
-            top_ids, top_scores = out[3]
+        out = _lib.split_rank_result(ctx.posttrain_rank(self._kp_hp, *packed, **kw), **kw)
+        score, rank = out.score, out.rank
         t_end = time.perf_counter()
         if fill:
             for i, s in enumerate(slots):
                 s.result = {"target_score": float(score[i]), "target_rank": int(rank[i])}
             if marks is not None:
+                m_score, m_rank, _ = out.marks
                 for i, s in enumerate(slots):
                     s.result["marks"] = [{"epoch": int(e), "score": float(m_score[i][j]), "rank": int(m_rank[i][j])}
                                          for j, e in enumerate(marks)]
             if traced:
-                for s, loss in zip(slots, out[-1]):
+                for s, loss in zip(slots, out.loss):
                     s.result["loss"] = [float(v) for v in loss]
             if probed:
-                p_score, p_rank = out[-2 if traced else -1]
+                p_score, p_rank = out.probes
                 j = 0
                 for s in slots:
                     s.result["probes"] = [{"triple": t, "score": float(p_score[j + i]), "rank": int(p_rank[j + i])}
                                           for i, (t, _, _) in enumerate(s.probes or [])]
                     j += len(s.probes or [])
             if k:
-                top_ids, top_scores = np.asarray(top_ids), np.asarray(top_scores)
+                top_ids, top_scores = np.asarray(out.top[0]), np.asarray(out.top[1])
                 # a list ends at its first -1 (fewer than k unmasked columns)
                 short = top_ids < 0
                 n_top = np.where(short.any(1), short.argmax(1), top_ids.shape[1])

@@ -5,6 +5,9 @@
 //     rule's message;
 //   * hand-derived plans: slots of 1, 2 and 3 steps per epoch and an empty slot in one batch,
 //     the marks {0}, {E} and all of 0..15, ConvE's pair counts with a last step of one pair;
+//   * the marks as rank rows: two slots by two marks, one slot's filter list empty; a filter
+//     entry count past 2^31 - 1 and a row count past the bound are refused before anything is
+//     read or written;
 //   * on 400 pseudo-random batches the plan equals a second, independent statement of the rule.
 // The arrays are heap vectors of their exact length, so a plan that reads past one is
 // reported.  Prints one line per case and exits 0 iff every case went as expected.
@@ -207,6 +210,38 @@ void hand_plans() {
   }
 }
 
+// the marks as rank rows (kp_mark_rows): row s * nm + j is (row, p, o) of slot s with a copy of
+// the slot's filter list
+void rank_rows() {
+  const std::vector<int32_t> pred{K, 3, 7, K, 1, K}, filt_off{0, 0, 2}, filt{4, 9};  // slot 0: no filter entry
+  std::vector<int32_t> trip{99}, po{99}, fo{99}, f;
+  const char* why = kp_mark_rows(2, 2, pred.data(), filt_off.data(), filt.data(), trip, po, fo, f);
+  bool ok = !why && trip == std::vector<int32_t>{0, 3, 7, 1, 3, 7, 2, 1, K, 3, 1, K} &&
+            po == std::vector<int32_t>{7, 7, K, K} && fo == std::vector<int32_t>{0, 0, 0, 2, 4} &&
+            f == std::vector<int32_t>{4, 9, 4, 9};
+  std::printf("rows 2 x 2, one empty filter: %s\n", why ? why : (ok ? "ok" : "wrong rows"));
+  if (!ok) fail("rows 2 x 2");
+  // no filter entry at all: `f` still holds one (zero) entry to upload
+  const std::vector<int32_t> none{0, 0, 0};
+  why = kp_mark_rows(2, 2, pred.data(), none.data(), nullptr, trip, po, fo, f);
+  ok = !why && fo == std::vector<int32_t>{0, 0, 0, 0, 0} && f == std::vector<int32_t>{0};
+  std::printf("rows without a filter: %s\n", why ? why : (ok ? "ok" : "wrong rows"));
+  if (!ok) fail("rows without a filter");
+  // 16 marks of two slots whose lists hold 2^27 entries each: 2^32 entries.  The offsets alone
+  // say so: there is no filter array behind them, and the outputs stay as they were
+  const std::vector<int32_t> huge{0, 1 << 27, 1 << 28};
+  trip = {99};
+  expect_msg("rows: 2^32 filter entries", kp_mark_rows(2, 16, pred.data(), huge.data(), nullptr, trip, po, fo, f),
+             "the mark rows' filter lists exceed 2^31 - 1 entries");
+  // two marks of one slot of 2^30 entries: 2^31, one more than fits
+  const std::vector<int32_t> edge{0, 1 << 30, 1 << 30};
+  expect_msg("rows: 2^31 filter entries", kp_mark_rows(2, 2, pred.data(), edge.data(), nullptr, trip, po, fo, f),
+             "the mark rows' filter lists exceed 2^31 - 1 entries");
+  if (trip != std::vector<int32_t>{99}) fail("rows: a refused call wrote its outputs");
+  expect_msg("rows: too many", kp_mark_rows(INT32_MAX / 4 / 16 + 1, 16, pred.data(), huge.data(), nullptr, trip, po, fo, f),
+             "too many mark rows");
+}
+
 uint32_t rng_state = 2463534242u;
 uint32_t rnd() {
   rng_state = rng_state * 1664525u + 1013904223u;
@@ -285,6 +320,7 @@ void random_batches() {
 int main() {
   errors();
   hand_plans();
+  rank_rows();
   random_batches();
   std::printf("%d failures\n", failures);
   return failures ? 1 : 0;

@@ -3,6 +3,7 @@
 // probe_check_asan` builds this file, tests/test_probe_check.py runs it.
 //   * a good set of probes passes, with and without probes, with an empty slot;
 //   * errors: the good set with exactly one rule broken must yield that rule's message;
+//   * the probes as rank rows: a slot without probes between two that have some;
 //   * on 400 pseudo-random valid sets the check passes and the chunks cover every probe row
 //     once, within the budget.
 // The arrays are heap vectors of their exact length, so a check that reads past one is
@@ -123,6 +124,24 @@ void errors() {
   }
 }
 
+// the probes as rank rows (kp_probe_rows): row i is (slot, p, o) of probe i
+void rank_rows() {
+  Probes g = good();  // slot 0: two probes, slot 1: none, slot 2: one
+  const kp_probes v = g.view();
+  std::vector<int32_t> trip{99}, po{99, 99};  // stale contents must go
+  kp_probe_rows(g.slots(), &v, trip, po);
+  const bool ok = trip == std::vector<int32_t>{0, 0, 3, 0, 3, K, 2, 1, 0} && po == std::vector<int32_t>{3, K, 0};
+  std::printf("rows, empty middle slot: %s\n", ok ? "ok" : "wrong rows");
+  if (!ok) fail("rows, empty middle slot");
+  Probes e;
+  e.slot({});
+  e.slot({});
+  const kp_probes ev = e.view();
+  kp_probe_rows(2, &ev, trip, po);
+  std::printf("rows, no probes: %s\n", trip.empty() && po.empty() ? "ok" : "wrong rows");
+  if (!trip.empty() || !po.empty()) fail("rows, no probes");
+}
+
 uint32_t rnd_state = 12345u;
 int rnd(int n) {  // [0, n)
   rnd_state = rnd_state * 1664525u + 1013904223u;
@@ -170,6 +189,7 @@ void random_sets() {
 
 int main() {
   errors();
+  rank_rows();
   random_sets();
   std::printf("%d failures\n", failures);
   return failures ? 1 : 0;

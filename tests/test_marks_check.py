@@ -7,7 +7,9 @@ under the host sanitizers.
 check once and requires that rule's message, compares the plan with hand-derived ones (slots
 of 1, 2 and 3 steps per epoch and an empty slot in one batch, the marks {0}, {E} and all of
 0..15, ConvE's pair counts with a last step of one pair) and, on 400 pseudo-random batches,
-with a second statement of the rule.  No kernel runs: a malformed request never reaches a GPU."""
+with a second statement of the rule; it expands two slots by two marks into rank rows (one
+slot's filter list empty) and requires that 2^31 and 2^32 filter entries, reached by the
+offsets alone, are refused.  No kernel runs: a malformed request never reaches a GPU."""
 import os
 import shutil
 import subprocess
@@ -41,6 +43,11 @@ def test_marks_check(target):
     assert "random batches: 400" in lines and "good: ok" in lines, p.stdout
     for plan in PLANS:
         assert f"{plan}: ok" in lines, (plan, p.stdout)
+    for rows in ("rows 2 x 2, one empty filter", "rows without a filter"):
+        assert f"{rows}: ok" in lines, (rows, p.stdout)
+    for case in ("rows: 2^31 filter entries", "rows: 2^32 filter entries"):
+        assert f"{case}: the mark rows' filter lists exceed 2^31 - 1 entries" in lines, (case, p.stdout)
+    assert "rows: too many: too many mark rows" in lines, p.stdout
     # every rule was broken at least once and reported
     told = [ln.rsplit(": ", 1)[1] for ln in lines if ": " in ln]
     assert all(m in told for m in MESSAGES), p.stdout

@@ -14,14 +14,19 @@
    at the score tolerance and the rank rule;
 5. KP_MARKS_CHUNK=16 with five marks: bitwise the unchunked call;
 6. a fresh context gives the same marks bitwise;
-7. malformed marks are host errors raised before any device work;
-8. every post-training of the reference fixture: score, rank and, in every family, the rows
+7. malformed marks are host errors raised before any device work, and a call that breaks two
+   rules at once reports the one checked first (batch, top-k, probes, trace, marks);
+8. both sets of rank rows chunked at once (KP_PROBE_CHUNK=16 and KP_MARKS_CHUNK=16, each set
+   with a partial last chunk), with the lists and the trace: bitwise the unchunked call;
+9. every post-training of the reference fixture: score, rank and, in every family, the rows
    against the reference's fp64 run.
 
 Run on an MI355X: ``python -m pytest tests -m gpu``.
 """
 import ctypes as C
 import functools
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -29,6 +34,9 @@ import pytest
 import marks_cases as mc
 import width_cases as wc
 from kelpie_amd import _lib
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+from extras_digest import probes_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -179,6 +187,15 @@ def test_definition_mixed_steps(case):
 
 
 # ----------------------------------------------------------------------------- 5. chunks, 6. rerun
+def _twice(args):
+    """The batch twice over: its slots, then the same slots again."""
+    hp, x0, row_off, rows, rng_off, rng, pred, filt_off, filt = args
+    return (hp, np.vstack([x0, x0]), np.concatenate([row_off, row_off[1:] + row_off[-1]]), np.vstack([rows, rows]),
+            np.concatenate([rng_off, rng_off[1:] + rng_off[-1]]), np.concatenate([rng[:rng_off[-1]]] * 2),
+            np.vstack([pred, pred]), np.concatenate([filt_off, filt_off[1:] + filt_off[-1]]),
+            np.concatenate([filt[:filt_off[-1]]] * 2))
+
+
 @pytest.mark.parametrize("case", FAMILY, ids=mc.ids(FAMILY))
 def test_chunks_and_rerun(case, monkeypatch):
     batches, model = _device(case["id"])
@@ -188,11 +205,7 @@ def test_chunks_and_rerun(case, monkeypatch):
     monkeypatch.setenv("KP_MARKS_CHUNK", "16")
     assert len(b["args"][2]) - 1 == 3 and 3 * len(marks) < 16
     # 15 rows fit one chunk of 16: the batch twice over makes 30 rows, slot 3's marks straddle
-    hp, x0, row_off, rows, rng_off, rng, pred, filt_off, filt = b["args"]
-    twice = (hp, np.vstack([x0, x0]), np.concatenate([row_off, row_off[1:] + row_off[-1]]), np.vstack([rows, rows]),
-             np.concatenate([rng_off, rng_off[1:] + rng_off[-1]]), np.concatenate([rng[:rng_off[-1]]] * 2),
-             np.vstack([pred, pred]), np.concatenate([filt_off, filt_off[1:] + filt_off[-1]]),
-             np.concatenate([filt[:filt_off[-1]]] * 2))
+    twice = _twice(b["args"])
     chunked = _call(model, {"args": twice}, marks=marks)
     monkeypatch.delenv("KP_MARKS_CHUNK")
     unchunked = _call(model, {"args": twice}, marks=marks)
@@ -255,6 +268,107 @@ def test_errors_are_host_errors(case, monkeypatch):
         assert rc == -95 and "marks need the fp64 rank" in err, (rc, err)
         rc, err = _raw(f32, args, [0, 2, 2])
         assert rc == -22, (rc, err)  # malformed first
+
+
+def _two_faults(ctx, args, faults, empty=False):
+    """kp_posttrain_rank_marks on the batch (``empty``: with n_slots = 0) with the requests named
+    in ``faults`` malformed and the others absent: "k" = 33, "probes" whose probe_off starts at 1,
+    "trace" without trace_off, "marks" with n = 0; "hp": batch_size = 0."""
+    hp, x0, row_off, rows, rng_off, rng, pred, filt_off, filt = args
+    n = len(row_off) - 1
+    hp = type(hp).from_buffer_copy(hp)
+    if "hp" in faults:
+        hp.batch_size = 0
+    keep = [np.ascontiguousarray(x0, np.float32), np.ascontiguousarray(row_off, np.int32),
+            np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(rng_off, np.int64),
+            np.ascontiguousarray(rng, np.int32), np.ascontiguousarray(pred, np.int32),
+            np.ascontiguousarray(filt_off, np.int32), np.ascontiguousarray(filt, np.int32),
+            np.zeros(n, np.float32), np.zeros(n, np.int64), np.ones(n + 1, np.int32), np.zeros(2, np.int32),
+            np.zeros(1, np.float32), np.zeros(1, np.int64), np.zeros((n, 33), np.int32), np.zeros((n, 33), np.float32)]
+    p = [_lib._ptr(a) for a in keep]
+    b = _lib.Batch(0 if empty else n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], None, p[8], p[9])
+    pr = _lib.Probes(1, p[10], p[11], p[11], p[11], p[12], p[13]) if "probes" in faults else None
+    tr = _lib.Trace(None, None) if "trace" in faults else None
+    mk = _lib.Marks(0, p[11], p[12], p[13], None) if "marks" in faults else None
+    ref = lambda st: C.byref(st) if st is not None else None  # noqa: E731
+    k = 33 if "k" in faults else 0
+    rc = _lib.lib().kp_posttrain_rank_marks(ctx.h, C.byref(hp), C.byref(b), k, p[14] if k else None,
+                                            p[15] if k else None, ref(pr), ref(tr), ref(mk))
+    return rc, _lib.lib().kp_last_error(ctx.h).decode()
+
+
+# what the library answered to each pair of faults before the request checks were joined into
+# one function (profiles/extras_refactor/two_faults_parent.txt): (faults, n_slots = 0) ->
+# message, "{m}" the family's name
+TWO_FAULTS = {
+    (("k", "probes"), False): "{m}: top-k: k must be in [0, 32]",
+    (("k", "probes"), True): "kp_posttrain_rank_topk: k must be in [0, 32]",
+    (("probes", "trace"), False): "{m}: probes: probe_off must start at 0",
+    (("probes", "trace"), True): "kp_posttrain_rank_probes: probes without a slot",
+    (("trace", "marks"), False): "{m}: trace: missing trace_off",
+    (("trace", "marks"), True): "{m}: trace: missing trace_off",
+    # without a slot no family runs, and none refuses its hyper-parameters
+    (("probes", "hp"), True): "kp_posttrain_rank_probes: probes without a slot",
+    (("hp", "trace"), True): "{m}: trace: batch_size must be positive",
+    (("hp", "marks"), True): "{m}: marks: n must be in [1, 16]",
+    (("k", "hp"), True): "kp_posttrain_rank_topk: k must be in [0, 32]",
+}
+# ComplEx / DistMult refuse batch_size = 0 before the request, ConvE between the probes and the
+# trace, TransE after the request (where the trace's own rule has already refused it)
+_CX_HP = "{m}: bad batch_size/epochs"
+HP_FAULTS = {
+    (("probes", "hp"), False): {"ComplEx": _CX_HP, "DistMult": _CX_HP, "ConvE": "{m}: probes: probe_off must start at 0",
+                                "TransE": "{m}: probes: probe_off must start at 0"},
+    (("hp", "trace"), False): {"ComplEx": _CX_HP, "DistMult": _CX_HP, "ConvE": "{m}: bad hyper-parameters",
+                               "TransE": "{m}: trace: batch_size must be positive"},
+    (("hp", "marks"), False): {"ComplEx": _CX_HP, "DistMult": _CX_HP, "ConvE": "{m}: bad hyper-parameters",
+                               "TransE": "{m}: marks: n must be in [1, 16]"},
+    (("k", "hp"), False): {"ComplEx": _CX_HP, "DistMult": _CX_HP, "ConvE": "{m}: top-k: k must be in [0, 32]",
+                           "TransE": "{m}: top-k: k must be in [0, 32]"},
+}
+
+
+@pytest.mark.parametrize("case", FAMILY, ids=mc.ids(FAMILY))
+def test_two_faults_report_the_first(case):
+    """A call that breaks two rules reports the one checked first: batch, top-k, probes, trace,
+    marks, with each family's hyper-parameter check at its own place among them."""
+    batches, model = _device(case["id"])
+    args = batches[0]["args"]
+    ctx = model.ctx._ctx
+    m = case["model"]
+    table = dict(TWO_FAULTS)
+    table.update({key: msgs[m] for key, msgs in HP_FAULTS.items()})
+    for (faults, empty), msg in table.items():
+        rc, err = _two_faults(ctx, args, faults, empty)
+        assert rc == -22 and err == msg.format(m=m), (faults, empty, rc, err)
+    rc, _ = _raw(ctx, args, [0, 2])
+    assert rc == 0  # the context stays usable
+
+
+# ----------------------------------------------------------------------------- 8. both row sets chunked
+@pytest.mark.parametrize("case", FAMILY, ids=mc.ids(FAMILY))
+def test_both_row_sets_chunked(case, monkeypatch):
+    """Six slots, three probes and five marks each: 18 probe rows and 30 mark rows, each more
+    than one chunk of 16 and no multiple of it, the smallest shape at which the two sets, each
+    with a partial last chunk, could disturb one another."""
+    batches, model = _device(case["id"])
+    args = _twice(batches[0]["args"])
+    n = len(args[2]) - 1
+    marks = [0, 1, 2, 5, 8]
+    probes = probes_of(args, model.ctx.n_ent, per_slot=3)
+    for rows in (len(probes[1]), n * len(marks)):
+        assert rows > 16 and rows % 16 != 0
+    kw = {"topk": 5, "probes": probes, "trace": True, "marks": marks}
+    whole = _call(model, {"args": args}, **kw)
+    monkeypatch.setenv("KP_PROBE_CHUNK", "16")
+    monkeypatch.setenv("KP_MARKS_CHUNK", "16")
+    chunked = _call(model, {"args": args}, **kw)
+    s, r, x, lists, probed, losses, marked = whole
+    s2, r2, x2, lists2, probed2, losses2, marked2 = chunked
+    for a, c in zip((s, r, x) + lists + probed + marked, (s2, r2, x2) + lists2 + probed2 + marked2):
+        assert _same(a, c)
+    assert len(losses) == len(losses2) == n and all(_same(a, c) for a, c in zip(losses, losses2))
+    assert sum(len(v) for v in losses) > 0 and (lists[0] >= 0).any() and len(probed[0]) == 18
 
 
 # ----------------------------------------------------------------------------- the reference fixture

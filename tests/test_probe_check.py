@@ -5,7 +5,8 @@ the host sanitizers.
 ``tests/native/probe_check_driver.cpp``, once plain and once with
 ``-fsanitize=address,undefined``.  The driver passes a good set of probes (an empty slot
 between full ones; no probes at all with null arrays), breaks each rule of the check once in
-the good set and requires that rule's message, and on 400 pseudo-random valid sets requires
+the good set and requires that rule's message, expands the good set into rank rows (the
+empty slot between two that have probes), and on 400 pseudo-random valid sets requires
 that the check passes and that the chunks cover every probe row once, in whole groups of 16
 rows, within their budget (or as KP_PROBE_CHUNK forces them).  No kernel runs: malformed
 probes never reach a GPU."""
@@ -41,6 +42,7 @@ def test_probe_check(target):
     assert lines[-1] == "0 failures" and "FAIL" not in p.stdout, p.stdout
     assert "random sets: 400" in lines, p.stdout
     assert "good: ok" in lines and "no probes, null arrays: ok" in lines, p.stdout
+    assert "rows, empty middle slot: ok" in lines and "rows, no probes: ok" in lines, p.stdout
     # every rule was broken at least once and reported
     told = [ln.split(": ", 1)[1] for ln in lines if ": " in ln]
     assert all(m in told for m in MESSAGES), p.stdout
