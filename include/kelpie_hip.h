@@ -49,7 +49,7 @@ extern "C" {
 /* DistMult (src/link_prediction/models/distmult.py:38-68; the reference leaves it out of its
  * registry): plain [d] float rows, score (lhs * rel) . rhs, maximizer, post-trained by the
  * ComplEx optimizer (multiclass_nll_optimizer.py:57-164).  Rows of at most 400 floats;
- * kp_posttrain_rank, kp_all_scores, kp_convertible and kp_predict_tails serve it,
+ * kp_posttrain_rank (and kp_posttrain_rank_f64), kp_all_scores, kp_convertible and kp_predict_tails serve it,
  * kp_train_epoch, kp_dp_relevance and kp_criage_relevance do not. */
 #define KP_MODEL_DISTMULT 3
 
@@ -305,6 +305,42 @@ typedef struct {
 int kp_posttrain_rank_marks(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
                             float* out_scores, const kp_probes* probes, const kp_trace* trace,
                             const kp_marks* marks);
+
+/* ---- fp64: post-train and rank in double precision on the device (ComplEx, DistMult) ----
+ * The fp64 result of a slot is what the reference returns when every tensor of the run is a
+ * float64 one (the `fp64` variant of tools/conditioning.py):
+ *   - the frozen tables are the fp32 tables upcast (exact);
+ *   - the kelpie init is drawn in fp32, upcast, and multiplied by init_scale in fp64: x0 below;
+ *   - every hyper-parameter is the Python double (0.01, not (float)0.01);
+ *   - the row, the query, the logits, the softmax, the gradient, the N3 / N2 term, the
+ *     optimizer state and the update are all fp64, in torch's op order;
+ *   - the draws are those of the fp32 run (kp_batch.rng_off / rng), so the generators end
+ *     in the same state in either precision;
+ *   - the score and the rank come from the fp64 row.
+ * Nothing is rounded to fp32 anywhere between x0 and the outputs.  The device sums its
+ * contractions in its own fixed order (an fp64 MFMA attention over the frozen entities whose
+ * key ranges merge by log-sum-exp in range order), so it agrees with the reference's fp64
+ * run to fp64 rounding, not bit for bit; a rerun on a fresh context is bitwise equal.
+ *   x0          [n_slots][dim]   the initial kelpie rows in fp64 (kp_batch.x0 is ignored)
+ *   lr .. reg_weight             take precedence over kp_hp's floats; the integers of kp_hp
+ *                                (optimizer, epochs, batch_size, reg_kind) are read from it
+ *   out_x       [n_slots][dim]   the final kelpie rows (may be NULL)
+ *   out_score   [n_slots]        the fp64 target score itself */
+typedef struct {
+  const double* x0;
+  double lr, beta1, beta2, eps, reg_weight;
+  double* out_x;
+  double* out_score;
+} kp_f64;
+
+/* kp_posttrain_rank in fp64 by the definition above.  batch->out_rank is the rank output;
+ * batch->x0, batch->out_x and batch->out_score are not read or written and may be NULL.
+ * Refusals, in this order: the batch check (KP_EINVAL); a NULL r, r->x0 or r->out_score
+ * (KP_EINVAL); a context that is not ComplEx / DistMult (KP_ENOTSUP, before any upload).
+ * The fp32 rank switches do not apply to these families.  Top-k lists, probes, the trace
+ * and the marks are not offered on this entry point.  The call uses workspaces of its own:
+ * a context that has served it returns bitwise the fp32 results of a fresh one afterwards. */
+int kp_posttrain_rank_f64(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, const kp_f64* r);
 
 /* Model.all_scores (model.py:19; transe.py:48-65, complex.py:88-112,
  * conve.py:133-158) for n (head, relation) pairs over the frozen entities:

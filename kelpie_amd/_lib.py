@@ -31,7 +31,7 @@ EXPORTS = ["kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_posttrain_ran
            "kp_gather_i32", "kp_rng_transe_calls_async", "kp_rng_torch_take", "kp_conve_train_begin",
            "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free", "kp_ctx_set_inflight",
            "kp_last_attn_plan", "kp_posttrain_rank_topk", "kp_posttrain_rank_probes", "kp_trace_steps",
-           "kp_posttrain_rank_trace", "kp_posttrain_rank_marks"]
+           "kp_posttrain_rank_trace", "kp_posttrain_rank_marks", "kp_posttrain_rank_f64"]
 
 
 class ModelDesc(C.Structure):
@@ -50,6 +50,24 @@ class HP(C.Structure):
 
 
 KP_REG = {"N3": 0, "N2": 1}
+
+
+class F64(C.Structure):
+    """kp_f64: the double inputs, hyper-parameters and outputs of kp_posttrain_rank_f64."""
+    _fields_ = [("x0", C.c_void_p), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("reg_weight", C.c_double), ("out_x", C.c_void_p), ("out_score", C.c_void_p)]
+
+
+class HP64(NamedTuple):
+    """The double form of ``HP`` for ``Context.posttrain_rank_f64``: ``hp`` carries the integers
+    (optimizer, epochs, batch_size, reg_kind) and the float32 roundings, the doubles here take
+    precedence over those (include/kelpie_hip.h, "fp64": 0.01, not (float)0.01)."""
+    hp: HP
+    lr: float
+    beta1: float
+    beta2: float
+    eps: float
+    reg_weight: float
 
 
 class Batch(C.Structure):
@@ -129,6 +147,8 @@ def lib():
         if hasattr(L, "kp_posttrain_rank_marks"):  # KELPIE_HIP_LIB may name a build from before the marks
             L.kp_posttrain_rank_marks.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
                                                   C.c_void_p, C.POINTER(Probes), C.POINTER(Trace), C.POINTER(Marks)]
+        if hasattr(L, "kp_posttrain_rank_f64"):  # KELPIE_HIP_LIB may name a build from before the fp64 path
+            L.kp_posttrain_rank_f64.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.POINTER(F64)]
         L.kp_all_scores.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kp_convertible.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
@@ -537,6 +557,30 @@ class Context:
             rc = lib().kp_posttrain_rank_topk(*head)
         check(rc, self.h)
         return ret
+
+    def posttrain_rank_f64(self, hp64: HP64, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False):
+        """kp_posttrain_rank_f64: (target scores float64, ranks, final rows float64 or None) of
+        the batch post-trained and ranked in fp64 on the device (ComplEx, DistMult).  ``x0`` is
+        the float64 init (``MultiClassNLLModel.kelpie_init64``); the other arrays are
+        ``posttrain_rank``'s, the draws included."""
+        n = len(row_off) - 1
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        rng_off = np.ascontiguousarray(rng_off, dtype=np.int64)
+        rng = np.ascontiguousarray(rng, dtype=np.int32)
+        pred = np.ascontiguousarray(pred, dtype=np.int32)
+        filt_off = np.ascontiguousarray(filt_off, dtype=np.int32)
+        filt = np.ascontiguousarray(filt, dtype=np.int32)
+        out_x = np.zeros((n, self.dim), np.float64) if want_x else None
+        out_s = np.zeros(n, np.float64)
+        out_r = np.zeros(n, np.int64)
+        b = Batch(n, None, _ptr(row_off), _ptr(rows), _ptr(rng_off), _ptr(rng), _ptr(pred), _ptr(filt_off),
+                  _ptr(filt), None, None, _ptr(out_r))
+        r = F64(_ptr(x0), float(hp64.lr), float(hp64.beta1), float(hp64.beta2), float(hp64.eps),
+                float(hp64.reg_weight), _ptr(out_x), _ptr(out_s))
+        check(lib().kp_posttrain_rank_f64(self.h, C.byref(hp64.hp), C.byref(b), C.byref(r)), self.h)
+        return out_s, out_r, out_x
 
     def all_scores(self, heads, rels):
         heads = np.ascontiguousarray(heads, dtype=np.int32)

@@ -262,6 +262,27 @@ int kp_posttrain_rank_marks(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32
   return posttrain_rank_call(c, hp, b, k, out_ids, out_scores, probes, trace, marks);
 }
 
+// kp_posttrain_rank in fp64 (include/kelpie_hip.h, "fp64"): the request carries the double
+// inputs and outputs; ComplEx / DistMult run it (kp_complex.hip), the other families are
+// refused by require_request after the batch check and before any upload
+int kp_posttrain_rank_f64(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const kp_f64* r) {
+  if (!c || !hp || !b) return KP_EINVAL;
+  static const kp_f64 none{};  // a NULL request is refused where a NULL x0 is: after the batch check
+  PostReq rq;
+  rq.f64 = r ? r : &none;
+  return guarded(c, [&] {
+    KP_REQUIRE(b->n_slots >= 0, "kp_posttrain_rank_f64: negative n_slots");
+    if (b->n_slots == 0) return require_request(c, hp, b, rq, true, kp_model_name(c->model));
+    KP_REQUIRE(b->row_off && b->pred && b->filt_off && b->out_rank, "kp_posttrain_rank_f64: missing buffer");
+    KP_HIP(hipSetDevice(c->device));
+    switch (c->model) {
+      case KP_MODEL_COMPLEX: complex_posttrain_rank(c, hp, b, rq); break;
+      case KP_MODEL_DISTMULT: distmult_posttrain_rank(c, hp, b, rq); break;
+      default: require_request(c, hp, b, rq, true, kp_model_name(c->model)); break;  // throws
+    }
+  });
+}
+
 // the steps of every slot (kp_trace_check.hpp): host work only
 int kp_trace_steps(int32_t model, const kp_hp* hp, int32_t n_slots, const int32_t* row_off, const int32_t* rows,
                    int32_t* out_steps) {

@@ -136,6 +136,16 @@ struct RankRowsWs {
 };
 KP_WS_COMPLETE(RankRowsWs);
 
+// kp_posttrain_rank_f64's rank inputs and buffers: the same roles as RankWs's own, kept apart
+// so that an fp64 call leaves every buffer of the fp32 path as it was
+struct Rank64Ws {
+  DevBuf pred, po, filt_off, filt;  // the ranked triples, their objects, the filter CSR
+  DevBuf target, rank;              // [ns] the converted target (unused by the caller) and the ranks
+  DevBuf q64, t64, bits;            // fp64 ranking queries, target | kelpie column scores, filter bitmaps
+  auto all() { return std::array{&pred, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &bits}; }
+};
+KP_WS_COMPLETE(Rank64Ws);
+
 // what every *_posttrain_rank shares (kp_posttrain.hpp fills it): the rank of the
 // post-trained rows, the two sets of rank rows and the trace.
 // Two borrowers outside a post-training call, kept so that a context allocates what it
@@ -160,13 +170,32 @@ struct RankWs {
   // workspace [ns][marks][dp], with the slot's filter list.  Neither set reuses the slots'
   // buffers above or the other's: the earlier downloads are still pending when a set ranks
   RankRowsWs probes, marks;
+  Rank64Ws f64;  // kp_posttrain_rank_f64
   auto all() {
     return kp_join(std::array{&pred, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &scores, &bits, &cand_key,
                               &cand_col, &top_ids, &top_scores, &tr_off, &tr_loss},
-                   probes.all(), marks.all());
+                   probes.all(), marks.all(), f64.all());
   }
 };
 KP_WS_COMPLETE(RankWs);
+
+// kp_complex.hip, kp_posttrain_rank_f64: the fp64 step's own workspaces (rows, optimizer state,
+// the plan's uploads, contributions, target sums, pair queries and attention partials in
+// double), none shared with the fp32 path
+struct Complex64Ws {
+  DevBuf x, s1, s2;                // kelpie rows [ns][dp] and their moments, double
+  DevBuf plans, queries, targets;  // the step plan's uploads, as ComplexWs's
+  DevBuf pairs, acts, stepq, stept;
+  DevBuf contrib;                  // per-step gradient contributions [items][dp], double
+  DevBuf tsum, qpair, lsef;        // target sums, pair queries, their frozen lse, double
+  DevBuf am, al, ao;               // kp_attn64's partials per key range (max, sum, output), double
+  DevBuf qs;                       // the step's queries [nq][dp], double
+  auto all() {
+    return std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
+                      &tsum, &qpair, &lsef, &am, &al, &ao, &qs};
+  }
+};
+KP_WS_COMPLETE(Complex64Ws);
 
 // kp_complex.hip
 struct ComplexWs {
@@ -185,10 +214,12 @@ struct ComplexWs {
   // kp_posttrain_rank_marks: the mark rows [ns][marks][dp] and, per entry of acts, the mark
   // row its update also stores (-1: none)
   DevBuf marks, mark_row;
+  Complex64Ws f64;  // kp_posttrain_rank_f64
   auto all() {
-    return std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
-                      &tsum, &qpair, &lsef, &am, &al, &ao, &qs, &score_q, &score_out, &tr_term, &tr_fe, &tr_fr,
-                      &marks, &mark_row};
+    return kp_join(std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
+                              &tsum, &qpair, &lsef, &am, &al, &ao, &qs, &score_q, &score_out, &tr_term, &tr_fe,
+                              &tr_fr, &marks, &mark_row},
+                   f64.all());
   }
 };
 KP_WS_COMPLETE(ComplexWs);
@@ -398,6 +429,10 @@ struct PostReq {
   // kp_posttrain_rank_marks' request (nullptr: no marks)
   const kp_marks* marks = nullptr;
   int n_marks() const { return marks ? marks->n : 0; }
+  // kp_posttrain_rank_f64's request (nullptr: the fp32 / bf16x3 step): the double inputs,
+  // hyper-parameters and outputs.  ComplEx / DistMult; the lists, the probes, the trace and
+  // the marks are not offered with it yet (require_request)
+  const kp_f64* f64 = nullptr;
 };
 void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const PostReq& rq = {});
 // kp_complex.hip, product policy

@@ -34,6 +34,7 @@
 
 #include "kp_attn.hpp"
 #include "kp_attn3.hpp"
+#include "kp_attn64.hpp"
 #include "kp_cx_plan.hpp"
 #include "kp_posttrain.hpp"
 
@@ -47,6 +48,18 @@ __device__ __forceinline__ double cx_q64(const float* __restrict__ lhs, const fl
   if (d < 2 * half) {
     const int i = d - half;
     return (double)lhs[i] * (double)rel[d] + (double)lhs[d] * (double)rel[i];
+  }
+  return 0.0;
+}
+
+// kp_posttrain_rank_f64: the same product on an fp64 left operand (the kelpie row), each
+// product and the sum rounded once, as torch's float64 ops round them (complex.py:65-72)
+__device__ __forceinline__ double cx_q64(const double* __restrict__ lhs, const float* __restrict__ rel, int d,
+                                         int half) {
+  if (d < half) return lhs[d] * (double)rel[d] - lhs[d + half] * (double)rel[d + half];
+  if (d < 2 * half) {
+    const int i = d - half;
+    return lhs[i] * (double)rel[d] + lhs[d] * (double)rel[i];
   }
   return 0.0;
 }
@@ -69,6 +82,19 @@ struct CxProd {  // ComplEx (complex.py:59-112)
   static __device__ __forceinline__ double q64(const float* __restrict__ lhs, const float* __restrict__ rel, int d,
                                                int w) {
     return cx_q64(lhs, rel, d, w);
+  }
+  static __device__ __forceinline__ double q64(const double* __restrict__ lhs, const float* __restrict__ rel, int d,
+                                               int w) {
+    return cx_q64(lhs, rel, d, w);
+  }
+  static __device__ __forceinline__ double mod64(const double* xv) { return sqrt(xv[0] * xv[0] + xv[1] * xv[1]); }
+  static __device__ __forceinline__ void emit(double* __restrict__ out, int i, int w, const double* xv,
+                                              const double* rv, const double* dv, double cf) {
+    const double a = xv[0], b = xv[1], cc = rv[0], ee = rv[1];
+    const double dre = dv[0], dim_ = dv[1];
+    const double qre = a * cc - b * ee, qim = a * ee + b * cc;
+    out[i] = dre * cc + dim_ * ee + cf * qre;
+    out[i + w] = -dre * ee + dim_ * cc + cf * qim;
   }
   // the factor of one (re, im) pair: the complex modulus (complex.py:80-84)
   static __device__ __forceinline__ float mod(const float* xv) { return sqrtf(xv[0] * xv[0] + xv[1] * xv[1]); }
@@ -97,6 +123,16 @@ struct DmProd {  // DistMult (distmult.py:38-68): plain [d] rows, q = lhs * rel
                                                int w) {
     return d < w ? (double)lhs[d] * (double)rel[d] : 0.0;
   }
+  static __device__ __forceinline__ double q64(const double* __restrict__ lhs, const float* __restrict__ rel, int d,
+                                               int w) {
+    return d < w ? lhs[d] * (double)rel[d] : 0.0;
+  }
+  static __device__ __forceinline__ double mod64(const double* xv) { return fabs(xv[0]); }
+  static __device__ __forceinline__ void emit(double* __restrict__ out, int i, int w, const double* xv,
+                                              const double* rv, const double* dv, double cf) {
+    const double q = xv[0] * rv[0];
+    out[i] = dv[0] * rv[0] + cf * q;
+  }
   // the factor of one coordinate: |x_i| (distmult.py:66, sqrt(x_i^2))
   static __device__ __forceinline__ float mod(const float* xv) { return fabsf(xv[0]); }
   static __device__ __forceinline__ double mod64(const float* xv) { return fabs((double)xv[0]); }
@@ -108,16 +144,26 @@ struct DmProd {  // DistMult (distmult.py:38-68): plain [d] rows, q = lhs * rel
   }
 };
 
-// qpair[p] = E[h] o R[r] for the frozen-head rows
-template <class Prod>
+// the product in the precision of the row it is stored to: fp32 (Prod::q), or fp64 for
+// kp_posttrain_rank_f64's double rows (Prod::q64)
+template <class Prod, class QT, class LT>
+__device__ __forceinline__ QT cx_q_as(const LT* __restrict__ lhs, const float* __restrict__ rel, int d, int w) {
+  if constexpr (sizeof(QT) == sizeof(double))
+    return Prod::q64(lhs, rel, d, w);
+  else
+    return Prod::q(lhs, rel, d, w);
+}
+
+// qpair[p] = E[h] o R[r] for the frozen-head rows (QT: the stored row's type)
+template <class Prod, class QT = float>
 __global__ void kp_cx_qpair(const float* __restrict__ E, const float* __restrict__ R, int dp, int half,
-                            const int2* __restrict__ pairs, int n_pairs, float* __restrict__ out) {
+                            const int2* __restrict__ pairs, int n_pairs, QT* __restrict__ out) {
   int p = blockIdx.x;
   if (p >= n_pairs) return;
   int2 hr = pairs[p];
   const float* lhs = E + (size_t)hr.x * dp;
   const float* rel = R + (size_t)hr.y * dp;
-  for (int d = threadIdx.x; d < dp; d += blockDim.x) out[(size_t)p * dp + d] = Prod::q(lhs, rel, d, half);
+  for (int d = threadIdx.x; d < dp; d += blockDim.x) out[(size_t)p * dp + d] = cx_q_as<Prod, QT>(lhs, rel, d, half);
 }
 
 // lsef[p] = the frozen-head pair's log-sum-exp over the frozen entities, merged from the
@@ -590,13 +636,14 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
 // sequential fp64 FMA chain over d (the order kp_rank_f64_count scores every entity in).
 // PROBE (kp_posttrain_rank_probes): row s is a probe, pred its (slot, p, o), and x the
 // kelpie row of that slot instead of row s; every operation and its order are the slot form's
-template <int DP, class Prod, bool PROBE = false>
-__global__ void kp_cx_rankq64(const float* __restrict__ X, const float* __restrict__ R, const float* __restrict__ E,
+// XT: the kelpie rows' type (double: kp_posttrain_rank_f64, whose row is never rounded)
+template <int DP, class Prod, bool PROBE = false, class XT = float>
+__global__ void kp_cx_rankq64(const XT* __restrict__ X, const float* __restrict__ R, const float* __restrict__ E,
                               int n_ent, int half, const int32_t* __restrict__ pred, int n_slots,
                               double* __restrict__ Q, double* __restrict__ t64, double* __restrict__ kcol64) {
   const int s = blockIdx.x;
   if (s >= n_slots) return;
-  const float* x = X + (size_t)(PROBE ? pred[3 * s] : s) * DP;
+  const XT* x = X + (size_t)(PROBE ? pred[3 * s] : s) * DP;
   const float* rel = R + (size_t)pred[3 * s + 1] * DP;
   double* q = Q + (size_t)s * DP;
   for (int d = threadIdx.x; d < DP; d += blockDim.x) q[d] = Prod::q64(x, rel, d, half);
@@ -631,21 +678,22 @@ __global__ void kp_cx_scoreq(const float* __restrict__ E, const float* __restric
 // host side
 // ----------------------------------------------------------------------------
 // step queries q_j = x_slot o R_rel (complex.py:65-72), one row per step query
-template <int DP, class Prod>
-__global__ void kp_cx_stepq(const float* __restrict__ X, const float* __restrict__ R, int half,
-                            const int4* __restrict__ stepq, int nq, float* __restrict__ Q) {
+// (XT: the rows' and the queries' type; double: kp_posttrain_rank_f64)
+template <int DP, class Prod, class XT = float>
+__global__ void kp_cx_stepq(const XT* __restrict__ X, const float* __restrict__ R, int half,
+                            const int4* __restrict__ stepq, int nq, XT* __restrict__ Q) {
   const int j = blockIdx.x;
   if (j >= nq) return;
   const int4 sq = stepq[j];
-  const float* x = X + (size_t)sq.x * DP;
+  const XT* x = X + (size_t)sq.x * DP;
   const float* rel = R + (size_t)sq.y * DP;
-  for (int d = threadIdx.x; d < DP; d += blockDim.x) Q[(size_t)j * DP + d] = Prod::q(x, rel, d, half);
+  for (int d = threadIdx.x; d < DP; d += blockDim.x) Q[(size_t)j * DP + d] = cx_q_as<Prod, XT>(x, rel, d, half);
 }
 
-template <int DB, class Prod>
-void launch_stepq(kp_ctx* c, const int4* stepq, const float* X, int nq, float* Q) {
+template <int DB, class Prod, class XT = float>
+void launch_stepq(kp_ctx* c, const int4* stepq, const XT* X, int nq, XT* Q) {
   if (nq <= 0) return;
-  hipLaunchKernelGGL((kp_cx_stepq<16 * DB, Prod>), dim3(nq), dim3(64), 0, c->stream, X, c->dR, Prod::extent(c->dim), stepq,
+  hipLaunchKernelGGL((kp_cx_stepq<16 * DB, Prod, XT>), dim3(nq), dim3(64), 0, c->stream, X, c->dR, Prod::extent(c->dim), stepq,
                      nq, Q);
   KP_HIP(hipGetLastError());
 }
@@ -723,10 +771,10 @@ void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, c
   KP_HIP(hipGetLastError());
 }
 
-template <int DB, class Prod>
-void launch_rankq64(kp_ctx* c, const float* X, const int32_t* pred, int n, double* Q, double* t64, double* kcol64) {
+template <int DB, class Prod, class XT = float>
+void launch_rankq64(kp_ctx* c, const XT* X, const int32_t* pred, int n, double* Q, double* t64, double* kcol64) {
   if (n <= 0) return;
-  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod>), dim3(n), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
+  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod, false, XT>), dim3(n), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
                      Prod::extent(c->dim), pred, n, Q, t64, kcol64);
   KP_HIP(hipGetLastError());
 }
@@ -928,6 +976,408 @@ int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxD
   return hot_launches;
 }
 
+// ============================================================================
+// kp_posttrain_rank_f64 (include/kelpie_hip.h, "fp64"): the same decomposition with the row,
+// the queries, the attention (kp_attn64.hpp), the merge, the gradient, the regulariser term,
+// the optimizer state and the update in fp64.  The small kernels above are compiled over the
+// row type (kp_cx_stepq, kp_cx_qpair, kp_cx_rankq64); the merge and the update are the forms
+// below: one partial per key range merged in range order where the fp32 form merges one per
+// lane, and no trace or mark arguments.  Every sum has a fixed order.
+// ============================================================================
+struct CxOpt64 {
+  int kind;
+  double lr, b2, eps;
+  double one_minus_b1, one_minus_b2;
+  double step_size;  // Adam: lr / (1 - b1^t)
+  double bc2_sqrt;   // Adam: sqrt(1 - b2^t)
+  double reg_w;
+  int reg_n2;
+};
+
+__device__ __forceinline__ double wave_sum64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Tsum in fp64 (the targets in list order)
+__global__ void kp_cx_tsum64(const float* __restrict__ E, int dp, const CxQuery* __restrict__ pq, int nq,
+                             const int32_t* __restrict__ targets, double* __restrict__ tsum) {
+  int q = blockIdx.x;
+  if (q >= nq) return;
+  CxQuery Q = pq[q];
+  for (int d = threadIdx.x; d < dp; d += blockDim.x) {
+    double acc = 0.0;
+    for (int i = 0; i < Q.tg_count; ++i) acc += (double)E[(size_t)targets[Q.tg_begin + i] * dp + d];
+    tsum[(size_t)q * dp + d] = acc;
+  }
+}
+
+// the log-sum-exp over the frozen entities from kp_attn64's per-range (m, l), in range order;
+// m_out: the merged max.  An empty range (m = -inf) adds nothing.
+__device__ __forceinline__ double lse_ranges64(const double* __restrict__ am, const double* __restrict__ al, int n,
+                                               int ranges, int item) {
+  double mm = -__builtin_inf();
+  for (int s = 0; s < ranges; ++s) mm = fmax(mm, am[(size_t)s * n + item]);
+  double ll = 0.0;
+  for (int s = 0; s < ranges; ++s) {
+    const double ms = am[(size_t)s * n + item];
+    if (ms != -__builtin_inf()) ll += al[(size_t)s * n + item] * exp(ms - mm);
+  }
+  return mm + log(ll);
+}
+
+__global__ void kp_cx_lse_merge64(int npairs, int ranges, const double* __restrict__ am,
+                                  const double* __restrict__ al, double* __restrict__ lsef) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npairs) return;
+  lsef[p] = lse_ranges64(am, al, npairs, ranges, p);
+}
+
+// kp_cx_contrib in fp64: one wave per (query or frozen-head row) of the step.  The formulas
+// are kp_cx_contrib's; the ranges' partials O_s merge with the weights exp(m_s - lse), one
+// range after the other in range order.
+template <int DP, class Prod>
+__global__ __launch_bounds__(256) void kp_cx_contrib64(int half, const int4* __restrict__ stepq, int nq,
+                                                       const int4* __restrict__ stept, int nt,
+                                                       const CxQuery* __restrict__ pq, const double* __restrict__ X,
+                                                       const float* __restrict__ R, const double* __restrict__ Tsum,
+                                                       const double* __restrict__ Qpair,
+                                                       const double* __restrict__ lsef,
+                                                       const double* __restrict__ att_m,
+                                                       const double* __restrict__ att_l,
+                                                       const double* __restrict__ att_O, int ranges,
+                                                       double* __restrict__ contrib) {
+  const int lane = threadIdx.x & 63;
+  const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= nq + nt) return;
+  double* out = contrib + (size_t)item * DP;
+  constexpr int G = Prod::G;
+  if (item < nq) {
+    const int4 sq = stepq[item];  // slot, rel, plan-query index
+    const double* x = X + (size_t)sq.x * DP;
+    const float* rel = R + (size_t)sq.y * DP;
+    const CxQuery Q = pq[sq.z];
+    double z = 0.0;
+    for (int d = lane; d < G * half; d += 64) z += Prod::q64(x, rel, d, half) * x[d];
+    z = wave_sum64(z);
+    const double lse_f = lse_ranges64(att_m, att_l, nq, ranges, item);
+    const double hi = fmax(lse_f, z), lo = fmin(lse_f, z);
+    const double lse = hi + log1p(exp(lo - hi));
+    const double pk = exp(z - lse);
+    constexpr int NI = (DP / G + 63) / 64;
+    double o_k[NI][G];
+#pragma unroll
+    for (int k = 0; k < NI; ++k)
+#pragma unroll
+      for (int h = 0; h < G; ++h) o_k[k][h] = 0.0;
+    for (int sp = 0; sp < ranges; ++sp) {
+      const double ms = att_m[(size_t)sp * nq + item];
+      if (ms == -__builtin_inf()) continue;  // wave-uniform
+      const double w0 = exp(ms - lse);
+      const double* O0 = att_O + ((size_t)sp * nq + item) * DP;
+#pragma unroll
+      for (int k = 0; k < NI; ++k) {
+        const int i = lane + 64 * k;
+        if (i < half) {
+#pragma unroll
+          for (int h = 0; h < G; ++h) o_k[k][h] += w0 * O0[i + h * half];
+        }
+      }
+    }
+    const double fc = (double)Q.c, fck = (double)Q.ck;
+    const double cf = fc * pk - fck;
+    const double* ts = Tsum + (size_t)sq.z * DP;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+      const int i = lane + 64 * k;
+      if (i >= half) continue;
+      double xv[G], rv[G], dv[G];
+#pragma unroll
+      for (int h = 0; h < G; ++h) xv[h] = x[i + h * half];
+#pragma unroll
+      for (int h = 0; h < G; ++h) rv[h] = (double)rel[i + h * half];
+#pragma unroll
+      for (int h = 0; h < G; ++h) {
+        const double e = o_k[k][h] + pk * xv[h];  // <E>: the frozen part and the kelpie column
+        dv[h] = fc * e - ts[i + h * half] - fck * xv[h];
+      }
+      Prod::emit(out, i, half, xv, rv, dv, cf);
+    }
+  } else {
+    const int4 st = stept[item - nq];  // slot, pair, count
+    const double* x = X + (size_t)st.x * DP;
+    const double* qp = Qpair + (size_t)st.y * DP;
+    double z = 0.0;
+    for (int d = lane; d < G * half; d += 64) z += qp[d] * x[d];
+    z = wave_sum64(z);
+    const double lf = lsef[st.y];
+    const double hi = fmax(lf, z), lo = fmin(lf, z);
+    const double lse = hi + log1p(exp(lo - hi));
+    const double coef = (double)st.z * (exp(z - lse) - 1.0);
+    for (int d = lane; d < G * half; d += 64) out[d] = coef * qp[d];
+  }
+}
+
+// kp_cx_update in fp64: one workgroup per active slot; the slot's contribution rows summed in
+// row order, 1 / B, the N3 / N2 term, then the optimizer in torch's op order on double state
+template <int DP, class Prod>
+__global__ __launch_bounds__(256) void kp_cx_update64(int half, const int4* __restrict__ act,
+                                                      const CxPlan* __restrict__ plans, int nq,
+                                                      const double* __restrict__ contrib, double* __restrict__ X,
+                                                      double* __restrict__ S1, double* __restrict__ S2, CxOpt64 opt) {
+  constexpr int G = Prod::G;
+  const int tid = threadIdx.x;
+  const int4 a4 = act[blockIdx.x];  // slot, plan, qoff, toff
+  const int slot = a4.x;
+  const CxPlan P = plans[a4.y];
+  double* x = X + (size_t)slot * DP;
+  const int nc = P.q_count + P.t_count;
+  auto crow = [&](int j) -> const double* {
+    return j < P.q_count ? contrib + (size_t)(a4.z + j) * DP : contrib + (size_t)(nq + a4.w + j - P.q_count) * DP;
+  };
+  const double fb = (double)P.b;
+  double n2 = 0.0;
+  if (opt.reg_w != 0.0 && opt.reg_n2) {  // ||f|| over the whole row, before the update
+    __shared__ double n2red[4];
+    double ps = 0.0;
+    for (int i = tid; i < half; i += 256) {
+      double xv[G];
+#pragma unroll
+      for (int h = 0; h < G; ++h) xv[h] = x[i + h * half];
+      const double f = Prod::mod64(xv);
+      ps += f * f;
+    }
+    ps = wave_sum64(ps);
+    if ((tid & 63) == 0) n2red[tid >> 6] = ps;
+    __syncthreads();
+    n2 = sqrt((n2red[0] + n2red[1]) + (n2red[2] + n2red[3]));
+  }
+  double xs[(DP / G + 255) / 256][G], gs[(DP / G + 255) / 256][G];
+#pragma unroll
+  for (int u = 0; u < (DP / G + 255) / 256; ++u) {
+    const int i = tid + 256 * u;
+    if (i >= half) continue;
+#pragma unroll
+    for (int h = 0; h < G; ++h) {
+      gs[u][h] = 0.0;
+      xs[u][h] = x[i + h * half];
+    }
+    for (int j = 0; j < nc; ++j) {
+      const double* c = crow(j);
+#pragma unroll
+      for (int h = 0; h < G; ++h) gs[u][h] += c[i + h * half];
+    }
+#pragma unroll
+    for (int h = 0; h < G; ++h) gs[u][h] /= fb;
+    if (opt.reg_w != 0.0) {
+      const double mod = opt.reg_n2 ? n2 : Prod::mod64(xs[u]);
+      const double k3 = 3.0 * opt.reg_w / fb * (double)(P.cnt_l + P.cnt_r) * mod;
+#pragma unroll
+      for (int h = 0; h < G; ++h) gs[u][h] += k3 * xs[u][h];
+    }
+  }
+  // (the N2 norm above read the whole row: every thread has it before any element moves)
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < (DP / G + 255) / 256; ++u) {
+    const int i = tid + 256 * u;
+    if (i >= half) continue;
+#pragma unroll
+    for (int h = 0; h < G; ++h) {
+      const int d = i + h * half;
+      const double gd = gs[u][h];
+      double xd = xs[u][h];
+      const size_t o = (size_t)slot * DP + d;
+      if (opt.kind == KP_OPT_ADAGRAD) {
+        double s1 = S1[o];
+        s1 = s1 + gd * gd;
+        const double stdv = sqrt(s1) + opt.eps;
+        xd = xd + (-opt.lr * gd) / stdv;
+        S1[o] = s1;
+      } else if (opt.kind == KP_OPT_ADAM) {
+        double m1 = S1[o], v2 = S2[o];
+        m1 = m1 + opt.one_minus_b1 * (gd - m1);
+        v2 = v2 * opt.b2;
+        v2 = v2 + (opt.one_minus_b2 * gd) * gd;
+        const double den = sqrt(v2) / opt.bc2_sqrt + opt.eps;
+        xd = xd + (-opt.step_size * m1) / den;
+        S1[o] = m1;
+        S2[o] = v2;
+      } else {
+        xd = xd + (-opt.lr) * gd;
+      }
+      x[d] = xd;
+    }
+  }
+}
+
+// the key ranges of a call's fp64 attention launches: the planner's S for the call's largest
+// launch (attn_plan_ranges; KP_ATTN_RANGES=S forces S as it does for kp_attn3), in whole
+// 32-key planner tiles.  One S for the whole call keeps the partials' layout fixed.
+struct Attn64Plan {
+  int ranges, keys_per_range;
+};
+inline Attn64Plan attn64_plan(const kp_ctx* c, int max_nq) {
+  const int slots = c->n_cu;
+  const AttnPlan p = c->attn_ranges > 0 ? attn_plan_oneshot(std::max(1, max_nq), c->n_ent, c->attn_ranges)
+                                        : attn_plan_ranges(std::max(1, max_nq), c->n_ent, slots);
+  const int S = std::max(1, p.wk.ranges);
+  const int tiles = (p.wk.ktq + S - 1) / S;
+  return {S, tiles * 32};
+}
+
+// kp_posttrain_rank_f64 for a context of product Prod
+template <class Prod>
+void posttrain_rank_f64(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq) {
+  const std::string who = kp_model_name(c->model);
+  const kp_f64& f = *rq.f64;
+  const int ns = bt->n_slots, DP = c->dp, DBV = DP / 16, dim = c->dim;
+  const int half = Prod::extent(dim);
+  KP_REQUIRE(hp->batch_size > 0 && hp->epochs >= 0, who + ": bad batch_size/epochs");
+  require_request(c, hp, bt, rq, true, kp_model_name(c->model));
+  KP_REQUIRE(hp->reg_kind == KP_REG_N3 || hp->reg_kind == KP_REG_N2, who + ": unknown regulariser");
+  CxOpt64 opt{};
+  opt.kind = hp->optimizer;
+  opt.lr = f.lr;
+  opt.b2 = f.beta2;
+  opt.eps = f.eps;
+  opt.one_minus_b1 = 1.0 - f.beta1;
+  opt.one_minus_b2 = 1.0 - f.beta2;
+  opt.reg_w = f.reg_weight;
+  opt.reg_n2 = hp->reg_kind == KP_REG_N2;
+
+  CxStepPlan sp;
+  if (const char* why = cx_step_plan(c->n_ent, c->n_rel2, hp->batch_size, hp->epochs, bt, sp))
+    throw KpError{KP_EINVAL, who + ": " + why};
+
+  // ---- workspaces, all sized here, ahead of the step loop (c->cx.f64, c->rank.f64)
+  Complex64Ws& w = c->cx.f64;
+  Rank64Ws& rw = c->rank.f64;
+  std::vector<double> xp((size_t)ns * DP, 0.0);
+  for (int s = 0; s < ns; ++s) std::memcpy(&xp[(size_t)s * DP], f.x0 + (size_t)s * dim, sizeof(double) * dim);
+  double* X = upload(c, w.x, xp.data(), xp.size());
+  double* S1 = ensure_n<double>(w.s1, (size_t)ns * DP);
+  double* S2 = ensure_n<double>(w.s2, (size_t)ns * DP);
+  KP_HIP(hipMemsetAsync(S1, 0, sizeof(double) * (size_t)ns * DP, c->stream));
+  KP_HIP(hipMemsetAsync(S2, 0, sizeof(double) * (size_t)ns * DP, c->stream));
+  const CxPlan* plans = upload(c, w.plans, sp.plans.data(), sp.plans.size());
+  const CxQuery* pq = upload(c, w.queries, sp.pqs.data(), sp.pqs.size());
+  const int32_t* tg = upload(c, w.targets, sp.targets.data(), sp.targets.size());
+  const int2* pairs = upload(c, w.pairs, as_dev(sp.pairs.data()), sp.pairs.size());
+  const int4* acts = upload(c, w.acts, as_dev(sp.acts.data()), sp.acts.size());
+  const int4* stepq = upload(c, w.stepq, as_dev(sp.stepq.data()), sp.stepq.size());
+  const int4* stept = upload(c, w.stept, as_dev(sp.stept.data()), sp.stept.size());
+  const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
+  double* contrib = ensure_n<double>(w.contrib, (size_t)std::max(1, sp.max_items) * DP);
+  double* tsum = ensure_n<double>(w.tsum, (size_t)std::max(npq, 1) * DP);
+  double* qpair = ensure_n<double>(w.qpair, (size_t)std::max(npairs, 1) * DP);
+  double* lsef = ensure_n<double>(w.lsef, (size_t)std::max(npairs, 1));
+  const Attn64Plan ap = attn64_plan(c, std::max(sp.max_nq, npairs));
+  const size_t att_rows = (size_t)std::max(1, std::max(sp.max_nq, npairs)) * ap.ranges;
+  double* am = ensure_n<double>(w.am, att_rows);
+  double* al = ensure_n<double>(w.al, att_rows);
+  double* ao = ensure_n<double>(w.ao, att_rows * DP);
+  double* qs = ensure_n<double>(w.qs, (size_t)std::max(sp.max_nq, 1) * DP);
+  // the rank's inputs and buffers
+  double* rq64 = ensure_n<double>(rw.q64, (size_t)ns * DP);
+  double* rt64 = ensure_n<double>(rw.t64, 2 * (size_t)ns);
+  double* rk64 = rt64 + ns;
+  const int32_t* dpred = upload(c, rw.pred, bt->pred, (size_t)ns * 3);
+  std::vector<int32_t> po(ns);
+  for (int s = 0; s < ns; ++s) po[s] = bt->pred[3 * s + 2];
+  const int32_t* dpo = upload(c, rw.po, po.data(), po.size());
+  const int32_t* dfo = upload(c, rw.filt_off, bt->filt_off, (size_t)ns + 1);
+  const int32_t* dfl = upload(c, rw.filt, bt->filt, (size_t)bt->filt_off[ns]);
+  float* dtarget = ensure_n<float>(rw.target, (size_t)ns);
+  int64_t* drank = ensure_n<int64_t>(rw.rank, (size_t)ns);
+
+  // ---- before the loop: target sums, the frozen-head pairs' q and frozen log-sum-exp
+  KP_HIP(hipEventRecord(c->ev0, c->stream));
+  c->attn_last = {};
+  if (npq > 0) {
+    hipLaunchKernelGGL(kp_cx_tsum64, dim3(npq), dim3(128), 0, c->stream, c->dE, DP, pq, npq, tg, tsum);
+    KP_HIP(hipGetLastError());
+  }
+  if (npairs > 0) {
+    hipLaunchKernelGGL((kp_cx_qpair<Prod, double>), dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP, half,
+                       pairs, npairs, qpair);
+    KP_HIP(hipGetLastError());
+    CX_DISPATCH(DBV, launch_attn64<DB>(c, false, qpair, npairs, ap.ranges, ap.keys_per_range, am, al, nullptr));
+    hipLaunchKernelGGL(kp_cx_lse_merge64, dim3((npairs + 255) / 256), dim3(256), 0, c->stream, npairs, ap.ranges, am,
+                       al, lsef);
+    KP_HIP(hipGetLastError());
+  }
+
+  struct LoopEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~LoopEvents() {
+      if (a) (void)hipEventDestroy(a);
+      if (b) (void)hipEventDestroy(b);
+    }
+  } lev;
+  KP_HIP(hipEventCreate(&lev.a));
+  KP_HIP(hipEventCreate(&lev.b));
+  KP_HIP(hipEventRecord(lev.a, c->stream));
+  int64_t hot_launches = 0;
+  c->hot_pairs.clear();
+  c->hot_iv.clear();
+  for (int t = 0; t < sp.T; ++t) {
+    const int nq = sp.q_off[t + 1] - sp.q_off[t];
+    const int nt = sp.t_off[t + 1] - sp.t_off[t];
+    const int na = sp.act_off[t + 1] - sp.act_off[t];
+    hipEvent_t ea = nullptr, eb = nullptr;
+    if (nq > 0 && c->time_hot) {
+      ea = c->event(2 * hot_launches);
+      eb = c->event(2 * hot_launches + 1);
+    }
+    CX_DISPATCH(DBV, (launch_stepq<DB, Prod, double>(c, stepq + sp.q_off[t], X, nq, qs)));
+    if (nq > 0 && c->time_hot) KP_HIP(hipEventRecord(ea, c->stream));
+    CX_DISPATCH(DBV, launch_attn64<DB>(c, true, qs, nq, ap.ranges, ap.keys_per_range, am, al, ao));
+    if (nq > 0) {
+      if (c->time_hot) {
+        KP_HIP(hipEventRecord(eb, c->stream));
+        c->hot_pairs.push_back({(double)nq, 0.0});
+      }
+      ++hot_launches;
+      if (nq >= c->attn_last.nq) {
+        c->attn_last.nq = nq;
+        c->attn_last.inflight = 1;
+        c->attn_last.ranges = ap.ranges;
+        c->attn_last.n_parts = ap.ranges;
+        c->attn_last.n_wg = (nq + A64_QT - 1) / A64_QT * ap.ranges;
+      }
+    }
+    if (na <= 0) continue;
+    // Adam's step scalars from the double hyper-parameters (torch: lr / (1 - b1^t), sqrt(1 - b2^t))
+    const double step = (double)(t + 1);
+    opt.step_size = f.lr / (1.0 - std::pow(f.beta1, step));
+    opt.bc2_sqrt = std::sqrt(1.0 - std::pow(f.beta2, step));
+    if (nq + nt > 0) {
+      CX_DISPATCH(DBV, hipLaunchKernelGGL((kp_cx_contrib64<16 * DB, Prod>), dim3((nq + nt + 3) / 4), dim3(256), 0,
+                                          c->stream, half, stepq + sp.q_off[t], nq, stept + sp.t_off[t], nt, pq, X,
+                                          c->dR, tsum, qpair, lsef, am, al, ao, ap.ranges, contrib));
+      KP_HIP(hipGetLastError());
+    }
+    CX_DISPATCH(DBV, hipLaunchKernelGGL((kp_cx_update64<16 * DB, Prod>), dim3(na), dim3(256), 0, c->stream, half,
+                                        acts + sp.act_off[t], plans, nq, contrib, X, S1, S2, opt));
+    KP_HIP(hipGetLastError());
+  }
+  KP_HIP(hipEventRecord(lev.b, c->stream));
+
+  // ---- the rank on the fp64 row; out_score is the fp64 target value itself
+  CX_DISPATCH(DBV, (launch_rankq64<DB, Prod, double>(c, X, dpred, ns, rq64, rt64, rk64)));
+  launch_rank_f64(c, ns, rq64, rt64, rk64, dpo, dfo, dfl, dtarget, drank, RANK64_DOT, 0, nullptr, nullptr, &rw.bits);
+  KP_HIP(hipEventRecord(c->ev1, c->stream));
+  if (f.out_x) KP_HIP(hipMemcpyAsync(xp.data(), X, sizeof(double) * xp.size(), hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipMemcpyAsync(f.out_score, rt64, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipMemcpyAsync(bt->out_rank, drank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipStreamSynchronize(c->stream));
+  if (f.out_x)
+    for (int s = 0; s < ns; ++s) std::memcpy(f.out_x + (size_t)s * dim, &xp[(size_t)s * DP], sizeof(double) * dim);
+  record_hot_timing(c, hot_launches, lev.a, lev.b);
+}
+
 // The batched post-training and rank of a model whose step is a 1-vs-all softmax over
 // q = lhs o rel (product policy Prod): planning (kp_cx_plan.hpp), workspaces, attention
 // planning and timing are the model's only through Prod.
@@ -935,6 +1385,7 @@ int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxD
 // and planning), up to the last launch enqueued, and waiting for the device
 template <class Prod>
 void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq) {
+  if (rq.f64) return posttrain_rank_f64<Prod>(c, hp, bt, rq);  // kp_posttrain_rank_f64
   const std::string who = kp_model_name(c->model);
   const double t_in = g_host_times ? host_ms() : 0.0;
   const int ns = bt->n_slots;

@@ -46,6 +46,13 @@ inline void require_request(const kp_ctx* c, const kp_hp* hp, const kp_batch* bt
     KP_REQUIRE(rq.n_probes() == 0, "kp_posttrain_rank_probes: probes without a slot");
   } else {
     if (const char* why = kp_check_batch(c->n_ent, c->n_rel2, c->dim, bt)) throw KpError{KP_EINVAL, who + ": " + why};
+    if (rq.f64) {  // kp_posttrain_rank_f64: its buffers, then the family, then what it does not offer yet
+      KP_REQUIRE(rq.f64->x0 && rq.f64->out_score, who + ": fp64: missing x0 or out_score");
+      if (c->model != KP_MODEL_COMPLEX && c->model != KP_MODEL_DISTMULT)
+        throw KpError{KP_ENOTSUP, who + ": fp64 post-training serves ComplEx and DistMult only"};
+      if (rq.k != 0 || rq.n_probes() > 0 || rq.trace || rq.marks)
+        throw KpError{KP_ENOTSUP, who + ": fp64: top-k, probes, trace and marks are not offered"};
+    }
     KP_REQUIRE(rq.k >= 0 && rq.k <= 32, who + ": top-k: k must be in [0, 32]");
     KP_REQUIRE(rq.k == 0 || (rq.ids && rq.scores), who + ": top-k: missing output");
     if (rq.k > 0 && !rank64)

@@ -171,6 +171,7 @@ class PostTrainingEngine(RelevanceEngine):
         self._fused = []  # TransE calls whose edits and draws _flush_fused makes in two library calls
         self._sched = None
         self._kp_hp = model.kp_hp(hp)
+        self._kp_hp64 = model.kp_hp64(hp) if hasattr(model, "kp_hp64") else None  # the double form (fp64)
         if getattr(model, "is_kelpie", False):
             raise Exception("Already a post-trainable KelpieModel.")
         self.set_cache()
@@ -181,6 +182,57 @@ class PostTrainingEngine(RelevanceEngine):
         self._cur_probes = None
         self._trace = False
         self._marks = None
+        self._precision = "fp32"
+
+    PRECISIONS = ("fp32", "fp64")
+    _precision = "fp32"
+
+    @property
+    def precision(self):
+        """``"fp32"`` (the default: every call goes where it always went) or ``"fp64"``: every
+        post-training and rank of ``compute_relevance``, ``compute_relevance_batch`` and
+        ``compute_relevance_multi`` runs in double precision on the device
+        (``kp_posttrain_rank_f64``; include/kelpie_hip.h, "fp64"), as the reference runs with
+        every tensor in float64: the float32 draw upcast and scaled in float64, the Python
+        doubles as hyper-parameters, ``target_score`` the double, the relevance formulas in
+        float64.  The draws are those of fp32, so the generators end in the same state.
+        ComplEx and DistMult only.  Not offered with ``top_k``, probes, ``trace``, ``marks``,
+        a slot sharding or ``compute_relevance_pipeline`` (NotImplementedError before any
+        draw).  The cached base results are kept per precision."""
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        if value not in self.PRECISIONS:
+            raise ValueError(f"precision must be one of {self.PRECISIONS}, got {value!r}")
+        if value == "fp64" and not hasattr(self.model, "kelpie_init64"):
+            raise NotImplementedError(f"precision='fp64': {self.model.name} has no fp64 post-training "
+                                      "(ComplEx and DistMult only)")
+        self._precision = value
+
+    def _fp64(self):
+        return self._precision == "fp64"
+
+    def _refuse_fp64(self):
+        """fp64's refusals, before any draw."""
+        if not self._fp64():
+            return
+        for on, what in ((self._top_k, "top_k"), (self._side_effects or self._probe_req is not None, "probes"),
+                         (self._trace, "trace"), (self._marks is not None, "marks")):
+            if on:
+                raise NotImplementedError(f"precision='fp64' with {what}: kp_posttrain_rank_f64 does not offer it")
+        if self._sharded():
+            raise NotImplementedError("precision='fp64' with a slot sharding: the fp64 results are not gathered "
+                                      "across ranks")
+
+    @property
+    def base_pt_results(self):
+        """The cached base post-training results of the current precision."""
+        return self._base_pt[self._precision]
+
+    @base_pt_results.setter
+    def base_pt_results(self, value):
+        self._base_pt[self._precision] = value
 
     _trace = False
     _marks = None  # the epochs after which every post-training is also ranked (marks), int32 array or None
@@ -297,7 +349,7 @@ class PostTrainingEngine(RelevanceEngine):
         self._top_k = int(k)
 
     def set_cache(self):
-        self.base_pt_results = {}
+        self._base_pt = {p: {} for p in self.PRECISIONS}  # keyed by precision (base_pt_results)
         self.kelpie_dataset_cache_size = 20
         self.kelpie_dataset_cache = OrderedDict()
 
@@ -336,13 +388,14 @@ class PostTrainingEngine(RelevanceEngine):
         if self._sharded():
             return self._schedule_sharded(pred, view, triples, mode, slots, pending_base)
         init = self.rng.rand_init(self.model.dimension)
-        x_base = self.model.kelpie_init(init, self.rng)  # base KelpieModel is built every call (A-Q6)
+        kelpie_init = self.model.kelpie_init64 if self._fp64() else self.model.kelpie_init
+        x_base = kelpie_init(init, self.rng)  # base KelpieModel is built every call (A-Q6)
         kp = view.as_kelpie_triple(pred)
         if pred not in self.base_pt_results and pred not in pending_base:
             pending_base[pred] = len(slots)
             slots.append(self._slot(x_base, view.base_rows, kp, view.filter_for(kp[1])))
             slots[-1].probes = self._slot_probes(view, None)
-        x_pt = self.model.kelpie_init(init, self.rng)
+        x_pt = kelpie_init(init, self.rng)
         rows, delta = view.removed(triples) if mode == "necessary" else view.added(triples)
         filt = view.filter_for(kp[1], delta.get(kp[1]))
         slots.append(self._slot(x_pt, rows, kp, filt))
@@ -589,6 +642,7 @@ class PostTrainingEngine(RelevanceEngine):
 
     def _schedule_all(self, items, checkpoints):
         """_schedule_multi, with every queued TransE call's draws made before it returns or raises."""
+        self._refuse_fp64()  # before any draw
         if self._top_k and self._sharded():
             # before any draw: the gather's records hold a score and a rank per slot
             raise NotImplementedError("top_k > 0 with a slot sharding: the lists are not gathered across ranks")
@@ -667,7 +721,7 @@ class PostTrainingEngine(RelevanceEngine):
         n = len(slots)
         if slots and slots[0].native is not None:
             return self._pack_native(slots, ctx)
-        x0 = np.stack([s.x0 for s in slots]).astype(np.float32)
+        x0 = np.stack([s.x0 for s in slots]).astype(np.float64 if self._fp64() else np.float32)
         row_off = np.zeros(n + 1, np.int32)
         row_off[1:] = np.cumsum([len(s.rows) for s in slots])
         rows = np.concatenate([s.rows.reshape(-1, 3) for s in slots]).astype(np.int32) if row_off[-1] \
@@ -803,7 +857,10 @@ class PostTrainingEngine(RelevanceEngine):
         marks = self._marks
         if marks is not None:
             kw["marks"] = marks
-        out = _lib.split_rank_result(ctx.posttrain_rank(self._kp_hp, *packed, **kw), **kw)
+        if self._fp64():  # the fp64 entry point alone (no optional request: _refuse_fp64)
+            out = _lib.RankResult(*ctx.posttrain_rank_f64(self._kp_hp64, *packed))
+        else:
+            out = _lib.split_rank_result(ctx.posttrain_rank(self._kp_hp, *packed, **kw), **kw)
         score, rank = out.score, out.rank
         t_end = time.perf_counter()
         if fill:
@@ -1158,6 +1215,9 @@ class PostTrainingEngine(RelevanceEngine):
         import os
         import threading
 
+        if self._fp64():  # before any draw
+            raise NotImplementedError("precision='fp64' on compute_relevance_pipeline: the fp64 path runs one "
+                                      "batch at a time")
         if depth is None:
             depth = int(os.environ.get("KELPIE_PIPELINE_DEPTH", "2"))
         ctxs = self.model.contexts(max(1, depth))
@@ -1438,7 +1498,11 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
                 self.last_results.append((pt, base))
         # int64 tensor + python float -> float32 tensor (A-Q5): one float32 add per call,
         # element-wise over the batch (the same bits as the scalar form)
-        rel = (np.asarray(rank_w, np.int64).astype(np.float32) + np.asarray(sig_w, np.float64).astype(np.float32)).tolist()
+        if self._fp64():  # the fp64 reference's default dtype is float64: no float32 add
+            rel = (np.asarray(rank_w, np.int64).astype(np.float64) + np.asarray(sig_w, np.float64)).tolist()
+        else:
+            rel = (np.asarray(rank_w, np.int64).astype(np.float32)
+                   + np.asarray(sig_w, np.float64).astype(np.float32)).tolist()
         k = 0
         for n in lens:
             outs.append(rel[k:k + n])
@@ -1464,6 +1528,8 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
             score_worsening = pt["score"] - base["score"]
         else:
             score_worsening = base["score"] - pt["score"]
+        if self._fp64():
+            return float(pt["rank"] - base["rank"]) + _sigmoid(score_worsening)
         return float(np.float32(pt["rank"] - base["rank"]) + np.float32(_sigmoid(score_worsening)))
 
     def _mk_rule(self, relevance, detail, epochs):
@@ -1498,7 +1564,10 @@ class SufficientPostTrainingEngine(PostTrainingEngine):
             score_improvement = base["score"] - pt["score"]
         else:
             score_improvement = pt["score"] - base["score"]
-        rel = float(np.float32(np.float32(rank_improvement) + np.float32(_sigmoid(score_improvement))))
+        if self._fp64():
+            rel = float(rank_improvement) + _sigmoid(score_improvement)
+        else:
+            rel = float(np.float32(np.float32(rank_improvement) + np.float32(_sigmoid(score_improvement))))
         return rel / float(base["rank"])
 
     def _mk_rule(self, relevance, detail, epochs):
@@ -1585,7 +1654,10 @@ class SufficientPostTrainingEngine(PostTrainingEngine):
                         score_improvement = base["target_score"] - pt["target_score"]
                     else:
                         score_improvement = pt["target_score"] - base["target_score"]
-                    rel = float(np.float32(np.float32(rank_improvement) + np.float32(_sigmoid(score_improvement))))
+                    if self._fp64():  # the fp64 reference's default dtype is float64: no float32 add
+                        rel = float(rank_improvement) + _sigmoid(score_improvement)
+                    else:
+                        rel = float(np.float32(np.float32(rank_improvement) + np.float32(_sigmoid(score_improvement))))
                     rel /= float(base["target_rank"])
                     rels.append(rel)
                 self.last_results.append(det)

@@ -137,6 +137,18 @@ class MultiClassNLLModel(FrozenModel):
                        eps=1e-10 if name == "Adagrad" else 1e-8, reg_weight=float(hp.get("regularizer_weight", 0.0)),
                        reg_kind=_lib.KP_REG[reg])
 
+    def kelpie_init64(self, init, rng):
+        """The fp64 run's kelpie row: the float32 draw upcast (exact) and multiplied by
+        ``init_scale`` in float64 (complex.py:155-157 on a float64 Parameter)."""
+        return init.astype(np.float32).astype(np.float64) * np.float64(self.init_scale)
+
+    def kp_hp64(self, hp):
+        """``kp_hp`` with the hyper-parameters as the Python doubles they are (``_lib.HP64``)."""
+        name = hp["optimizer_name"]
+        return _lib.HP64(hp=self.kp_hp(hp), lr=float(hp["lr"]), beta1=float(hp.get("decay1", 0.9)),
+                         beta2=float(hp.get("decay2", 0.999)), eps=1e-10 if name == "Adagrad" else 1e-8,
+                         reg_weight=float(hp.get("regularizer_weight", 0.0)))
+
     def posttrain_draws(self, rows, hp, rng):
         return rng.complex_epochs(len(rows), int(hp["epochs"]), int(hp["batch_size"]))
 
