@@ -342,6 +342,84 @@ typedef struct {
  * a context that has served it returns bitwise the fp32 results of a fresh one afterwards. */
 int kp_posttrain_rank_f64(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, const kp_f64* r);
 
+/* ---- Keyed draws: order-independent post-training randomness, generated on the device ----
+ * The reference draws each post-training's kelpie init, epoch shuffles and negatives from
+ * process-global generators in call order; kp_batch.x0 / rng_off / rng carry those draws and
+ * that stays the default.  Keyed draws are a second, opt-in source: every slot's numbers are
+ * a pure function of two 64-bit keys, generated by a counter-based generator on the device
+ * into the buffers the step kernels read.  No generator state exists; a rerun gives the same
+ * bits.  TransE, ComplEx and DistMult (ConvE's mask layout is not keyed yet).
+ *
+ * Generator: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ * 0xBB67AE85, ten rounds).  Known answers (counter | key | output), the Random123 vectors:
+ *   00000000 x4 | 00000000 x2 | 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *   ffffffff x4 | ffffffff x2 | 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *   243f6a88 85a308d3 13198a2e 03707344 | a4093822 299f31d0 | d16cfe09 94fdcceb 5001e420 24126ea1
+ *
+ * Keys: a slot carries init_key and slot_key.  The library takes whatever keys the caller
+ * passes.  kelpie_amd (kelpie_amd/keyed.py) derives both as the first 8 bytes, little-endian,
+ * of blake2b(digest_size = 8) over
+ *   init_key: "kelpie-keyed/init\0" | seed int64 | s, p, o int32
+ *   slot_key: "kelpie-keyed/slot\0" | seed int64 | s, p, o int32 | role uint8 (0 base, 1 edited)
+ *             | mode uint8 (0 necessary, 1 sufficient) | count uint32 | the rule's triples
+ *             SORTED, each h, r, t int32
+ * every integer little-endian, (s, p, o) the prediction the slot ranks in the dataset's ids
+ * (for a conversion entity: after replace_entity_in_triple).  A prediction's base slot and
+ * all of its edited slots share init_key, hence x0: common random numbers.
+ *
+ * Words: word w of stream s, epoch e, under key k is lane w % 4 of
+ *   Philox(counter = (w / 4, e, s, 0), key = (lo32(k), hi32(k))).
+ * Streams:
+ *   0  x0, under init_key, epoch 0.  ComplEx / DistMult: element i =
+ *      float(word_i >> 8) * 2^-24, then * x0_scale in float32 (kelpie_init's one multiply).
+ *      TransE: element i takes words 2 i, 2 i + 1: u1 = (w + 1) * 2^-32, u2 = w' * 2^-32,
+ *      value (x0_scale * sqrt(-2 ln u1)) * cos(2 pi u2) in float64, rounded once to float32
+ *      (x0_scale: the xavier std, float(sqrt(2 / (d + 1)))).
+ *   1  the permutation of epoch e, under slot_key: row i gets key word i; the permutation is
+ *      the stable ascending argsort of the key words (ties by row index).
+ *   2  TransE negative entity of (epoch, row): (uint64(word) * neg_bound) >> 32.
+ *   3  TransE head-or-tail of (epoch, row): word >> 31 (1 corrupts the head).
+ * Layout: exactly kp_batch.rng's.  ComplEx / DistMult: epochs x R permutations for a slot with
+ * R > batch_size, no words otherwise.  TransE: epochs x [R row order | R negatives | R
+ * head_or_tail], each epoch's row order its own permutation.
+ *   init_key    [n_slots]
+ *   slot_key    [n_slots]
+ *   x0_scale    ComplEx / DistMult: init_scale; TransE: the normal's std
+ *   neg_bound   TransE: the bound of the negatives (n_ent + 1 as the reference draws), in
+ *               [1, 2^31]; not read otherwise */
+typedef struct {
+  int32_t n_slots;
+  const uint64_t* init_key;
+  const uint64_t* slot_key;
+  float x0_scale;
+  int64_t neg_bound;
+} kp_keyed;
+
+/* Arm the context: the next kp_posttrain_rank, _topk, _probes, _trace or _marks call on it
+ * whose batch has x0, rng_off and rng all NULL generates its draws from these keys (copied
+ * here; the caller's arrays are not read later) and disarms.  A call that brings its buffers
+ * leaves the context armed; any failing call disarms.  The armed call checks the request after
+ * the batch check and before any device work (KP_EINVAL: n_slots differs from the batch's,
+ * missing keys, neg_bound out of range, a word count beyond int64).  Its results are bit for
+ * bit those of the same batch fed with kp_keyed_draws' arrays.  kp_posttrain_rank_f64 on an
+ * armed context answers KP_ENOTSUP and disarms; so does arming a ConvE context.  keyed == NULL
+ * disarms.  Unarmed, a NULL buffer is the KP_EINVAL it always was. */
+int kp_ctx_arm_keyed(kp_ctx* ctx, const kp_keyed* keyed);
+
+/* The per-slot word counts of the layout above, out_words [n_slots]: pure host work, no
+ * context.  hp: epochs and batch_size are read.  They are what the reference protocol's draws
+ * occupy for the same slot.  KP_ENOTSUP for ConvE, KP_EINVAL (kp_last_error(NULL)) otherwise. */
+int kp_keyed_rng_words(int32_t model, const kp_hp* hp, int32_t n_slots, const int32_t* row_off, int64_t* out_words);
+
+/* Generate the draws of n_slots slots on the device and download them: out_x0 [n_slots][dim]
+ * (may be NULL), out_rng_off [n_slots + 1] the prefix sums of kp_keyed_rng_words, out_rng
+ * [out_rng_off[n_slots]] (cap: its capacity in words; KP_EINVAL when too small).  These are
+ * kp_batch's x0 / rng_off / rng of the armed call.  For tests and for callers that want the
+ * numbers.  The armed call downloads none of them, but for ComplEx / DistMult the permutations
+ * of its multi-step slots (R > batch_size): those families plan their steps on the host. */
+int kp_keyed_draws(kp_ctx* ctx, const kp_hp* hp, int32_t n_slots, const int32_t* row_off, const kp_keyed* keyed,
+                   float* out_x0, int64_t* out_rng_off, int32_t* out_rng, int64_t cap);
+
 /* Model.all_scores (model.py:19; transe.py:48-65, complex.py:88-112,
  * conve.py:133-158) for n (head, relation) pairs over the frozen entities:
  * out[n][n_ent].  The RelevanceEngine.select_entities_to_convert sweep

@@ -31,7 +31,8 @@ EXPORTS = ["kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_posttrain_ran
            "kp_gather_i32", "kp_rng_transe_calls_async", "kp_rng_torch_take", "kp_conve_train_begin",
            "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free", "kp_ctx_set_inflight",
            "kp_last_attn_plan", "kp_posttrain_rank_topk", "kp_posttrain_rank_probes", "kp_trace_steps",
-           "kp_posttrain_rank_trace", "kp_posttrain_rank_marks", "kp_posttrain_rank_f64"]
+           "kp_posttrain_rank_trace", "kp_posttrain_rank_marks", "kp_posttrain_rank_f64", "kp_ctx_arm_keyed",
+           "kp_keyed_rng_words", "kp_keyed_draws"]
 
 
 class ModelDesc(C.Structure):
@@ -88,6 +89,13 @@ class Trace(C.Structure):
 class Marks(C.Structure):
     _fields_ = [("n", C.c_int32), ("epochs", C.c_void_p), ("out_score", C.c_void_p), ("out_rank", C.c_void_p),
                 ("out_x", C.c_void_p)]
+
+
+class Keyed(C.Structure):
+    """kp_keyed: the slots' keys, the x0 scale and the negatives' bound (include/kelpie_hip.h,
+    "Keyed draws")."""
+    _fields_ = [("n_slots", C.c_int32), ("init_key", C.c_void_p), ("slot_key", C.c_void_p), ("x0_scale", C.c_float),
+                ("neg_bound", C.c_int64)]
 
 
 MARKS_MAX = 16  # kp_marks.n
@@ -149,6 +157,11 @@ def lib():
                                                   C.c_void_p, C.POINTER(Probes), C.POINTER(Trace), C.POINTER(Marks)]
         if hasattr(L, "kp_posttrain_rank_f64"):  # KELPIE_HIP_LIB may name a build from before the fp64 path
             L.kp_posttrain_rank_f64.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.POINTER(F64)]
+        if hasattr(L, "kp_ctx_arm_keyed"):  # KELPIE_HIP_LIB may name a build from before the keyed draws
+            L.kp_ctx_arm_keyed.argtypes = [C.c_void_p, C.POINTER(Keyed)]
+            L.kp_keyed_rng_words.argtypes = [C.c_int32, C.POINTER(HP), C.c_int32, C.c_void_p, C.c_void_p]
+            L.kp_keyed_draws.argtypes = [C.c_void_p, C.POINTER(HP), C.c_int32, C.c_void_p, C.POINTER(Keyed),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         L.kp_all_scores.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kp_convertible.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
@@ -257,6 +270,25 @@ def trace_steps(model_name: str, hp: HP, row_off, rows) -> np.ndarray:
     check(lib().kp_trace_steps(KP_MODEL[model_name], C.byref(hp), n, _ptr(row_off),
                                _ptr(rows) if len(rows) else None, _ptr(out)))
     return out[:n]
+
+
+def keyed_rng_words(model_name: str, hp: HP, row_off) -> np.ndarray:
+    """kp_keyed_rng_words: the words of every slot's keyed draws in kp_batch.rng's layout, int64
+    [n_slots].  Host work only: no context, no device."""
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    n = len(row_off) - 1
+    out = np.zeros(max(1, n), np.int64)
+    check(lib().kp_keyed_rng_words(KP_MODEL[model_name], C.byref(hp), n, _ptr(row_off), _ptr(out)))
+    return out[:n]
+
+
+def _keyed_struct(init_keys, slot_keys, x0_scale, neg_bound):
+    ik = np.ascontiguousarray(init_keys, dtype=np.uint64).reshape(-1)
+    sk = np.ascontiguousarray(slot_keys, dtype=np.uint64).reshape(-1)
+    if len(ik) != len(sk):
+        raise ValueError("keyed draws: one init_key and one slot_key per slot are needed")
+    return Keyed(len(ik), _ptr(ik) if len(ik) else None, _ptr(sk) if len(sk) else None, float(x0_scale),
+                 int(neg_bound)), (ik, sk)
 
 
 def mt19937_discard(state: np.ndarray, n: int):
@@ -495,11 +527,12 @@ class Context:
         if not 0 <= topk <= 32:
             raise ValueError(f"topk must be in [0, 32], got {topk}")
         n = len(row_off) - 1
-        x0 = np.ascontiguousarray(x0, dtype=np.float32)
+        # x0, rng_off and rng all None: the call of an armed context (arm_keyed), NULL buffers
+        x0 = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float32)
         row_off = np.ascontiguousarray(row_off, dtype=np.int32)
         rows = np.ascontiguousarray(rows, dtype=np.int32)
-        rng_off = np.ascontiguousarray(rng_off, dtype=np.int64)
-        rng = np.ascontiguousarray(rng, dtype=np.int32)
+        rng_off = None if rng_off is None else np.ascontiguousarray(rng_off, dtype=np.int64)
+        rng = None if rng is None else np.ascontiguousarray(rng, dtype=np.int32)
         pred = np.ascontiguousarray(pred, dtype=np.int32)
         filt_off = np.ascontiguousarray(filt_off, dtype=np.int32)
         filt = np.ascontiguousarray(filt, dtype=np.int32)
@@ -557,6 +590,32 @@ class Context:
             rc = lib().kp_posttrain_rank_topk(*head)
         check(rc, self.h)
         return ret
+
+    def arm_keyed(self, init_keys, slot_keys, x0_scale, neg_bound=0):
+        """kp_ctx_arm_keyed: the next ``posttrain_rank`` (any of its requests) whose ``x0``,
+        ``rng_off`` and ``rng`` are all None generates its draws on the device from these keys
+        (uint64 per slot).  ``init_keys is None`` disarms."""
+        if init_keys is None:
+            check(lib().kp_ctx_arm_keyed(self.h, None), self.h)
+            return
+        k, keep = _keyed_struct(init_keys, slot_keys, x0_scale, neg_bound)
+        check(lib().kp_ctx_arm_keyed(self.h, C.byref(k)), self.h)
+        del keep  # the library copied the keys
+
+    def keyed_draws(self, hp: HP, row_off, init_keys, slot_keys, x0_scale, neg_bound=0):
+        """kp_keyed_draws: (x0 float32 [n][dim], rng_off int64 [n + 1], rng int32) generated on
+        the device from the keys: the arrays an armed call's step kernels read."""
+        row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+        n = len(row_off) - 1
+        k, keep = _keyed_struct(init_keys, slot_keys, x0_scale, neg_bound)
+        total = int(keyed_rng_words(self.model_name, hp, row_off).sum())
+        x0 = np.zeros((n, self.dim), np.float32)
+        off = np.zeros(n + 1, np.int64)
+        rng = np.zeros(max(1, total), np.int32)
+        check(lib().kp_keyed_draws(self.h, C.byref(hp), n, _ptr(row_off), C.byref(k), _ptr(x0), _ptr(off), _ptr(rng),
+                                   total), self.h)
+        del keep
+        return x0, off, rng[:total]
 
     def posttrain_rank_f64(self, hp64: HP64, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False):
         """kp_posttrain_rank_f64: (target scores float64, ranks, final rows float64 or None) of

@@ -69,9 +69,18 @@ class StochasticBuilder:
     AUTO_MIN, AUTO_MAX = 4, 32
 
     def __init__(self, xsi, engine, summarization: str = None, max_explanation_length: int = 4, window=32,
-                 pipelined=False, top_k=0, side_effects=0, trace=False):
+                 pipelined=False, top_k=0, side_effects=0, trace=False, draws=None, seed=None):
         if summarization is not None:
             raise NotImplementedError("summarisation (simulation / bisimulation) is out of scope")
+        # the source of the post-training draws (PostTrainingEngine.draws / .seed; None: as the
+        # engine has it).  Keyed draws have nothing to rewind: the windows' checkpoints are
+        # taken and restored as ever and change nothing; the pipelined builder is not offered
+        if seed is not None:
+            engine.seed = seed
+        if draws is not None:
+            engine.draws = draws
+        if pipelined and getattr(engine, "draws", "reference") == "keyed":
+            raise NotImplementedError("draws='keyed' with a pipelined builder: keyed batches run one at a time")
         self.xsi = xsi
         self.engine = engine
         self.dataset = engine.dataset

@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "kp_keyed.hpp"
 #include "kp_posttrain.hpp"
 
 int cx_pick_db(int dim);
@@ -217,10 +218,17 @@ static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, in
   rq.probes = probes;
   rq.trace = trace;
   rq.marks = marks;
-  return guarded(c, [&] {
+  // an armed context (kp_ctx_arm_keyed) generates the draws of a call that brings none of the
+  // three buffers, and is disarmed by it; a failing call disarms whatever it brought
+  const bool keyed = c->keyed_armed && !b->x0 && !b->rng_off && !b->rng;
+  if (keyed) {
+    rq.keyed = &c->keyed;
+    c->keyed_armed = false;
+  }
+  const int rc = guarded(c, [&] {
     KP_REQUIRE(b->n_slots >= 0, "kp_posttrain_rank: negative n_slots");
     if (b->n_slots == 0) return require_request(c, hp, b, rq, true, kp_model_name(c->model));
-    KP_REQUIRE(b->x0 && b->row_off && b->pred && b->filt_off && b->out_score && b->out_rank,
+    KP_REQUIRE((keyed || b->x0) && b->row_off && b->pred && b->filt_off && b->out_score && b->out_rank,
                "kp_posttrain_rank: missing buffer");
     KP_HIP(hipSetDevice(c->device));
     switch (c->model) {
@@ -230,6 +238,8 @@ static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, in
       case KP_MODEL_CONVE: conve_posttrain_rank(c, hp, b, rq); break;
     }
   });
+  if (rc != KP_OK) c->keyed_armed = false;
+  return rc;
 }
 
 int kp_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b) { return posttrain_rank_call(c, hp, b); }
@@ -270,6 +280,10 @@ int kp_posttrain_rank_f64(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const k
   static const kp_f64 none{};  // a NULL request is refused where a NULL x0 is: after the batch check
   PostReq rq;
   rq.f64 = r ? r : &none;
+  if (c->keyed_armed) {  // keyed draws are not offered in fp64: refused, and the context disarmed
+    c->keyed_armed = false;
+    return guarded(c, [&] { throw KpError{KP_ENOTSUP, "kp_posttrain_rank_f64: keyed draws are not offered in fp64"}; });
+  }
   return guarded(c, [&] {
     KP_REQUIRE(b->n_slots >= 0, "kp_posttrain_rank_f64: negative n_slots");
     if (b->n_slots == 0) return require_request(c, hp, b, rq, true, kp_model_name(c->model));
@@ -280,6 +294,43 @@ int kp_posttrain_rank_f64(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const k
       case KP_MODEL_DISTMULT: distmult_posttrain_rank(c, hp, b, rq); break;
       default: require_request(c, hp, b, rq, true, kp_model_name(c->model)); break;  // throws
     }
+  });
+}
+
+// ---- keyed draws (include/kelpie_hip.h, "Keyed draws"; kp_keyed.hpp, kp_keyed.hip)
+int kp_ctx_arm_keyed(kp_ctx* c, const kp_keyed* k) {
+  if (!c) return KP_EINVAL;
+  c->keyed_armed = false;
+  if (!k) return KP_OK;
+  return guarded(c, [&] {
+    if (!kp_keyed_family(c->model))
+      throw KpError{KP_ENOTSUP, std::string(kp_model_name(c->model)) + ": keyed draws serve TransE, ComplEx and DistMult"};
+    KP_REQUIRE(k->n_slots >= 0, "kp_ctx_arm_keyed: negative n_slots");
+    KP_REQUIRE(k->n_slots == 0 || (k->init_key && k->slot_key), "kp_ctx_arm_keyed: missing keys");
+    c->keyed_init.assign(k->init_key, k->init_key + k->n_slots);
+    c->keyed_slot.assign(k->slot_key, k->slot_key + k->n_slots);
+    c->keyed = *k;
+    c->keyed.init_key = c->keyed_init.data();
+    c->keyed.slot_key = c->keyed_slot.data();
+    c->keyed_armed = true;
+  });
+}
+
+int kp_keyed_rng_words(int32_t model, const kp_hp* hp, int32_t n_slots, const int32_t* row_off, int64_t* out_words) {
+  return guarded(nullptr, [&] {
+    if (model == KP_MODEL_CONVE) throw KpError{KP_ENOTSUP, "kp_keyed_rng_words: ConvE's masks are not keyed"};
+    KP_REQUIRE(n_slots <= 0 || out_words, "kp_keyed_rng_words: missing output");
+    if (const char* why = kp_keyed_words_host(model, hp, n_slots, row_off, out_words, nullptr))
+      throw KpError{KP_EINVAL, std::string("kp_keyed_rng_words: ") + why};
+  });
+}
+
+int kp_keyed_draws(kp_ctx* c, const kp_hp* hp, int32_t n_slots, const int32_t* row_off, const kp_keyed* keyed,
+                   float* out_x0, int64_t* out_rng_off, int32_t* out_rng, int64_t cap) {
+  if (!c || !hp) return KP_EINVAL;
+  return guarded(c, [&] {
+    KP_HIP(hipSetDevice(c->device));
+    keyed_draws(c, hp, n_slots, row_off, keyed, out_x0, out_rng_off, out_rng, cap);
   });
 }
 

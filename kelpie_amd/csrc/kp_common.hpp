@@ -237,6 +237,22 @@ struct TranseWs {
 };
 KP_WS_COMPLETE(TranseWs);
 
+// kp_keyed.hip: the keyed draws' inputs on the device (the keys, the slots' row and word
+// offsets, the slot lists of the two permutation launches), the sorting network's global
+// scratch for slots beyond its LDS form, and kp_keyed_draws' own outputs (the armed call
+// generates into the family's x and rng)
+struct KeyedWs {
+  DevBuf init_key, slot_key;    // [ns] uint64
+  DevBuf row_off, rng_off;      // [ns + 1] int32 / int64
+  DevBuf lds_slots, big_slots;  // int32 slot lists: rows <= 4096 / beyond
+  DevBuf scratch;               // [workgroups][N] (key word, row) pairs of the global network
+  DevBuf x, rng;                // kp_keyed_draws' rows [ns][dp] and words; ComplEx's armed permutations
+  auto all() {
+    return std::array{&init_key, &slot_key, &row_off, &rng_off, &lds_slots, &big_slots, &scratch, &x, &rng};
+  }
+};
+KP_WS_COMPLETE(KeyedWs);
+
 // kp_conve.hip
 struct ConveWs {
   DevBuf x, s1, s2;               // kelpie rows [ns][dp] and their Adam moments
@@ -311,6 +327,11 @@ struct kp_ctx : ImageBufs {
   ComplexWs cx;
   TranseWs te;
   ConveWs cv;
+  KeyedWs kd;
+  // kp_ctx_arm_keyed's copy of the request (keyed.init_key / slot_key point into the vectors)
+  bool keyed_armed = false;
+  kp_keyed keyed{};
+  std::vector<uint64_t> keyed_init, keyed_slot;
   std::string err;
   Timing timing;
   bool time_hot = true;
@@ -350,6 +371,7 @@ struct kp_ctx : ImageBufs {
     add(cx.all());
     add(te.all());
     add(cv.all());
+    add(kd.all());
     return v;
   }
   hipEvent_t event(size_t i) {
@@ -433,7 +455,19 @@ struct PostReq {
   // hyper-parameters and outputs.  ComplEx / DistMult; the lists, the probes, the trace and
   // the marks are not offered with it yet (require_request)
   const kp_f64* f64 = nullptr;
+  // the armed context's keyed request (nullptr: the draws are the batch's x0 / rng_off / rng):
+  // the batch's three buffers are NULL and the family generates them (kp_keyed.hip)
+  const kp_keyed* keyed = nullptr;
 };
+// kp_keyed.hip: the keyed draws on the context's stream.  keyed_x0_dev: the slots' rows
+// [ns][dp] into dX, padding included.  keyed_rng_dev: the slots' words into dRng at the offsets
+// rng_off (host, [ns + 1]: kp_keyed_words_host's prefix sums).
+void keyed_x0_dev(kp_ctx* c, const kp_keyed* k, int ns, float* dX);
+void keyed_rng_dev(kp_ctx* c, const kp_hp* hp, const kp_keyed* k, int ns, const int32_t* row_off,
+                   const int64_t* rng_off, int32_t* dRng);
+// kp_keyed_draws: the request check, the generation into the keyed workspace and the download
+void keyed_draws(kp_ctx* c, const kp_hp* hp, int ns, const int32_t* row_off, const kp_keyed* k, float* out_x0,
+                 int64_t* out_rng_off, int32_t* out_rng, int64_t cap);
 void complex_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const PostReq& rq = {});
 // kp_complex.hip, product policy
 void distmult_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* b, const PostReq& rq = {});

@@ -837,7 +837,7 @@ CxDev cx_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostRe
                     std::vector<float>& xp) {
   const int ns = bt->n_slots, DP = c->dp;
   CxDev d;
-  d.X = upload_x0(c, c->cx.x, bt, xp);
+  d.X = upload_x0(c, c->cx.x, bt, xp, rq.keyed);
   d.S1 = ensure_n<float>(c->cx.s1, (size_t)ns * DP);
   d.S2 = ensure_n<float>(c->cx.s2, (size_t)ns * DP);
   KP_HIP(hipMemsetAsync(d.S1, 0, sizeof(float) * (size_t)ns * DP, c->stream));
@@ -1394,6 +1394,29 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostRe
   // model family (kp_batch_check.hpp)
   require_request(c, hp, bt, rq, true, kp_model_name(c->model));
   const CxOpt opt = make_opt(hp, who);
+
+  // an armed call (kp_ctx_arm_keyed): the step plan is host work, so the permutations of the
+  // multi-step slots (R > batch_size; none in most batches) are generated on the device and
+  // brought back for it; the rows are generated in place by cx_workspaces
+  kp_batch keyed_bt;
+  std::vector<int64_t> keyed_off;
+  std::vector<int32_t> keyed_perm;
+  if (rq.keyed) {
+    keyed_off.resize((size_t)ns + 1);
+    (void)kp_keyed_words_host(c->model, hp, ns, bt->row_off, nullptr, keyed_off.data());  // require_request checked it
+    const int64_t total = keyed_off[ns];
+    keyed_perm.resize((size_t)std::max<int64_t>(1, total));
+    if (total > 0) {
+      int32_t* dPerm = ensure_n<int32_t>(c->kd.rng, (size_t)total);
+      keyed_rng_dev(c, hp, rq.keyed, ns, bt->row_off, keyed_off.data(), dPerm);
+      KP_HIP(hipMemcpyAsync(keyed_perm.data(), dPerm, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+      KP_HIP(hipStreamSynchronize(c->stream));
+    }
+    keyed_bt = *bt;
+    keyed_bt.rng_off = keyed_off.data();
+    keyed_bt.rng = keyed_perm.data();
+    bt = &keyed_bt;
+  }
 
   CxStepPlan sp;
   if (const char* why = cx_step_plan(c->n_ent, c->n_rel2, hp->batch_size, hp->epochs, bt, sp))

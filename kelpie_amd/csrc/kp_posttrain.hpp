@@ -17,6 +17,7 @@
 
 #include "kp_batch_check.hpp"
 #include "kp_common.hpp"
+#include "kp_keyed.hpp"
 #include "kp_marks_check.hpp"
 #include "kp_probe_check.hpp"
 #include "kp_trace_check.hpp"
@@ -44,8 +45,14 @@ inline void require_request(const kp_ctx* c, const kp_hp* hp, const kp_batch* bt
   if (bt->n_slots == 0) {
     KP_REQUIRE(rq.k >= 0 && rq.k <= 32, "kp_posttrain_rank_topk: k must be in [0, 32]");
     KP_REQUIRE(rq.n_probes() == 0, "kp_posttrain_rank_probes: probes without a slot");
+    KP_REQUIRE(!rq.keyed || rq.keyed->n_slots == 0, who + ": keyed draws: n_slots differs from the batch's");
   } else {
     if (const char* why = kp_check_batch(c->n_ent, c->n_rel2, c->dim, bt)) throw KpError{KP_EINVAL, who + ": " + why};
+    if (rq.keyed) {  // an armed call: the keyed request, before any device work (kp_keyed.hpp)
+      int code = KP_EINVAL;
+      if (const char* why = kp_check_keyed(c->model, hp, bt->n_slots, bt->row_off, rq.keyed, &code))
+        throw KpError{code, who + ": keyed draws: " + why};
+    }
     if (rq.f64) {  // kp_posttrain_rank_f64: its buffers, then the family, then what it does not offer yet
       KP_REQUIRE(rq.f64->x0 && rq.f64->out_score, who + ": fp64: missing x0 or out_score");
       if (c->model != KP_MODEL_COMPLEX && c->model != KP_MODEL_DISTMULT)
@@ -89,9 +96,16 @@ inline AdamStep adam_step(const kp_hp* hp, int t) {
 }
 
 // x0 [ns][dim] zero-padded to [ns][dp] in `xp` (kept by the caller for download_results)
-// and uploaded into `b`
-inline float* upload_x0(kp_ctx* c, DevBuf& b, const kp_batch* bt, std::vector<float>& xp) {
+// and uploaded into `b`; with `keyed`, generated there instead (kp_keyed.hip)
+inline float* upload_x0(kp_ctx* c, DevBuf& b, const kp_batch* bt, std::vector<float>& xp,
+                        const kp_keyed* keyed = nullptr) {
   const int ns = bt->n_slots;
+  if (keyed) {  // an armed call: the rows are generated where the upload would land
+    xp.assign((size_t)ns * c->dp, 0.f);
+    float* dX = ensure_n<float>(b, xp.size());
+    keyed_x0_dev(c, keyed, ns, dX);
+    return dX;
+  }
   xp.assign((size_t)ns * c->dp, 0.f);
   for (int s = 0; s < ns; ++s)
     std::memcpy(&xp[(size_t)s * c->dp], bt->x0 + (size_t)s * c->dim, sizeof(float) * c->dim);

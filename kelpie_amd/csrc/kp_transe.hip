@@ -642,20 +642,34 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   // before the first upload: the buffers below are sized by DP, the kernels hold DP / 256 float4 per lane
   KP_REQUIRE(DP <= 512, "TransE: dimension > 512 not supported");
   KP_REQUIRE(hp->neg_ratio >= 1 && hp->batch_size >= 1 && hp->epochs >= 0, "TransE: bad hyper-parameters");
+  // an armed call (kp_ctx_arm_keyed): the word offsets are the keyed layout's, and the rows and
+  // the words are generated where the uploads land
+  std::vector<int64_t> keyed_off;
+  if (rq.keyed) {
+    keyed_off.resize((size_t)ns + 1);
+    (void)kp_keyed_words_host(c->model, hp, ns, bt->row_off, nullptr, keyed_off.data());  // require_request checked it
+  }
+  const int64_t* rng_off = rq.keyed ? keyed_off.data() : bt->rng_off;
   std::vector<TeSlot> slots(ns);
   for (int s = 0; s < ns; ++s) {
     const int R = bt->row_off[s + 1] - bt->row_off[s];
-    slots[s] = TeSlot{bt->row_off[s], R, (long long)bt->rng_off[s]};
-    KP_REQUIRE(bt->rng_off[s + 1] - bt->rng_off[s] >= (int64_t)hp->epochs * 3 * R,
+    slots[s] = TeSlot{bt->row_off[s], R, (long long)rng_off[s]};
+    KP_REQUIRE(rng_off[s + 1] - rng_off[s] >= (int64_t)hp->epochs * 3 * R,
                "TransE: missing per-epoch draws (order | entities | head_or_tail)");
   }
   const int total_rows = bt->row_off[ns];
   std::vector<float> xp;
-  float* dX = upload_x0(c, c->te.x, bt, xp);
+  float* dX = upload_x0(c, c->te.x, bt, xp, rq.keyed);
   TeSlot* dSlots = upload(c, c->te.slots, slots.data(), slots.size());
   int32_t* dRows = upload(c, c->te.rows, bt->rows, (size_t)std::max(1, 3 * total_rows));
-  const int64_t nrng = bt->rng_off[ns];
-  int32_t* dRng = upload(c, c->te.rng, bt->rng, (size_t)std::max<int64_t>(1, nrng));
+  const int64_t nrng = rng_off[ns];
+  int32_t* dRng;
+  if (rq.keyed) {
+    dRng = ensure_n<int32_t>(c->te.rng, (size_t)std::max<int64_t>(1, nrng));
+    keyed_rng_dev(c, hp, rq.keyed, ns, bt->row_off, rng_off, dRng);
+  } else {
+    dRng = upload(c, c->te.rng, bt->rng, (size_t)std::max<int64_t>(1, nrng));
+  }
   const RankRows pd = upload_probes(c, bt, rq, dX);
   // kp_posttrain_rank_marks: the mark rows (each the padded x0 until its epoch ends) and the epochs
   const MarksDev md = upload_marks(c, c->te.marks, hp, bt, rq, dX);

@@ -22,6 +22,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
+from . import keyed as _keyed
 from .hparams import optimizer_hp
 from .data import MANY_TO_ONE, ONE_TO_ONE, Dataset, KelpieView
 from .models import FrozenModel
@@ -53,6 +54,9 @@ class _Slot:
     # probes ranked on this slot's post-trained row (compute_side_effects): a list of
     # (triple in original ids, (p, o) in kelpie form, filter); None: no probes asked for
     probes: list = None
+    # keyed draws (engine.draws = "keyed"): (init_key, slot_key) of the slot; x0 and rng are
+    # then None and the device generates both (kelpie_amd/keyed.py, Context.arm_keyed)
+    keys: tuple = None
 
 
 def _contiguous_draws(slots, total, ctx=None):
@@ -183,6 +187,69 @@ class PostTrainingEngine(RelevanceEngine):
         self._trace = False
         self._marks = None
         self._precision = "fp32"
+        self._draws = "reference"
+        self._seed = 0
+
+    DRAWS = ("reference", "keyed")
+
+    @property
+    def draws(self):
+        """``"reference"`` (the default: every post-training's kelpie init, epoch shuffles and
+        negatives come from the process-global torch / numpy generators in the reference's call
+        order, bit for bit) or ``"keyed"``: every slot's random numbers are a pure function of
+        ``(seed, prediction, rule)``, generated on the device by a counter-based generator
+        (include/kelpie_hip.h, "Keyed draws"; the keys: kelpie_amd/keyed.py).  A relevance is
+        then a function of its arguments: the same in any batch, beside any other prediction, in
+        any order, on a fresh engine.  A prediction's base and edited post-trainings start from
+        the same row.  No keyed call reads or advances the torch or numpy generators;
+        ``checkpoints`` lists are accepted and get nothing to rewind.  Python's ``random`` keeps
+        its role (the builder's termination, the conversion entities).  TransE, ComplEx and
+        DistMult.  Not offered for ConvE, with ``precision = "fp64"``, a slot sharding,
+        ``compute_relevance_pipeline`` or ``submit_batch`` (NotImplementedError before any
+        work).  Setting it clears the cached base results."""
+        return self._draws
+
+    @draws.setter
+    def draws(self, value):
+        if value not in self.DRAWS:
+            raise ValueError(f"draws must be one of {self.DRAWS}, got {value!r}")
+        if value != self._draws:
+            self.set_cache()
+        self._draws = value
+
+    @property
+    def seed(self):
+        """The seed of the keyed draws (an integer of at most 64 bits, signed; default 0).
+        Not read in reference mode.  Setting it clears the cached base results."""
+        return self._seed
+
+    @seed.setter
+    def seed(self, value):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+            raise TypeError(f"seed must be an integer, got {type(value).__name__}")
+        if not -2 ** 63 <= int(value) < 2 ** 63:
+            raise ValueError("seed must fit a signed 64-bit integer")
+        if int(value) != self._seed:
+            self.set_cache()
+        self._seed = int(value)
+
+    def _keyed(self):
+        return self._draws == "keyed"
+
+    def _refuse_keyed(self, what=None):
+        """Keyed mode's refusals, before any work."""
+        if not self._keyed():
+            return
+        if what is not None:
+            raise NotImplementedError(f"draws='keyed' on {what}: keyed batches run one at a time")
+        if not hasattr(self.model, "keyed_params"):
+            raise NotImplementedError(f"draws='keyed': {self.model.name} has no keyed draws "
+                                      "(TransE, ComplEx and DistMult only)")
+        if self._fp64():
+            raise NotImplementedError("draws='keyed' with precision='fp64': kp_posttrain_rank_f64 takes no keys")
+        if self._sharded():
+            raise NotImplementedError("draws='keyed' with a slot sharding: the keyed results are not gathered "
+                                      "across ranks")
 
     PRECISIONS = ("fp32", "fp64")
     _precision = "fp32"
@@ -383,6 +450,8 @@ class PostTrainingEngine(RelevanceEngine):
         and append its slots.  Returns (pt_slot, base_key)."""
         pred = tuple(int(v) for v in pred)
         view = self._get_kelpie_dataset(pred[0])
+        if self._keyed():
+            return self._schedule_keyed(pred, view, triples, mode, slots, pending_base)
         if getattr(self.model, "fused_call_draws", False):
             return self._schedule_fused(pred, view, triples, mode, slots, pending_base)
         if self._sharded():
@@ -399,6 +468,27 @@ class PostTrainingEngine(RelevanceEngine):
         rows, delta = view.removed(triples) if mode == "necessary" else view.added(triples)
         filt = view.filter_for(kp[1], delta.get(kp[1]))
         slots.append(self._slot(x_pt, rows, kp, filt))
+        slots[-1].probes = self._slot_probes(view, delta)
+        return len(slots) - 1, pred
+
+    def _schedule_keyed(self, pred, view, triples, mode, slots, pending_base):
+        """_schedule in keyed mode: the same slots, each with its two keys instead of draws.  No
+        generator is asked for anything; the plain path for every family."""
+        kp = view.as_kelpie_triple(pred)
+        ik = _keyed.init_key(self._seed, pred)
+        if pred not in self.base_pt_results and pred not in pending_base:
+            pending_base[pred] = len(slots)
+            slots.append(_Slot(x0=None, rows=view.base_rows, rng=None, pred=tuple(int(v) for v in kp),
+                               filt=list(view.filter_for(kp[1])),
+                               keys=(ik, _keyed.slot_key(self._seed, pred, _keyed.ROLE_BASE, mode))))
+            slots[-1].probes = self._slot_probes(view, None)
+        # the rule in its canonical (sorted) order: an addition appends its rows in the rule's
+        # order, and a row's draws go by its position
+        triples = sorted(tuple(int(v) for v in t) for t in triples)
+        rows, delta = view.removed(triples) if mode == "necessary" else view.added(triples)
+        slots.append(_Slot(x0=None, rows=rows, rng=None, pred=tuple(int(v) for v in kp),
+                           filt=list(view.filter_for(kp[1], delta.get(kp[1]))),
+                           keys=(ik, _keyed.slot_key(self._seed, pred, _keyed.ROLE_EDITED, mode, triples))))
         slots[-1].probes = self._slot_probes(view, delta)
         return len(slots) - 1, pred
 
@@ -642,6 +732,7 @@ class PostTrainingEngine(RelevanceEngine):
 
     def _schedule_all(self, items, checkpoints):
         """_schedule_multi, with every queued TransE call's draws made before it returns or raises."""
+        self._refuse_keyed()  # before any work
         self._refuse_fp64()  # before any draw
         if self._top_k and self._sharded():
             # before any draw: the gather's records hold a score and a rank per slot
@@ -721,20 +812,24 @@ class PostTrainingEngine(RelevanceEngine):
         n = len(slots)
         if slots and slots[0].native is not None:
             return self._pack_native(slots, ctx)
-        x0 = np.stack([s.x0 for s in slots]).astype(np.float64 if self._fp64() else np.float32)
+        # keyed draws: no x0, no rng_off, no rng (the armed context generates them)
+        keyed = bool(slots) and slots[0].keys is not None
+        x0 = None if keyed else np.stack([s.x0 for s in slots]).astype(np.float64 if self._fp64() else np.float32)
         row_off = np.zeros(n + 1, np.int32)
         row_off[1:] = np.cumsum([len(s.rows) for s in slots])
         rows = np.concatenate([s.rows.reshape(-1, 3) for s in slots]).astype(np.int32) if row_off[-1] \
             else np.zeros((0, 3), np.int32)
-        rng_off = np.zeros(n + 1, np.int64)
-        rng_off[1:] = np.cumsum([s.rng.size for s in slots])
-        rng = _contiguous_draws(slots, int(rng_off[-1]), ctx)
+        rng_off = rng = None
+        if not keyed:
+            rng_off = np.zeros(n + 1, np.int64)
+            rng_off[1:] = np.cumsum([s.rng.size for s in slots])
+            rng = _contiguous_draws(slots, int(rng_off[-1]), ctx)
         pred = np.array([s.pred for s in slots], np.int32)
         filt_off = np.zeros(n + 1, np.int32)
         filt_off[1:] = np.cumsum([len(s.filt) for s in slots])
         filt = np.concatenate([np.asarray(s.filt, np.int32) for s in slots]) if filt_off[-1] \
             else np.zeros(1, np.int32)
-        assert x0.shape == (n, self.model.dimension)
+        assert keyed or x0.shape == (n, self.model.dimension)
         return x0, row_off, rows, rng_off, rng, pred, filt_off, filt
 
     @staticmethod
@@ -857,6 +952,9 @@ class PostTrainingEngine(RelevanceEngine):
         marks = self._marks
         if marks is not None:
             kw["marks"] = marks
+        if slots[0].keys is not None:  # keyed draws: the context generates x0 and the words from the keys
+            scale, bound = self.model.keyed_params()
+            ctx.arm_keyed([s.keys[0] for s in slots], [s.keys[1] for s in slots], scale, bound)
         if self._fp64():  # the fp64 entry point alone (no optional request: _refuse_fp64)
             out = _lib.RankResult(*ctx.posttrain_rank_f64(self._kp_hp64, *packed))
         else:
@@ -1101,6 +1199,7 @@ class PostTrainingEngine(RelevanceEngine):
         import threading
 
         from . import rng as _rng_mod
+        self._refuse_keyed("submit_batch")
         ctxs = self.model.contexts(2)
         self._submit_n = getattr(self, "_submit_n", -1) + 1
         ctx = ctxs[self._submit_n % len(ctxs)]
@@ -1215,6 +1314,7 @@ class PostTrainingEngine(RelevanceEngine):
         import os
         import threading
 
+        self._refuse_keyed("compute_relevance_pipeline")
         if self._fp64():  # before any draw
             raise NotImplementedError("precision='fp64' on compute_relevance_pipeline: the fp64 path runs one "
                                       "batch at a time")
@@ -1456,7 +1556,7 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
 
     def _schedule_multi(self, items, checkpoints):
         slots, pending, jobs = [], {}, []
-        fast = checkpoints is None and getattr(self.model, "fused_call_draws", False)
+        fast = checkpoints is None and getattr(self.model, "fused_call_draws", False) and not self._keyed()
         for pred, rules in items:
             self._cur_probes = self._probes_of(pred)
             if fast and all(len(r) for r in rules):

@@ -152,6 +152,10 @@ class MultiClassNLLModel(FrozenModel):
     def posttrain_draws(self, rows, hp, rng):
         return rng.complex_epochs(len(rows), int(hp["epochs"]), int(hp["batch_size"]))
 
+    def keyed_params(self):
+        """(x0_scale, neg_bound) of the keyed draws (kp_keyed): the uniform row's init_scale."""
+        return self.init_scale, 0
+
     skip_needs_rows = False
 
     def kelpie_skip(self, rng):
@@ -219,6 +223,11 @@ class TransE(FrozenModel):
     def posttrain_draws(self, rows, hp, rng):
         return rng.transe_epochs(len(rows), int(hp["epochs"]), int(hp["negative_triples_ratio"]),
                                  self.dataset.num_entities + 1)
+
+    def keyed_params(self):
+        """(x0_scale, neg_bound) of the keyed draws (kp_keyed): xavier_normal_'s std as a float32
+        and the bound of the negatives, both as the reference-order draws take them."""
+        return float(np.float32(math.sqrt(2.0 / float(self.dimension + 1)))), self.dataset.num_entities + 1
 
 
 class ConvE(FrozenModel):

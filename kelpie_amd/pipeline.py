@@ -27,12 +27,17 @@ from .prefilters import PREFILTERS, TOPOLOGY_PREFILTER, TYPE_PREFILTER, Topology
 
 
 class Pipeline:
-    def __init__(self, dataset, prefilter, builder):
+    def __init__(self, dataset, prefilter, builder, draws=None, seed=None):
         self.dataset = dataset
         self.prefilter = prefilter
         self.builder = builder
         self.engine = self.builder.engine
         self.model = self.engine.model
+        # the source of the post-training draws (PostTrainingEngine.draws / .seed); None: as the engine has it
+        if seed is not None:
+            self.engine.seed = seed
+        if draws is not None:
+            self.engine.draws = draws
 
     def explain(self, pred, prefilter_k=-1):
         if isinstance(self.engine, PostTrainingEngine):
@@ -56,8 +61,9 @@ class SufficientPipeline(Pipeline):
 
 
 def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="auto", entity_classes=None,
-                   pipelined=False, top_k=0, side_effects=0, trace=False):
-    """explain.py:49-89 for the post-training engines (baseline=None, no summarisation)."""
+                   pipelined=False, top_k=0, side_effects=0, trace=False, draws="reference", seed=0):
+    """explain.py:49-89 for the post-training engines (baseline=None, no summarisation).
+    ``draws`` / ``seed``: the source of the post-training draws (PostTrainingEngine.draws)."""
     if prefilter == TYPE_PREFILTER:
         raise NotImplementedError("type_based prefilter: out of scope (kelpie_amd/prefilters.py)")
     cls = PREFILTERS.get(prefilter, TopologyPreFilter) if prefilter else PREFILTERS[TOPOLOGY_PREFILTER]
@@ -67,13 +73,13 @@ def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="a
         engine = NecessaryPostTrainingEngine(model, dataset, hp)
         return NecessaryPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
                                                                   top_k=top_k, side_effects=side_effects,
-                                                                  trace=trace))
+                                                                  trace=trace, draws=draws, seed=seed))
     if mode == "sufficient":
         xsi = 0.9 if xsi is None else xsi
         engine = SufficientPostTrainingEngine(model, dataset, hp)
         return SufficientPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
                                                                   top_k=top_k, side_effects=side_effects,
-                                                                  trace=trace))
+                                                                  trace=trace, draws=draws, seed=seed))
     raise ValueError(f"unknown mode {mode!r}")
 
 
