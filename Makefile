@@ -72,7 +72,8 @@ build/san/host_tsan: $(SAN_SRC) include/kelpie_hip.h
 #   trace_check  the trace's step counts and check (kp_trace_check.hpp)
 #   marks_check  the epoch marks' check, plan and rank rows (kp_marks_check.hpp)
 #   keyed        the keyed draws' generator, streams, word counts and request check (kp_keyed.hpp)
-DRIVERS := batch_check attn_plan step_plan probe_check trace_check marks_check keyed
+#   margins      the rank margins' request check and threshold rule (kp_margins_check.hpp)
+DRIVERS := batch_check attn_plan step_plan probe_check trace_check marks_check keyed margins
 DRIVER_DEP := $(wildcard kelpie_amd/csrc/kp_*_check.hpp kelpie_amd/csrc/kp_*_plan.hpp) kelpie_amd/csrc/kp_keyed.hpp \
               include/kelpie_hip.h
 $(DRIVERS) $(DRIVERS:%=%_asan): %: build/san/%

@@ -306,6 +306,68 @@ int kp_posttrain_rank_marks(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch,
                             float* out_scores, const kp_probes* probes, const kp_trace* trace,
                             const kp_marks* marks);
 
+/* ---- Rank margins: how far every rank row's rank is from changing ----
+ * A rank row is anything the fp64 rank ranks: a slot's target, a probe, a mark.  For a rank row
+ * with target column o, c_e is the value the count compares for column e (columns 0 .. n_ent,
+ * column n_ent = the kelpie entity) and c_t the target's.  Masking is exactly the rank's, the
+ * filtered-target rules of each family included, and `own` is what the rank counts for the
+ * target column itself (0 or 1).  The compared value and the score units per family:
+ *   ComplEx / DistMult   the fp64 score          the same
+ *   ConvE                the fp64 logit          the same
+ *   TransE L2            the squared distance    sqrt(c)
+ *   TransE L1            the L1 distance         the same
+ * Tolerance: a call carries one tol, finite, 0 <= tol <= 1.  Per row delta = tol * max(1, |v_t|)
+ * with v_t = c_t in score units.
+ * Thresholds, in compared units, once per row in fp64:
+ *   maximizers  thr_lo = c_t + delta           thr_hi = c_t - delta
+ *   L1          thr_lo = c_t - delta           thr_hi = c_t + delta
+ *   L2          thr_lo = max(v_t - delta, 0)^2 thr_hi = (v_t + delta)^2
+ *   tol == 0    both are c_t itself, not a recomputation of it.
+ * (L2: a threshold that the rounding of the root and the square would carry across c_t, which
+ * takes a delta below one ulp of v_t, is c_t.)
+ * Band:
+ *   rank_lo = own + #{e != o unmasked: c_e at least as good as thr_lo}
+ *   rank_hi = own + #{e != o unmasked: c_e at least as good as thr_hi}
+ * "as good as" is >= for maximizers and <= for minimizers.  ConvE keeps the saturation rule on
+ * both thresholds: with a saturated target (float32 sigmoid 1.0) a saturated column counts in
+ * both.  Hence rank_lo <= out_rank <= rank_hi always, and at tol == 0 all three are equal: the
+ * predicate is the rank's own.
+ * Ties: the number of other unmasked columns with c_e == c_t exactly.
+ * Nearest competitors: id_better is, among the unmasked columns other than o strictly better
+ * than the target, the one closest to it in compared order, the lower column id on equal
+ * values; gap_better = |v_e - v_t| in score units, fp64 (>= 0; it may be 0 after the L2 square
+ * root).  id_worse / gap_worse are the same on the other side.  Without such a column the id
+ * is -1 and the gap +inf.  The kelpie column takes part unless it is masked.
+ * Determinism: a margin is a pure function of the row's inputs.  The counts are integer sums of
+ * per-workgroup partial counts, the nearest competitors minima of (value key, column) pairs;
+ * no floating-point atomics; a rerun on a fresh context gives the same bits.
+ *
+ * One set of outputs per kind of rank row; a NULL pointer = not wanted (rank_lo and rank_hi go
+ * together). */
+typedef struct {
+  int64_t *rank_lo, *rank_hi, *ties;
+  double *gap_better, *gap_worse;
+  int32_t *id_better, *id_worse;
+} kp_margin_out;
+typedef struct {
+  double tol;
+  kp_margin_out slots;  /* [n_slots] */
+  kp_margin_out probes; /* [probes->n] */
+  kp_margin_out marks;  /* [n_slots][marks->n] */
+} kp_margins;
+
+/* kp_posttrain_rank_marks, plus the margins of every rank row.  Every other output of the call
+ * (out_x, out_score, out_rank, the lists, the probes, the trace, the marks) is bit for bit what
+ * it is without margins: the margins come from one more fp64 pass over the entity table per
+ * rank row, after the row's own count.  margins == NULL is kp_posttrain_rank_marks.
+ * KP_EINVAL (after the marks check, before any upload) for a tol that is NaN, negative or above
+ * 1, for probe or mark outputs wanted without probes or marks, or for an output set with only
+ * one of rank_lo / rank_hi; KP_ENOTSUP when the context ranks in fp32 (KP_TE_RANK=f32,
+ * KP_CV_RANK=f32).  Not offered on kp_posttrain_rank_f64. */
+int kp_posttrain_rank_margins(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
+                              float* out_scores, const kp_probes* probes, const kp_trace* trace,
+                              const kp_marks* marks, const kp_margins* margins);
+
 /* ---- fp64: post-train and rank in double precision on the device (ComplEx, DistMult) ----
  * The fp64 result of a slot is what the reference returns when every tensor of the run is a
  * float64 one (the `fp64` variant of tools/conditioning.py):

@@ -32,7 +32,7 @@ EXPORTS = ["kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_posttrain_ran
            "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free", "kp_ctx_set_inflight",
            "kp_last_attn_plan", "kp_posttrain_rank_topk", "kp_posttrain_rank_probes", "kp_trace_steps",
            "kp_posttrain_rank_trace", "kp_posttrain_rank_marks", "kp_posttrain_rank_f64", "kp_ctx_arm_keyed",
-           "kp_keyed_rng_words", "kp_keyed_draws"]
+           "kp_keyed_rng_words", "kp_keyed_draws", "kp_posttrain_rank_margins"]
 
 
 class ModelDesc(C.Structure):
@@ -89,6 +89,39 @@ class Trace(C.Structure):
 class Marks(C.Structure):
     _fields_ = [("n", C.c_int32), ("epochs", C.c_void_p), ("out_score", C.c_void_p), ("out_rank", C.c_void_p),
                 ("out_x", C.c_void_p)]
+
+
+class MarginOut(C.Structure):
+    """kp_margin_out: one kind of rank row's margin outputs (NULL: not wanted)."""
+    _fields_ = [("rank_lo", C.c_void_p), ("rank_hi", C.c_void_p), ("ties", C.c_void_p), ("gap_better", C.c_void_p),
+                ("gap_worse", C.c_void_p), ("id_better", C.c_void_p), ("id_worse", C.c_void_p)]
+
+
+class Margins(C.Structure):
+    """kp_margins: the tolerance and the slots', probes' and marks' outputs (include/kelpie_hip.h,
+    "Rank margins")."""
+    _fields_ = [("tol", C.c_double), ("slots", MarginOut), ("probes", MarginOut), ("marks", MarginOut)]
+
+
+MARGIN_FIELDS = (("rank_lo", np.int64), ("rank_hi", np.int64), ("ties", np.int64), ("gap_better", np.float64),
+                 ("gap_worse", np.float64), ("id_better", np.int32), ("id_worse", np.int32))
+
+
+def check_margin_tol(tol):
+    """A margins tolerance as a float: finite and in [0, 1] (include/kelpie_hip.h, "Rank
+    margins").  TypeError for a value that is no real number, ValueError outside the range."""
+    if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (int, float, np.integer, np.floating)):
+        raise TypeError(f"margins: tol must be a real number, got {tol!r}")
+    tol = float(tol)
+    if not 0.0 <= tol <= 1.0:  # NaN included
+        raise ValueError(f"margins: tol must be in [0, 1], got {tol}")
+    return tol
+
+
+def _margin_arrays(shape):
+    """One kind of rank row's output arrays and their kp_margin_out."""
+    arrs = {name: np.zeros(shape, dt) for name, dt in MARGIN_FIELDS}
+    return arrs, MarginOut(*(_ptr(arrs[name]) for name, _ in MARGIN_FIELDS))
 
 
 class Keyed(C.Structure):
@@ -155,6 +188,10 @@ def lib():
         if hasattr(L, "kp_posttrain_rank_marks"):  # KELPIE_HIP_LIB may name a build from before the marks
             L.kp_posttrain_rank_marks.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
                                                   C.c_void_p, C.POINTER(Probes), C.POINTER(Trace), C.POINTER(Marks)]
+        if hasattr(L, "kp_posttrain_rank_margins"):  # KELPIE_HIP_LIB may name a build from before the margins
+            L.kp_posttrain_rank_margins.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
+                                                    C.c_void_p, C.POINTER(Probes), C.POINTER(Trace), C.POINTER(Marks),
+                                                    C.POINTER(Margins)]
         if hasattr(L, "kp_posttrain_rank_f64"):  # KELPIE_HIP_LIB may name a build from before the fp64 path
             L.kp_posttrain_rank_f64.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.POINTER(F64)]
         if hasattr(L, "kp_ctx_arm_keyed"):  # KELPIE_HIP_LIB may name a build from before the keyed draws
@@ -460,14 +497,15 @@ class RankResult(NamedTuple):
     probes: object = None  # (scores, ranks)
     loss: object = None    # one array per slot
     marks: object = None   # (scores, ranks, rows or None)
+    margins: object = None  # (slots, probes or None, marks or None): dicts of MARGIN_FIELDS arrays
 
 
-def split_rank_result(out, topk=0, probes=None, trace=False, marks=None) -> RankResult:
+def split_rank_result(out, topk=0, probes=None, trace=False, marks=None, margins=None) -> RankResult:
     """``Context.posttrain_rank``'s tuple (of a context or of a stand-in that follows its
     convention) by name, given the requests the call was made with: the optional elements
-    follow (scores, ranks, rows) in the order topk, probes, trace, marks, each only when asked
-    for."""
-    asked = (bool(topk), probes is not None, bool(trace), marks is not None)
+    follow (scores, ranks, rows) in the order topk, probes, trace, marks, margins, each only
+    when asked for."""
+    asked = (bool(topk), probes is not None, bool(trace), marks is not None, margins is not None)
     if len(out) != 3 + sum(asked):
         raise ValueError(f"posttrain_rank returned {len(out)} elements for {sum(asked)} optional requests")
     rest = iter(out[3:])
@@ -511,7 +549,7 @@ class Context:
             pass
 
     def posttrain_rank(self, hp: HP, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False, topk=0,
-                       probes=None, trace=False, marks=None):
+                       probes=None, trace=False, marks=None, margins=None):
         """kp_posttrain_rank: (target scores, ranks, final rows or None).  With ``topk`` > 0
         (kp_posttrain_rank_topk) a fourth element: (ids int32 [n][topk], scores float32
         [n][topk]), the slots' best unmasked tails, -1 / 0 past the last one.  With ``probes``
@@ -522,7 +560,11 @@ class Context:
         kp_trace_steps).  With ``marks`` = a list of epochs (kp_posttrain_rank_marks) a last
         element after that: (scores float32 [n][m], ranks int64 [n][m], rows float32
         [n][m][dim] or None without ``want_x``), every slot's result after each marked epoch:
-        what this call returns for the slot with ``hp.epochs`` set to that epoch."""
+        what this call returns for the slot with ``hp.epochs`` set to that epoch.  With
+        ``margins`` = a tolerance in [0, 1] (kp_posttrain_rank_margins) a last element after
+        that: (slots, probes, marks), each a dict of arrays ``rank_lo``, ``rank_hi``, ``ties``
+        (int64), ``gap_better``, ``gap_worse`` (float64), ``id_better``, ``id_worse`` (int32)
+        shaped as that kind's ranks ([n], [m], [n][marks]), None for a kind the call has not."""
         topk = int(topk)
         if not 0 <= topk <= 32:
             raise ValueError(f"topk must be in [0, 32], got {topk}")
@@ -541,7 +583,7 @@ class Context:
         out_r = np.zeros(n, np.int64)
         b = Batch(n, _ptr(x0), _ptr(row_off), _ptr(rows), _ptr(rng_off), _ptr(rng), _ptr(pred), _ptr(filt_off),
                   _ptr(filt), _ptr(out_x), _ptr(out_s), _ptr(out_r))
-        if topk == 0 and probes is None and not trace and marks is None:
+        if topk == 0 and probes is None and not trace and marks is None and margins is None:
             check(lib().kp_posttrain_rank(self.h, C.byref(hp), C.byref(b)), self.h)
             return out_s, out_r, out_x
         # the optional requests, each marshalled once; the entry point is the first that takes
@@ -580,7 +622,18 @@ class Context:
             ret += ((m_s, m_r, m_x),)
         ref = lambda st: C.byref(st) if st is not None else None  # noqa: E731
         head = (self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top))
-        if mk is not None:
+        if margins is not None:
+            # the tolerance as given: the library checks its range
+            mg = Margins(float(margins))
+            mg_s, mg.slots = _margin_arrays(n)
+            mg_p = mg_m = None
+            if pr is not None and pr.n > 0:
+                mg_p, mg.probes = _margin_arrays(pr.n)
+            if mk is not None:
+                mg_m, mg.marks = _margin_arrays((n, mk.n))
+            ret += ((mg_s, mg_p, mg_m),)
+            rc = lib().kp_posttrain_rank_margins(*head, ref(pr), ref(tr), ref(mk), C.byref(mg))
+        elif mk is not None:
             rc = lib().kp_posttrain_rank_marks(*head, ref(pr), ref(tr), ref(mk))
         elif tr is not None:
             rc = lib().kp_posttrain_rank_trace(*head, ref(pr), ref(tr))

@@ -57,6 +57,14 @@ steps (``engine.trace``), and each record gains ``"traces"``, aligned with
 ``rule_to_relevance``: per rule ``{"base", "post"}``, each the list of losses in step order
 (the sufficient engine: one such record per conversion entity, with its label).  A base
 result cached without a trace gives None.
+
+With ``margins`` = a tolerance in [0, 1] every post-training also reports how far its rank is
+from changing (``engine.margin_tol``), and each record gains ``"margins"``, aligned with
+``rule_to_relevance``: per rule ``engine.compute_margins``' report of it -- ``"relevance_lo"``
+/ ``"relevance_hi"`` and ``"base"`` / ``"post"`` with the rank bands, the ties and the nearest
+competitors (the sufficient engine: ``"conversions"``, one such pair per conversion entity,
+with its label).  A base result cached without margins gives None for its figures and for the
+band.  Not offered with a pipelined builder.
 """
 from __future__ import annotations
 
@@ -69,7 +77,7 @@ class StochasticBuilder:
     AUTO_MIN, AUTO_MAX = 4, 32
 
     def __init__(self, xsi, engine, summarization: str = None, max_explanation_length: int = 4, window=32,
-                 pipelined=False, top_k=0, side_effects=0, trace=False, draws=None, seed=None):
+                 pipelined=False, top_k=0, side_effects=0, trace=False, draws=None, seed=None, margins=None):
         if summarization is not None:
             raise NotImplementedError("summarisation (simulation / bisimulation) is out of scope")
         # the source of the post-training draws (PostTrainingEngine.draws / .seed; None: as the
@@ -99,6 +107,12 @@ class StochasticBuilder:
         self.trace = bool(trace)
         if self.trace:
             engine.trace = True
+        self.margins = margins
+        if margins is not None:
+            engine.margin_tol = margins  # validates the type and the range
+            self.margins = engine.margin_tol
+            if pipelined:
+                raise NotImplementedError("margins with a pipelined builder: batches with margins run one at a time")
         self._details = {}  # rule -> the engine's (post-trained, base) results of its evaluation
         self.stats = {"batches": 0, "evaluated": 0, "wasted": 0, "batch_s": 0.0, "schedule_s": 0.0, "pack_s": 0.0,
                       "lib_s": 0.0}
@@ -142,11 +156,13 @@ class StochasticBuilder:
             out["side_effects"] = [self._side_effect(self._details[rule]) for rule, _ in rule_to_rel]
         if self.trace:
             out["traces"] = [self._trace_of(self._details[rule]) for rule, _ in rule_to_rel]
+        if self.margins is not None:
+            out["margins"] = [self._margins_of(rel, self._details[rule]) for rule, rel in rule_to_rel]
         return out
 
     def _keep_details(self, rules, n):
         """The engine's per-rule results of its last batch, for the first ``n`` of ``rules``."""
-        if self.top_k or self.side_effects or self.trace:
+        if self.top_k or self.side_effects or self.trace or self.margins is not None:
             for rule, det in zip(rules[:n], self.engine.last_results):
                 self._details[tuple(rule)] = det
 
@@ -166,6 +182,13 @@ class StochasticBuilder:
         # sufficient: one pair per conversion entity
         return [{"entity": self.dataset.id_to_entity[e], "base": self._labelled(base, e), "post": self._labelled(pt, e)}
                 for e, (pt, base) in zip(self.engine.entities_to_convert, det)]
+
+    def _margins_of(self, rel, det):
+        """engine.compute_margins' report of one rule, a conversion entity by its label."""
+        out = self.engine._mg_rule(rel, det, self.margins)
+        for c in out.get("conversions", ()):
+            c["entity"] = self.dataset.id_to_entity[c["entity"]]
+        return out
 
     def _trace_of(self, det):
         if isinstance(det, tuple):  # necessary: (post-trained, base) of the prediction's subject

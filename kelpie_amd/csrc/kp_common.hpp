@@ -132,7 +132,10 @@ struct RankRowsWs {
   DevBuf target, rank;
   DevBuf q64, t64, bits;
   DevBuf enc_src, enc_q;
-  auto all() { return std::array{&trip, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &bits, &enc_src, &enc_q}; }
+  DevBuf mg_out, mg_part;  // the rows' margins [n] and one chunk's margin workspace (MarginDev)
+  auto all() {
+    return std::array{&trip, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &bits, &enc_src, &enc_q, &mg_out, &mg_part};
+  }
 };
 KP_WS_COMPLETE(RankRowsWs);
 
@@ -165,6 +168,7 @@ struct RankWs {
   DevBuf cand_key, cand_col;
   DevBuf top_ids, top_scores;
   DevBuf tr_off, tr_loss;  // kp_posttrain_rank_trace: the trace offsets [ns + 1] and the losses [steps]
+  DevBuf mg_out, mg_part;  // kp_posttrain_rank_margins: the slots' margins [ns] and their workspace (MarginDev)
   // kp_posttrain_rank_probes: row r is probe r, (slot, p, o), on the slots' kelpie rows; and
   // kp_posttrain_rank_marks: row s * marks + j is (row, p, o) of slot s on the family's mark
   // workspace [ns][marks][dp], with the slot's filter list.  Neither set reuses the slots'
@@ -173,7 +177,7 @@ struct RankWs {
   Rank64Ws f64;  // kp_posttrain_rank_f64
   auto all() {
     return kp_join(std::array{&pred, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &scores, &bits, &cand_key,
-                              &cand_col, &top_ids, &top_scores, &tr_off, &tr_loss},
+                              &cand_col, &top_ids, &top_scores, &tr_off, &tr_loss, &mg_out, &mg_part},
                    probes.all(), marks.all(), f64.all());
   }
 };
@@ -451,6 +455,8 @@ struct PostReq {
   // kp_posttrain_rank_marks' request (nullptr: no marks)
   const kp_marks* marks = nullptr;
   int n_marks() const { return marks ? marks->n : 0; }
+  // kp_posttrain_rank_margins' request (nullptr: no margins)
+  const kp_margins* margins = nullptr;
   // kp_posttrain_rank_f64's request (nullptr: the fp32 / bf16x3 step): the double inputs,
   // hyper-parameters and outputs.  ComplEx / DistMult; the lists, the probes, the trace and
   // the marks are not offered with it yet (require_request)
@@ -520,12 +526,36 @@ enum { RANK_TRIPLE_RESULTS = 0, RANK_PREDICT_TAILS = 1, RANK_SORT_POSITION = 2 }
 // values by column), ids and converted scores into d_top_ids / d_top_scores [n][topk]
 // (device), -1 / 0 past the last unmasked column; the ranks are those of topk == 0
 // bits_buf: the filter bitmaps' buffer (default c->rank.bits; the probe rows bring their own)
+// mg: also the rows' margins (include/kelpie_hip.h, "Rank margins"), by a margin form of the
+// count and a merge of its per-workgroup partials, launched after the rows' own count; the
+// ranks and every other result are those without it
 // launch_rank_f64's score kinds
 enum { RANK64_DOT = 0, RANK64_SIGMOID = 1, RANK64_DIST = 2, RANK64_DIST1 = 3 };
+// The margins of a set of rank rows on the device: the results [n] of every row, and the
+// workspace of one launch of `cap` rows over `nblk` column blocks of 256 (no allocation at
+// launch time: kp_posttrain.hpp's margin_buffers sizes both with the call's other buffers).
+struct MarginDev {
+  double tol = 0.0;
+  int64_t *rank_lo = nullptr, *rank_hi = nullptr, *ties = nullptr;  // [n]
+  double *gap_better = nullptr, *gap_worse = nullptr;               // [n]
+  int32_t *id_better = nullptr, *id_worse = nullptr;                // [n]
+  double* thr = nullptr;               // [cap][2] thr_lo, thr_hi
+  unsigned long long* pkey = nullptr;  // [cap][nblk][2] the blocks' nearest better / worse keys
+  int32_t* pcol = nullptr;             // [cap][nblk][2] their columns (-1: none)
+  int32_t* pcnt = nullptr;             // [cap][nblk][3] the blocks' counts: lo, hi, ties
+  int cap = 0, nblk = 0;
+  // the same workspace for the rows from r0 on
+  MarginDev at(size_t r0) const {
+    MarginDev m = *this;
+    m.rank_lo += r0, m.rank_hi += r0, m.ties += r0, m.gap_better += r0, m.gap_worse += r0, m.id_better += r0,
+        m.id_worse += r0;
+    return m;
+  }
+};
 void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* d_t64, const double* d_kcol64,
                      const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt, float* d_target,
                      int64_t* d_rank, int act = 0, int topk = 0, int32_t* d_top_ids = nullptr,
-                     float* d_top_scores = nullptr, DevBuf* bits_buf = nullptr);
+                     float* d_top_scores = nullptr, DevBuf* bits_buf = nullptr, const MarginDev* mg = nullptr);
 void launch_rank_count(kp_ctx* c, int n_slots, const float* d_scores, int ld, int n_cols,
                        const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt,
                        int minimizer, float* d_target, int64_t* d_rank,

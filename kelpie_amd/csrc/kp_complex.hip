@@ -1447,7 +1447,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostRe
   // (launch_rank_f64: at the reference init the target's neighbours are ~1e-5 relative away)
   CX_DISPATCH(c->dp / 16, launch_rankq64<DB, Prod>(c, d.X, d.pred, ns, d.r64.q, d.r64.t, d.r64.kcol));
   launch_rank_f64(c, ns, d.r64.q, d.r64.t, d.r64.kcol, d.rk.po, d.rk.filt_off, d.rk.filt, d.rk.target, d.rk.rank,
-                  RANK64_DOT, rq.k, d.rk.top_ids, d.rk.top_scores);
+                  RANK64_DOT, rq.k, d.rk.top_ids, d.rk.top_scores, nullptr, d.rk.margins());
   // the probes on the slots' rows, then the marks on the mark workspace
   const auto probe_queries = [c](const RankRows& rr, int r0, int m) {
     CX_DISPATCH(c->dp / 16, launch_probeq64<DB, Prod>(c, rr, r0, m));

@@ -1316,7 +1316,7 @@ RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const PostReq&
                        r64.t, r64.kcol);
     KP_HIP(hipGetLastError());
     launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_SIGMOID,
-                    rq.k, rk.top_ids, rk.top_scores);
+                    rq.k, rk.top_ids, rk.top_scores, nullptr, rk.margins());
     // the probes on the slots' rows, then the marks on the mark workspace: a chunk's rows
     // through the encoder (eval mode) on the set's rows, then the probe form and the count
     const auto probe_queries = [c, K, DP](const RankRows& rr, int r0, int m) {

@@ -5,7 +5,8 @@
 // every result and the hot-launch timing.  The model-specific step planning is pure host code
 // in headers of its own (kp_cx_plan.hpp: ComplEx / DistMult; kp_cv_plan.hpp: ConvE; TransE's
 // schedule is kp_sched.cpp), as are the request's checks and its expansion into rank rows
-// (kp_batch_check.hpp, kp_probe_check.hpp, kp_trace_check.hpp, kp_marks_check.hpp); the
+// (kp_batch_check.hpp, kp_probe_check.hpp, kp_trace_check.hpp, kp_marks_check.hpp,
+// kp_margins_check.hpp); the
 // launches, and where in the call each upload happens, stay in kp_complex.hip / kp_transe.hip
 // / kp_conve.hip.
 #pragma once
@@ -18,6 +19,7 @@
 #include "kp_batch_check.hpp"
 #include "kp_common.hpp"
 #include "kp_keyed.hpp"
+#include "kp_margins_check.hpp"
 #include "kp_marks_check.hpp"
 #include "kp_probe_check.hpp"
 #include "kp_trace_check.hpp"
@@ -32,7 +34,8 @@ inline double host_ms() {
 // The checks of a call, first thing in every *_posttrain_rank, so that a malformed call
 // leaves no device work in flight; the first rule broken is the one reported, as KP_EINVAL
 // under the model's name: the batch (kp_batch_check.hpp), the top-k request, the probes
-// (kp_probe_check.hpp), the trace (kp_trace_check.hpp), the marks (kp_marks_check.hpp).
+// (kp_probe_check.hpp), the trace (kp_trace_check.hpp), the marks (kp_marks_check.hpp), the
+// margins (kp_margins_check.hpp).
 // `rank64`: the call ranks on launch_rank_f64's fp64 operands; the lists, the probes and the
 // marks need them (KP_ENOTSUP under the fp32 diagnostic ranks, KP_TE_RANK / KP_CV_RANK = f32,
 // once well formed), the trace does not depend on the rank.
@@ -82,6 +85,11 @@ inline void require_request(const kp_ctx* c, const kp_hp* hp, const kp_batch* bt
     if (const char* why = kp_check_marks(hp, rq.marks)) throw KpError{KP_EINVAL, who + ": marks: " + why};
     if (!rank64) throw KpError{KP_ENOTSUP, who + ": marks need the fp64 rank (the fp32 rank switch is set)"};
   }
+  if (rq.margins) {
+    int code = KP_EINVAL;
+    if (const char* why = kp_check_margins(rq.margins, rq.n_probes(), rq.n_marks(), rank64, &code))
+      throw KpError{code, who + ": margins: " + why};
+  }
 }
 
 // Adam's per-step scalars at step t (0-based) of a call: lr / (1 - beta1^(t+1)) and
@@ -121,7 +129,52 @@ struct RankDev {
   int64_t* rank;  // [ns]
   int32_t* top_ids = nullptr;   // [ns][k] (kp_posttrain_rank_topk, k > 0)
   float* top_scores = nullptr;  // [ns][k]
+  MarginDev mg;                 // the slots' margins (kp_posttrain_rank_margins; cap 0: none)
+  const MarginDev* margins() const { return mg.cap > 0 ? &mg : nullptr; }
 };
+
+// The margins of n rank rows ranked `cap` rows at a launch: every result array [n] in `out`,
+// the thresholds and the per-workgroup partials of one launch in `part`.  Sized where the rank
+// inputs and the rank rows are sized, never inside the step loop.  Not wanted (or n == 0): an
+// empty MarginDev (cap 0).
+inline MarginDev margin_buffers(kp_ctx* c, DevBuf& out, DevBuf& part, const kp_margins* m, const kp_margin_out* want,
+                                int n, int cap) {
+  MarginDev d;
+  if (!m || !kp_margin_wanted(*want) || n <= 0) return d;
+  d.tol = m->tol;
+  d.cap = cap;
+  d.nblk = (c->n_ent + 255) / 256;
+  char* o = reinterpret_cast<char*>(out.ensure((size_t)n * 48));
+  d.rank_lo = reinterpret_cast<int64_t*>(o);
+  d.rank_hi = d.rank_lo + n;
+  d.ties = d.rank_hi + n;
+  d.gap_better = reinterpret_cast<double*>(d.ties + n);
+  d.gap_worse = d.gap_better + n;
+  d.id_better = reinterpret_cast<int32_t*>(d.gap_worse + n);
+  d.id_worse = d.id_better + n;
+  const size_t cells = (size_t)cap * d.nblk;
+  char* w = reinterpret_cast<char*>(part.ensure((size_t)cap * 16 + cells * 36));
+  d.thr = reinterpret_cast<double*>(w);
+  d.pkey = reinterpret_cast<unsigned long long*>(d.thr + 2 * (size_t)cap);
+  d.pcol = reinterpret_cast<int32_t*>(d.pkey + 2 * cells);
+  d.pcnt = d.pcol + 2 * cells;
+  return d;
+}
+
+// enqueue the download of the margins a caller asked for
+inline void download_margins(kp_ctx* c, const MarginDev& d, const kp_margin_out& o, size_t n) {
+  if (d.cap == 0) return;
+  const auto to_host = [c](void* dst, const void* src, size_t bytes) {
+    if (dst) KP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  };
+  to_host(o.rank_lo, d.rank_lo, 8 * n);
+  to_host(o.rank_hi, d.rank_hi, 8 * n);
+  to_host(o.ties, d.ties, 8 * n);
+  to_host(o.gap_better, d.gap_better, 8 * n);
+  to_host(o.gap_worse, d.gap_worse, 8 * n);
+  to_host(o.id_better, d.id_better, 4 * n);
+  to_host(o.id_worse, d.id_worse, 4 * n);
+}
 
 // upload the ranked objects and the filter CSR, size the result buffers.  The caller
 // chooses where in its call this happens: an upload's position decides what it overlaps.
@@ -139,6 +192,7 @@ inline RankDev upload_rank_inputs(kp_ctx* c, const kp_batch* bt, const PostReq& 
     r.top_ids = ensure_n<int32_t>(c->rank.top_ids, (size_t)ns * rq.k);
     r.top_scores = ensure_n<float>(c->rank.top_scores, (size_t)ns * rq.k);
   }
+  if (rq.margins) r.mg = margin_buffers(c, c->rank.mg_out, c->rank.mg_part, rq.margins, &rq.margins->slots, ns, ns);
   return r;
 }
 
@@ -178,6 +232,7 @@ struct RankRows {
   DevBuf* bits = nullptr;                              // the chunk's filter bitmaps (launch_rank_f64 sizes them)
   int2* enc_src = nullptr;                             // ConvE: [n] the rows' encoder sources (-row - 1, p)
   float* enc_q = nullptr;                              // ConvE: [chunk][dp] the chunk's encoder output
+  MarginDev mg;                                        // the rows' margins (cap 0: none), one chunk's workspace
 };
 
 // upload a set of rank rows (kp_probe_check.hpp's / kp_marks_check.hpp's expansion) and size
@@ -190,7 +245,8 @@ struct RankRows {
 inline RankRows upload_rank_rows(kp_ctx* c, RankRowsWs& ws, const char* chunk_env, const float* X,
                                  const std::vector<int32_t>& trip, const std::vector<int32_t>& po,
                                  const int32_t* filt_off, const int32_t* filt, size_t n_filt,
-                                 size_t enc_row_bytes = 0) {
+                                 size_t enc_row_bytes = 0, const kp_margins* mg = nullptr,
+                                 const kp_margin_out* mg_want = nullptr) {
   RankRows d;
   const int n = (int)po.size();
   if (n == 0) return d;
@@ -218,6 +274,7 @@ inline RankRows upload_rank_rows(kp_ctx* c, RankRowsWs& ws, const char* chunk_en
     d.enc_src = upload(c, ws.enc_src, src.data(), src.size());
     d.enc_q = ensure_n<float>(ws.enc_q, (size_t)d.chunk * c->dp);
   }
+  if (mg) d.mg = margin_buffers(c, ws.mg_out, ws.mg_part, mg, mg_want, n, std::min(n, d.chunk));
   return d;
 }
 
@@ -228,7 +285,8 @@ inline RankRows upload_probes(kp_ctx* c, const kp_batch* bt, const PostReq& rq, 
   std::vector<int32_t> trip, po;
   kp_probe_rows(bt->n_slots, rq.probes, trip, po);
   return upload_rank_rows(c, c->rank.probes, "KP_PROBE_CHUNK", dX, trip, po, rq.probes->filt_off, rq.probes->filt,
-                          (size_t)rq.probes->filt_off[rq.probes->n], enc_row_bytes);
+                          (size_t)rq.probes->filt_off[rq.probes->n], enc_row_bytes, rq.margins,
+                          rq.margins ? &rq.margins->probes : nullptr);
 }
 
 // rank a set of rows, chunk by chunk: `queries(d, r0, m)` enqueues the model's probe form of
@@ -239,8 +297,9 @@ inline void rank_rows(kp_ctx* c, const RankRows& d, int act, F&& queries) {
   for (int r0 = 0; r0 < d.n; r0 += d.chunk) {
     const int m = std::min(d.chunk, d.n - r0);
     queries(d, r0, m);
+    const MarginDev mg = d.mg.cap > 0 ? d.mg.at((size_t)r0) : MarginDev{};
     launch_rank_f64(c, m, d.q, d.t, d.kcol, d.po + r0, d.filt_off + r0, d.filt, d.target + r0, d.rank + r0, act, 0,
-                    nullptr, nullptr, d.bits);
+                    nullptr, nullptr, d.bits, d.mg.cap > 0 ? &mg : nullptr);
   }
 }
 
@@ -271,7 +330,7 @@ inline MarksDev upload_marks(kp_ctx* c, DevBuf& ws, const kp_hp* hp, const kp_ba
     KP_HIP(hipMemcpy2DAsync(d.X + (size_t)j * c->dp, sizeof(float) * (size_t)nm * c->dp, dX, sizeof(float) * c->dp,
                             sizeof(float) * c->dp, ns, hipMemcpyDeviceToDevice, c->stream));
   d.rows = upload_rank_rows(c, c->rank.marks, "KP_MARKS_CHUNK", d.X, trip, po, fo.data(), filt.data(), filt.size(),
-                            enc_row_bytes);
+                            enc_row_bytes, rq.margins, rq.margins ? &rq.margins->marks : nullptr);
   return d;
 }
 
@@ -337,6 +396,11 @@ inline double download_results(kp_ctx* c, const kp_batch* bt, const float* dX, c
   if (pd.n > 0) {
     to_host(rq.probes->out_score, pd.target, sizeof(float) * pd.n);
     to_host(rq.probes->out_rank, pd.rank, sizeof(int64_t) * pd.n);
+  }
+  if (rq.margins) {
+    download_margins(c, r.mg, rq.margins->slots, (size_t)ns);
+    download_margins(c, pd.mg, rq.margins->probes, (size_t)pd.n);
+    download_margins(c, md.rows.mg, rq.margins->marks, (size_t)md.rows.n);
   }
   const double t_wait = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipStreamSynchronize(c->stream));

@@ -1,6 +1,11 @@
 // kp_rank.hip -- all-entity scoring (fp32 MFMA) and the filtered rank of
 // PostTrainingEngine.get_triple_results (post_training_engine.py:101-125).
 #include "kp_common.hpp"
+#include "kp_margins_check.hpp"
+
+static_assert(KP_MG_DOT == RANK64_DOT && KP_MG_SIGMOID == RANK64_SIGMOID && KP_MG_DIST == RANK64_DIST &&
+                  KP_MG_DIST1 == RANK64_DIST1,
+              "kp_margins_check.hpp restates launch_rank_f64's score kinds");
 
 // ----------------------------------------------------------------------------
 // score GEMM:  out[q][e] = act( Q[q] . E[e] )  for e < n_ent
@@ -477,12 +482,235 @@ __global__ __launch_bounds__(256) void kp_rank_topk_merge(int n_ent, int nwords,
   }
 }
 
+// ----------------------------------------------------------------------------
+// rank margins (kp_posttrain_rank_margins; include/kelpie_hip.h, "Rank margins"): per rank row
+// the band [rank_lo, rank_hi] of the rank under a tolerance on the compared values, the exact
+// ties and the nearest better / worse column.  Three launches after the row's own count, none
+// with an atomic: the thresholds (one thread per row, kp_margins_check.hpp's rule), the margin
+// form of the count (the count's grid and its fp64 chain per column, so c_e is the value the
+// rank compared; every workgroup leaves its counts and its nearest (key, column) pairs of each
+// row in the workspace) and the merge (one wave per row: the workgroups' partials in a fixed
+// order, the kelpie column, `own`).  A nearest pair's key orders like topk_key on the worse
+// side and reversed on the better side, so both sides take the minimum by topk_before: the
+// closest value, the lower column among equal ones.
+// ----------------------------------------------------------------------------
+constexpr uint32_t MG_NONE = 0xffffffffu;
+
+__global__ void kp_rank_margin_thr(int n, int act, const double* __restrict__ t64, double tol,
+                                   double* __restrict__ thr) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  double lo, hi;
+  kp_margin_thresholds(act, t64[s], tol, &lo, &hi);
+  thr[2 * s] = lo;
+  thr[2 * s + 1] = hi;
+}
+
+// one unmasked column other than the target, of value c at column e, against a row's target ct
+// and thresholds: its counts (lo | hi << 8 | tie << 16) and, when it is strictly better /
+// worse than the target, its candidate pair for that side (written over what the caller
+// passed: a caller that holds a candidate already merges by topk_before)
+__device__ __forceinline__ int margin_column(int act, double c, uint32_t e, double ct, double thr_lo, double thr_hi,
+                                             bool t_sat, unsigned long long& bk, uint32_t& bc,
+                                             unsigned long long& wk, uint32_t& wc) {
+  const bool mini = act == RANK64_DIST || act == RANK64_DIST1;
+  bool lo = mini ? c <= thr_lo : c >= thr_lo;
+  bool hi = mini ? c <= thr_hi : c >= thr_hi;
+  if (act == RANK64_SIGMOID && t_sat && sigmoid_f32_saturated(c)) lo = hi = true;
+  const unsigned long long k = topk_key(c, mini);
+  if (mini ? c < ct : c > ct) bk = ~k, bc = e;
+  if (mini ? c > ct : c < ct) wk = k, wc = e;
+  return (lo ? 1 : 0) | (hi ? 1 << 8 : 0) | (c == ct ? 1 << 16 : 0);
+}
+
+// the minimum (key, column) pair over the wave's lanes, in every lane
+__device__ __forceinline__ void margin_wave_min(unsigned long long& key, uint32_t& col) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long pk = __shfl_xor(key, o, 64);
+    const uint32_t pc = __shfl_xor(col, o, 64);
+    if (topk_before(pk, pc, key, col)) key = pk, col = pc;
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void kp_rank_f64_margin(int n_slots, int n_ent, int dp, const double* __restrict__ Q,
+                                                          const double* __restrict__ t64,
+                                                          const int32_t* __restrict__ pred_o,
+                                                          const float* __restrict__ ET, int ldt, int nwords,
+                                                          const uint32_t* __restrict__ bits,
+                                                          const double* __restrict__ thr,
+                                                          unsigned long long* __restrict__ pkey,
+                                                          int32_t* __restrict__ pcol, int32_t* __restrict__ pcnt) {
+  __shared__ int cnt_s[4][RQ];
+  __shared__ unsigned long long key_s[4][RQ][2];
+  __shared__ uint32_t col_s[4][RQ][2];
+  const int s0 = blockIdx.y * RQ;
+  const int e = blockIdx.x * 256 + threadIdx.x;  // < ldt: ET is zero-padded
+  const int ns = min(RQ, n_slots - s0);
+  double acc[RQ];
+#pragma unroll
+  for (int j = 0; j < RQ; ++j) acc[j] = 0.0;
+  // kp_rank_f64_count's chain, operation for operation: the same c_e
+  const double* q = Q + (size_t)s0 * dp;
+  for (int d = 0; d < dp; ++d) {
+    const double v = (double)ET[(size_t)d * ldt + e];
+#pragma unroll
+    for (int j = 0; j < RQ; ++j)
+      if (j < ns) {
+        if constexpr (MODE == RANK64_DIST) {
+          const double df = q[(size_t)j * dp + d] - v;
+          acc[j] = __fma_rn(df, df, acc[j]);
+        } else if constexpr (MODE == RANK64_DIST1) {
+          acc[j] += fabs(q[(size_t)j * dp + d] - v);
+        } else {
+          acc[j] = __fma_rn(q[(size_t)j * dp + d], v, acc[j]);
+        }
+      }
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < RQ; ++j) {
+    if (j < ns) {  // block-uniform
+      const int s = s0 + j;
+      int cnt = 0;
+      unsigned long long bk = ~0ull, wk = ~0ull;
+      uint32_t bc = MG_NONE, wc = MG_NONE;
+      if (e < n_ent && e != pred_o[s]) {
+        const bool filtered = (bits[(size_t)s * nwords + (e >> 5)] >> (e & 31)) & 1u;
+        if (!filtered) {
+          const double ct = t64[s];
+          const bool t_sat = MODE == RANK64_SIGMOID && sigmoid_f32_saturated(ct);
+          cnt = margin_column(MODE, acc[j], (uint32_t)e, ct, thr[2 * s], thr[2 * s + 1], t_sat, bk, bc, wk, wc);
+        }
+      }
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);  // three fields of at most 64 each
+      margin_wave_min(bk, bc);
+      margin_wave_min(wk, wc);
+      if (lane == 0) {
+        cnt_s[w][j] = cnt;
+        key_s[w][j][0] = bk, col_s[w][j][0] = bc;
+        key_s[w][j][1] = wk, col_s[w][j][1] = wc;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * ns) {  // thread (j, side): the four waves' partials in wave order
+    const int j = threadIdx.x >> 1, side = threadIdx.x & 1;
+    const size_t at = (size_t)(s0 + j) * gridDim.x + blockIdx.x;
+    unsigned long long k = key_s[0][j][side];
+    uint32_t c = col_s[0][j][side];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+      if (topk_before(key_s[i][j][side], col_s[i][j][side], k, c)) k = key_s[i][j][side], c = col_s[i][j][side];
+    pkey[2 * at + side] = k;
+    pcol[2 * at + side] = (int32_t)c;
+    if (side == 0) {
+      int lo = 0, hi = 0, ties = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        lo += cnt_s[i][j] & 0xff, hi += (cnt_s[i][j] >> 8) & 0xff, ties += cnt_s[i][j] >> 16;
+      }
+      pcnt[3 * at] = lo, pcnt[3 * at + 1] = hi, pcnt[3 * at + 2] = ties;
+    }
+  }
+}
+
+// one wave per row: the row's nblk partials, the kelpie column and `own` into its margins
+__global__ __launch_bounds__(64) void kp_rank_margin_merge(int n_ent, int nwords, int nblk, int act,
+                                                           const uint32_t* __restrict__ bits,
+                                                           const int32_t* __restrict__ pred_o,
+                                                           const double* __restrict__ t64,
+                                                           const double* __restrict__ kcol64,
+                                                           const double* __restrict__ thr,
+                                                           const unsigned long long* __restrict__ pkey,
+                                                           const int32_t* __restrict__ pcol,
+                                                           const int32_t* __restrict__ pcnt, MarginDev out) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const bool mini = act == RANK64_DIST || act == RANK64_DIST1;
+  long long lo = 0, hi = 0, ties = 0;
+  unsigned long long bk = ~0ull, wk = ~0ull;
+  uint32_t bc = MG_NONE, wc = MG_NONE;
+  for (int b = lane; b < nblk; b += 64) {
+    const size_t at = (size_t)s * nblk + b;
+    lo += pcnt[3 * at], hi += pcnt[3 * at + 1], ties += pcnt[3 * at + 2];
+    if (topk_before(pkey[2 * at], (uint32_t)pcol[2 * at], bk, bc)) bk = pkey[2 * at], bc = (uint32_t)pcol[2 * at];
+    if (topk_before(pkey[2 * at + 1], (uint32_t)pcol[2 * at + 1], wk, wc))
+      wk = pkey[2 * at + 1], wc = (uint32_t)pcol[2 * at + 1];
+  }
+  const double ct = t64[s];
+  const int o = pred_o[s];
+  if (lane == 0) {
+    const bool kfilt = (bits[(size_t)s * nwords + (n_ent >> 5)] >> (n_ent & 31)) & 1u;
+    if (o != n_ent && !kfilt) {  // the kelpie column, unless it is the target or masked
+      const bool t_sat = act == RANK64_SIGMOID && sigmoid_f32_saturated(ct);
+      unsigned long long kbk = ~0ull, kwk = ~0ull;
+      uint32_t kbc = MG_NONE, kwc = MG_NONE;
+      const int cnt =
+          margin_column(act, kcol64[s], (uint32_t)n_ent, ct, thr[2 * s], thr[2 * s + 1], t_sat, kbk, kbc, kwk, kwc);
+      lo += cnt & 0xff, hi += (cnt >> 8) & 0xff, ties += cnt >> 16;
+      if (topk_before(kbk, kbc, bk, bc)) bk = kbk, bc = kbc;  // one more candidate of this lane's
+      if (topk_before(kwk, kwc, wk, wc)) wk = kwk, wc = kwc;
+    }
+    // own: what the rank counts for the target column itself (a minimizer's target is restored
+    // before the count, a maximizer's filtered target is left out)
+    const bool ofilt = (bits[(size_t)s * nwords + (o >> 5)] >> (o & 31)) & 1u;
+    const int own = (mini || !ofilt) ? 1 : 0;
+    lo += own, hi += own;
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    lo += __shfl_xor(lo, d, 64), hi += __shfl_xor(hi, d, 64), ties += __shfl_xor(ties, d, 64);
+  }
+  margin_wave_min(bk, bc);
+  margin_wave_min(wk, wc);
+  if (lane != 0) return;
+  const double vt = kp_margin_units(act, ct);
+  if (out.rank_lo) out.rank_lo[s] = lo;
+  if (out.rank_hi) out.rank_hi[s] = hi;
+  if (out.ties) out.ties[s] = ties;
+  if (out.id_better) out.id_better[s] = (int32_t)bc;
+  if (out.id_worse) out.id_worse[s] = (int32_t)wc;
+  if (out.gap_better)
+    out.gap_better[s] = bc == MG_NONE ? (double)INFINITY : fabs(kp_margin_units(act, topk_value(~bk, mini)) - vt);
+  if (out.gap_worse)
+    out.gap_worse[s] = wc == MG_NONE ? (double)INFINITY : fabs(kp_margin_units(act, topk_value(wk, mini)) - vt);
+}
+
+// the margins of n rows whose filter bitmaps, targets and kelpie column scores the rows' own
+// rank has just read
+static void launch_margins(kp_ctx* c, int n, const double* d_q64, const double* d_t64, const double* d_kcol64,
+                           const int32_t* d_pred_o, const uint32_t* bits, int nwords, int ldt, int act,
+                           const MarginDev& mg) {
+  const int nblk = ldt / 256;
+  KP_REQUIRE(n <= mg.cap && nblk == mg.nblk, "margins: the workspace does not hold this launch");
+  hipLaunchKernelGGL(kp_rank_margin_thr, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, act, d_t64, mg.tol, mg.thr);
+  KP_HIP(hipGetLastError());
+  const dim3 grid(nblk, (n + RQ - 1) / RQ);
+#define KP_MARGIN_LAUNCH(MODE)                                                                                  \
+  hipLaunchKernelGGL(kp_rank_f64_margin<MODE>, grid, dim3(256), 0, c->stream, n, c->n_ent, c->dp, d_q64, d_t64, \
+                     d_pred_o, c->eT.as<float>(), ldt, nwords, bits, mg.thr, mg.pkey, mg.pcol, mg.pcnt)
+  if (act == RANK64_DIST)
+    KP_MARGIN_LAUNCH(RANK64_DIST);
+  else if (act == RANK64_DIST1)
+    KP_MARGIN_LAUNCH(RANK64_DIST1);
+  else if (act == RANK64_SIGMOID)
+    KP_MARGIN_LAUNCH(RANK64_SIGMOID);
+  else
+    KP_MARGIN_LAUNCH(RANK64_DOT);
+#undef KP_MARGIN_LAUNCH
+  KP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kp_rank_margin_merge, dim3(n), dim3(64), 0, c->stream, c->n_ent, nwords, nblk, act, bits, d_pred_o,
+                     d_t64, d_kcol64, mg.thr, mg.pkey, mg.pcol, mg.pcnt, mg);
+  KP_HIP(hipGetLastError());
+}
+
 // bytes of candidate workspace a launch may hold: the slots run in chunks of whole slot rows
 constexpr size_t TOPK_WS_BYTES = (size_t)64 << 20;
 
 void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* d_t64, const double* d_kcol64,
                      const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt, float* d_target,
-                     int64_t* d_rank, int act, int topk, int32_t* d_top_ids, float* d_top_scores, DevBuf* bits_buf) {
+                     int64_t* d_rank, int act, int topk, int32_t* d_top_ids, float* d_top_scores, DevBuf* bits_buf,
+                     const MarginDev* mg) {
   if (n_slots <= 0) return;
   const int ldt = (c->n_ent + 255) / 256 * 256;
   if (!c->eT_ready) {
@@ -503,6 +731,7 @@ void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* 
   hipLaunchKernelGGL(kp_rank_f64_kelpie, dim3((n_slots + 63) / 64), dim3(64), 0, c->stream, n_slots, c->n_ent, nwords,
                      bits, d_pred_o, d_t64, d_kcol64, act, d_target, rank);
   KP_HIP(hipGetLastError());
+  if (mg) launch_margins(c, n_slots, d_q64, d_t64, d_kcol64, d_pred_o, bits, nwords, ldt, act, *mg);
   if (topk > 0) {
     // every wave of the scoring grid leaves a list of k candidates per slot (12 bytes each):
     // the slots run in chunks of whole slot rows that keep the lists within TOPK_WS_BYTES

@@ -773,7 +773,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
                        ns, r64.q, r64.t, r64.kcol, l1 ? 1 : 0);
     KP_HIP(hipGetLastError());
     launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank,
-                    l1 ? RANK64_DIST1 : RANK64_DIST, rq.k, rk.top_ids, rk.top_scores);
+                    l1 ? RANK64_DIST1 : RANK64_DIST, rq.k, rk.top_ids, rk.top_scores, nullptr, rk.margins());
     // the probes on the slots' rows, then the marks on the mark workspace: the probe form
     // reads row trip[3 r] of the set's rows instead of row r
     const auto probe_queries = [c, DP, l1](const RankRows& rr, int r0, int m) {

@@ -397,6 +397,39 @@ class PostTrainingEngine(RelevanceEngine):
     def marks(self, epochs):
         self._marks = None if epochs is None else _lib.check_marks(epochs, int(self._kp_hp.epochs))
 
+    _margin_tol = None  # the tolerance of the rank margins every post-training also reports (None: off)
+
+    @property
+    def margin_tol(self):
+        """The tolerance of the rank margins every post-training also reports (None: none, the
+        default; else a real number in [0, 1]): how far the slot's rank is from changing
+        (include/kelpie_hip.h, "Rank margins").  With ``delta = margin_tol * max(1, |score|)``
+        every slot's result gains ``"margins"``: ``rank_lo`` / ``rank_hi`` (the rank were every
+        other column's compared value held against the target's moved by ``delta`` against /
+        for the target: ``rank_lo <= rank <= rank_hi``, all equal at 0), ``ties`` (other
+        columns equal to the target exactly), ``id_better`` / ``gap_better`` and ``id_worse`` /
+        ``gap_worse`` (the nearest strictly better / worse unmasked column and its distance in
+        score units; -1 / inf without one; ``num_entities``: the kelpie entity), and ``tol``.
+        The relevances, the draws and the batches are those of ``margin_tol`` = None.  Not
+        offered with ``precision="fp64"``, a slot sharding, ``compute_relevance_pipeline`` or
+        ``submit_batch`` (NotImplementedError before any draw)."""
+        return self._margin_tol
+
+    @margin_tol.setter
+    def margin_tol(self, tol):
+        self._margin_tol = None if tol is None else _lib.check_margin_tol(tol)
+
+    def _refuse_margins(self, what=None):
+        """The margins' refusals, before any work."""
+        if self._margin_tol is None:
+            return
+        if what is not None:
+            raise NotImplementedError(f"margins on {what}: batches with margins run one at a time")
+        if self._fp64():
+            raise NotImplementedError("margins with precision='fp64': kp_posttrain_rank_f64 does not offer them")
+        if self._sharded():
+            raise NotImplementedError("margins with a slot sharding: their results are not gathered across ranks")
+
     @property
     def top_k(self):
         """How many of each post-training's best tails the device also reports (0: none, the
@@ -733,6 +766,7 @@ class PostTrainingEngine(RelevanceEngine):
     def _schedule_all(self, items, checkpoints):
         """_schedule_multi, with every queued TransE call's draws made before it returns or raises."""
         self._refuse_keyed()  # before any work
+        self._refuse_margins()  # before any draw
         self._refuse_fp64()  # before any draw
         if self._top_k and self._sharded():
             # before any draw: the gather's records hold a score and a rank per slot
@@ -952,6 +986,9 @@ class PostTrainingEngine(RelevanceEngine):
         marks = self._marks
         if marks is not None:
             kw["marks"] = marks
+        tol = self._margin_tol
+        if tol is not None:
+            kw["margins"] = tol
         if slots[0].keys is not None:  # keyed draws: the context generates x0 and the words from the keys
             scale, bound = self.model.keyed_params()
             ctx.arm_keyed([s.keys[0] for s in slots], [s.keys[1] for s in slots], scale, bound)
@@ -969,6 +1006,10 @@ class PostTrainingEngine(RelevanceEngine):
                 for i, s in enumerate(slots):
                     s.result["marks"] = [{"epoch": int(e), "score": float(m_score[i][j]), "rank": int(m_rank[i][j])}
                                          for j, e in enumerate(marks)]
+            if tol is not None:
+                mg = out.margins[0]
+                for i, s in enumerate(slots):
+                    s.result["margins"] = {"tol": tol, **{name: mg[name][i].item() for name, _ in _lib.MARGIN_FIELDS}}
             if traced:
                 for s, loss in zip(slots, out.loss):
                     s.result["loss"] = [float(v) for v in loss]
@@ -1161,6 +1202,62 @@ class PostTrainingEngine(RelevanceEngine):
         ep = [int(e) for e in ep]
         return [self._mk_rule(rel, det, ep) for rel, det in zip(rels, self.last_results)]
 
+    @staticmethod
+    def _mg_side(res, tol):
+        """One post-training of a margins report: its target score and rank and its margins,
+        None each when the result was cached without margins of this tolerance."""
+        mg = res.get("margins")
+        if mg is not None and mg["tol"] != tol:
+            mg = None
+        side = {"score": res["target_score"], "rank": res["target_rank"]}
+        for name, _ in _lib.MARGIN_FIELDS:
+            side[name] = None if mg is None else mg[name]
+        return side
+
+    def _band_of(self, base, pt):
+        """(low, high) of the engine's relevance formula in float64 over the rank bands of one
+        (base, post-trained) pair of _mg_side results, the score term as computed; None when a
+        side has no margins."""
+        raise NotImplementedError
+
+    def _score_term(self, base, pt, improvement):
+        """The sigmoid term of the relevance formulas, in float64: of the score's improvement
+        (the sufficient engine) or worsening (the necessary engine) from base to post."""
+        d = float(pt["score"]) - float(base["score"])
+        if bool(self.model.is_minimizer()) == bool(improvement):  # smaller is better: an improvement is base - post
+            d = -d
+        return float(_sigmoid(d))
+
+    def _mg_rule(self, relevance, detail, tol):
+        raise NotImplementedError
+
+    def compute_margins(self, pred, rules, tol=1e-4):
+        """``compute_relevance_batch(pred, rules)`` -- the same schedule, draws, batches and
+        relevances, the generators left where it leaves them -- that also reports how far every
+        rank is from changing (:attr:`margin_tol`): per rule ``{"relevance", "relevance_lo",
+        "relevance_hi", "base", "post"}`` (the sufficient engine: ``{"relevance",
+        "relevance_lo", "relevance_hi", "conversions": [{"entity", "base", "post"}, ...]}``),
+        ``base`` / ``post`` = ``{"score", "rank", "rank_lo", "rank_hi", "ties", "gap_better",
+        "gap_worse", "id_better", "id_worse"}``.  ``relevance`` is ``compute_relevance_batch``'s
+        bit for bit.  ``relevance_lo`` / ``relevance_hi`` are the relevance formula in float64
+        over the rank bands: the necessary engine's with ``post.rank_lo - base.rank_hi`` and
+        ``post.rank_hi - base.rank_lo``; the sufficient engine's per conversion entity the
+        minimum and maximum over the corners (``base.rank``, ``post.rank``) in {lo, hi} x {lo,
+        hi} (the formula is monotone in each), then the mean of the lows and the mean of the
+        highs.  The band moves the ranks only: the score term stays as computed (a score moved
+        by at most delta moves its sigmoid, hence the relevance, by less than delta / 2).  No
+        post-training runs for the sake of a margin: a base result cached without margins of
+        this ``tol`` reports None for them and for the band.  TypeError / ValueError for a bad
+        ``tol`` and NotImplementedError for a combination not offered, before any draw."""
+        tol = _lib.check_margin_tol(tol)
+        old = self._margin_tol
+        self._margin_tol = tol
+        try:
+            rels = self.compute_relevance_batch(pred, rules)
+        finally:
+            self._margin_tol = old
+        return [self._mg_rule(rel, det, tol) for rel, det in zip(rels, self.last_results)]
+
     def _schedule_multi(self, items, checkpoints):
         raise NotImplementedError
 
@@ -1200,6 +1297,7 @@ class PostTrainingEngine(RelevanceEngine):
 
         from . import rng as _rng_mod
         self._refuse_keyed("submit_batch")
+        self._refuse_margins("submit_batch")
         ctxs = self.model.contexts(2)
         self._submit_n = getattr(self, "_submit_n", -1) + 1
         ctx = ctxs[self._submit_n % len(ctxs)]
@@ -1315,6 +1413,7 @@ class PostTrainingEngine(RelevanceEngine):
         import threading
 
         self._refuse_keyed("compute_relevance_pipeline")
+        self._refuse_margins("compute_relevance_pipeline")
         if self._fp64():  # before any draw
             raise NotImplementedError("precision='fp64' on compute_relevance_pipeline: the fp64 path runs one "
                                       "batch at a time")
@@ -1637,6 +1736,18 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
         b, p = self._mk_side(base, epochs), self._mk_side(pt, epochs)
         return {"relevance": relevance, "epochs": list(epochs), "curve": self._curve(b, p), "base": b, "post": p}
 
+    def _band_of(self, base, pt):
+        if base["rank_lo"] is None or pt["rank_lo"] is None:
+            return None
+        sig = self._score_term(base, pt, improvement=False)
+        return (float(pt["rank_lo"] - base["rank_hi"]) + sig, float(pt["rank_hi"] - base["rank_lo"]) + sig)
+
+    def _mg_rule(self, relevance, detail, tol):
+        pt, base = detail
+        b, p = self._mg_side(base, tol), self._mg_side(pt, tol)
+        band = self._band_of(b, p) or (None, None)
+        return {"relevance": relevance, "relevance_lo": band[0], "relevance_hi": band[1], "base": b, "post": p}
+
 
 class SufficientPostTrainingEngine(PostTrainingEngine):
     """post_training_engine.py:160-207."""
@@ -1678,6 +1789,24 @@ class SufficientPostTrainingEngine(PostTrainingEngine):
         if curves and all(c is not None for c in curves):  # the mean over the conversions, as the relevance
             curve = [sum(c[j] for c in curves) / len(curves) for j in range(len(epochs))]
         return {"relevance": relevance, "epochs": list(epochs), "curve": curve, "conversions": conv}
+
+    def _band_of(self, base, pt):
+        if base["rank_lo"] is None or pt["rank_lo"] is None:
+            return None
+        sig = np.float64(self._score_term(base, pt, improvement=True))
+        with np.errstate(all="ignore"):  # a base rank of 0 divides by zero, as the relevance itself does
+            corners = [float((np.float64(b - p) + sig) / np.float64(b))
+                       for b in (base["rank_lo"], base["rank_hi"]) for p in (pt["rank_lo"], pt["rank_hi"])]
+        return min(corners), max(corners)
+
+    def _mg_rule(self, relevance, detail, tol):
+        conv = [{"entity": int(e), "base": self._mg_side(base, tol), "post": self._mg_side(pt, tol)}
+                for e, (pt, base) in zip(self.entities_to_convert, detail)]
+        bands = [self._band_of(c["base"], c["post"]) for c in conv]
+        lo = hi = None
+        if bands and all(b is not None for b in bands):  # the mean over the conversions, as the relevance
+            lo, hi = sum(b[0] for b in bands) / len(bands), sum(b[1] for b in bands) / len(bands)
+        return {"relevance": relevance, "relevance_lo": lo, "relevance_hi": hi, "conversions": conv}
 
     def __init__(self, model, dataset, hp, rng=None):
         super().__init__(model, dataset, hp, rng)

@@ -13,7 +13,9 @@ Mirrors the reference's callers of the relevance engine:
   ``"counterfactuals"`` (kelpie_amd/builder.py): what the model predicts instead.  With
   ``side_effects`` > 0 every record also holds ``"side_effects"``: what each rule's edit
   does to the subject's other held-out facts.  With ``trace`` every record also holds
-  ``"traces"``: the optimizer's per-step loss of each rule's post-trainings.
+  ``"traces"``: the optimizer's per-step loss of each rule's post-trainings.  With
+  ``margins`` = a tolerance every record also holds ``"margins"``: how far each rule's ranks
+  are from changing, and the band of its relevance.
 
 The DP / CRIAGE baselines and summarisation are out of scope.
 """
@@ -61,9 +63,11 @@ class SufficientPipeline(Pipeline):
 
 
 def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="auto", entity_classes=None,
-                   pipelined=False, top_k=0, side_effects=0, trace=False, draws="reference", seed=0):
+                   pipelined=False, top_k=0, side_effects=0, trace=False, draws="reference", seed=0,
+                   margins=None):
     """explain.py:49-89 for the post-training engines (baseline=None, no summarisation).
-    ``draws`` / ``seed``: the source of the post-training draws (PostTrainingEngine.draws)."""
+    ``draws`` / ``seed``: the source of the post-training draws (PostTrainingEngine.draws).
+    ``margins``: the tolerance of the rank margins (PostTrainingEngine.margin_tol; None: none)."""
     if prefilter == TYPE_PREFILTER:
         raise NotImplementedError("type_based prefilter: out of scope (kelpie_amd/prefilters.py)")
     cls = PREFILTERS.get(prefilter, TopologyPreFilter) if prefilter else PREFILTERS[TOPOLOGY_PREFILTER]
@@ -73,13 +77,13 @@ def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="a
         engine = NecessaryPostTrainingEngine(model, dataset, hp)
         return NecessaryPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
                                                                   top_k=top_k, side_effects=side_effects,
-                                                                  trace=trace, draws=draws, seed=seed))
+                                                                  trace=trace, draws=draws, seed=seed, margins=margins))
     if mode == "sufficient":
         xsi = 0.9 if xsi is None else xsi
         engine = SufficientPostTrainingEngine(model, dataset, hp)
         return SufficientPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
                                                                   top_k=top_k, side_effects=side_effects,
-                                                                  trace=trace, draws=draws, seed=seed))
+                                                                  trace=trace, draws=draws, seed=seed, margins=margins))
     raise ValueError(f"unknown mode {mode!r}")
 
 
@@ -152,7 +156,8 @@ def reference_construction_draws(model_name, num_entities, num_relations, model_
 
 
 def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefilter=None, prefilter_k=20,
-                xsi=None, skip=-1, output_path=None, device=0, top_k=0, side_effects=0, trace=False):
+                xsi=None, skip=-1, output_path=None, device=0, top_k=0, side_effects=0, trace=False,
+                margins=None):
     """explain.py main() (explain.py:143-203) without the CLI: seeds 42 (explain.py:144),
     the reference model construction's random draws (:171-172), the checkpoint state dict
     (``torch.load(path, weights_only=True)``, :174) as a frozen model on the MI355X, the
@@ -169,5 +174,5 @@ def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefi
     reference_construction_draws(model_name, dataset.num_entities, dataset.num_relations, model_params)
     model = from_state_dict(model_name, dataset, state, model_params, device=device)
     pipe = build_pipeline(model, dataset, hp, mode, prefilter=prefilter, xsi=xsi, top_k=top_k,
-                          side_effects=side_effects, trace=trace)
+                          side_effects=side_effects, trace=trace, margins=margins)
     return explain_preds(pipe, dataset, preds, prefilter_k=prefilter_k, skip=skip, output_path=output_path)
