@@ -122,62 +122,49 @@ inline auto kp_join(const std::array<DevBuf*, N>&... lists) {
   return out;
 }
 
-// one set of rank rows (kp_posttrain.hpp's RankRows: upload_rank_rows fills it, rank_rows
-// counts it): the rows' (row, p, o) [n][3], objects [n], filter CSR and results [n]; one chunk
-// of rows' fp64 queries [chunk][dp], target | kelpie column scores [2][chunk] and filter
-// bitmaps; ConvE: the rows' encoder sources (-row - 1, p) [n] and one chunk's encoder output
-// [chunk][dp]
+// the buffers of one set of rank rows (RankSet below: kp_posttrain.hpp's upload_rank_rows
+// fills it, rank_rows counts it): the rows' (row, p, o) [n][3], objects [n], filter CSR and
+// results [n]; one chunk of rows' fp64 queries [chunk][dp], target | kelpie column scores
+// [2][chunk] and filter bitmaps; ConvE: the rows' encoder sources (-row - 1, p) [n] and one
+// chunk's encoder output [chunk][dp] (the slots' is ConveWs::q); the rows' margins [n] and one
+// chunk's margin workspace (MarginDev)
 struct RankRowsWs {
   DevBuf trip, po, filt_off, filt;
   DevBuf target, rank;
   DevBuf q64, t64, bits;
   DevBuf enc_src, enc_q;
-  DevBuf mg_out, mg_part;  // the rows' margins [n] and one chunk's margin workspace (MarginDev)
+  DevBuf mg_out, mg_part;
   auto all() {
     return std::array{&trip, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &bits, &enc_src, &enc_q, &mg_out, &mg_part};
   }
 };
 KP_WS_COMPLETE(RankRowsWs);
 
-// kp_posttrain_rank_f64's rank inputs and buffers: the same roles as RankWs's own, kept apart
-// so that an fp64 call leaves every buffer of the fp32 path as it was
-struct Rank64Ws {
-  DevBuf pred, po, filt_off, filt;  // the ranked triples, their objects, the filter CSR
-  DevBuf target, rank;              // [ns] the converted target (unused by the caller) and the ranks
-  DevBuf q64, t64, bits;            // fp64 ranking queries, target | kelpie column scores, filter bitmaps
-  auto all() { return std::array{&pred, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &bits}; }
-};
-KP_WS_COMPLETE(Rank64Ws);
-
-// what every *_posttrain_rank shares (kp_posttrain.hpp fills it): the rank of the
-// post-trained rows, the two sets of rank rows and the trace.
+// what every *_posttrain_rank shares (kp_posttrain.hpp fills it): the four sets of rank rows,
+// what only the slots have, and the trace.
+//   slots:  row s is (s, p_s, o_s) on the post-trained kelpie rows; never chunked;
+//   probes: kp_posttrain_rank_probes, row r is probe r, (slot, p, o), on the same rows;
+//   marks:  kp_posttrain_rank_marks, row s * marks + j is (row, p, o) of slot s on the family's
+//           mark workspace [ns][marks][dp], with the slot's filter list;
+//   f64:    kp_posttrain_rank_f64's slots, on its double rows.
+// The sets share a type and nothing else: the probes and the marks rank while the earlier
+// sets' downloads are still pending, and an fp64 call leaves every buffer of the fp32 path as
+// it was.
 // Two borrowers outside a post-training call, kept so that a context allocates what it
-// always did: complex_all_scores uploads its heads / relations into pred / po, and
+// always did: complex_all_scores uploads its heads / relations into slots.trip / slots.po, and
 // transe_all_scores writes its score matrix into scores.
 struct RankWs {
-  DevBuf pred;            // [ns][3] the ranked triples (ComplEx, TransE: their fp64 query kernels)
-  DevBuf po;              // [ns] their objects
-  DevBuf filt_off, filt;  // the filter CSR
-  DevBuf target, rank;    // [ns] results
-  DevBuf q64, t64;        // fp64 ranking queries [ns][dp]; target | kelpie column scores [2][ns]
-  DevBuf scores;          // fp32 score matrix [ns][ld] (KP_TE_RANK / KP_CV_RANK = f32)
-  DevBuf bits;            // launch_rank_f64's filter bitmap (kp_rank.hip owns it)
+  RankRowsWs slots;
+  DevBuf scores;  // fp32 score matrix [ns][ld] (KP_TE_RANK / KP_CV_RANK = f32)
   // kp_posttrain_rank_topk (kp_rank.hip owns the first two): the waves' candidate lists
   // [chunk slots][4 column blocks][k] (sort keys, columns) of one chunk of slots, and the
   // final lists [ns][k]
   DevBuf cand_key, cand_col;
   DevBuf top_ids, top_scores;
   DevBuf tr_off, tr_loss;  // kp_posttrain_rank_trace: the trace offsets [ns + 1] and the losses [steps]
-  DevBuf mg_out, mg_part;  // kp_posttrain_rank_margins: the slots' margins [ns] and their workspace (MarginDev)
-  // kp_posttrain_rank_probes: row r is probe r, (slot, p, o), on the slots' kelpie rows; and
-  // kp_posttrain_rank_marks: row s * marks + j is (row, p, o) of slot s on the family's mark
-  // workspace [ns][marks][dp], with the slot's filter list.  Neither set reuses the slots'
-  // buffers above or the other's: the earlier downloads are still pending when a set ranks
-  RankRowsWs probes, marks;
-  Rank64Ws f64;  // kp_posttrain_rank_f64
+  RankRowsWs probes, marks, f64;
   auto all() {
-    return kp_join(std::array{&pred, &po, &filt_off, &filt, &target, &rank, &q64, &t64, &scores, &bits, &cand_key,
-                              &cand_col, &top_ids, &top_scores, &tr_off, &tr_loss, &mg_out, &mg_part},
+    return kp_join(slots.all(), std::array{&scores, &cand_key, &cand_col, &top_ids, &top_scores, &tr_off, &tr_loss},
                    probes.all(), marks.all(), f64.all());
   }
 };
@@ -279,18 +266,17 @@ struct ConveWs {
   DevBuf gscale;                  // 1 / (b (n_ent + 1)) per kelpie instance
   DevBuf o;                       // attention output [rows * splits][dp]
   DevBuf dfc, gk, dflat, dl;      // backward: dL/dfc, g . x, dL/dflat (unfused), lhs image gradient
-  DevBuf rank_src;                // the ranked triples' encoder sources
   // kp_posttrain_rank_trace: a step's rows [rows][dp], one chunk's logits [chunk][ld] and the
   // rows' summed BCE terms (fp64)
   DevBuf tr_rows, tr_scores, tr_rowloss;
   // kp_posttrain_rank_marks: the mark rows [ns][marks][dp] and, per entry of the active lists,
-  // the mark row its update also stores (-1: none).  (The probes' and the mark rows' encoder
-  // sources and outputs are with their rank rows, RankRowsWs.)
+  // the mark row its update also stores (-1: none).  (Every set of rank rows' encoder
+  // sources, and the probes' and the mark rows' encoder outputs, are with the set: RankRowsWs.)
   DevBuf marks, mark_row;
   auto all() {
     return std::array{&x, &s1, &s2, &kinst, &finst, &acts, &tails, &keep_bits, &fcf, &fpairs, &flat, &slab,
                       &relu, &g3, &sr_src, &sr_rng, &psr, &relu_s, &slab_l, &mid, &map_l, &map_m, &gs, &dls,
-                      &q, &enc_src, &enc_bits, &fchunks, &fpart, &gscale, &o, &dfc, &gk, &dflat, &dl, &rank_src,
+                      &q, &enc_src, &enc_bits, &fchunks, &fpart, &gscale, &o, &dfc, &gk, &dflat, &dl,
                       &tr_rows, &tr_scores, &tr_rowloss, &marks, &mark_row};
   }
 };
@@ -517,18 +503,6 @@ void conve_train_read(kp_ctx* c, float* conv_w, float* conv_b, float* fc_w, floa
 void launch_gemm_abt(kp_ctx* c, const float* A, int lda, int M, const float* B, int ldb, int N, int K, float* out,
                      int ldo, const float* bias, int act, int ksplit);
 enum { RANK_TRIPLE_RESULTS = 0, RANK_PREDICT_TAILS = 1, RANK_SORT_POSITION = 2 };
-// get_triple_results of a maximizer in fp64 (kp_rank.hip): q64 [n][dp] the ranking queries,
-// t64 [n] their target scores (q . E_o, or the kelpie column when o is the kelpie),
-// kcol64 [n] the kelpie column scores q . x; rank = #{e not filtered : score_e >= target}
-// over the frozen entities (scores q . E_e summed in fp64, sequentially over d) plus the
-// kelpie column.  The target itself counts unless filtered.
-// topk > 0: also the topk best unmasked columns of every slot (better value first, equal
-// values by column), ids and converted scores into d_top_ids / d_top_scores [n][topk]
-// (device), -1 / 0 past the last unmasked column; the ranks are those of topk == 0
-// bits_buf: the filter bitmaps' buffer (default c->rank.bits; the probe rows bring their own)
-// mg: also the rows' margins (include/kelpie_hip.h, "Rank margins"), by a margin form of the
-// count and a merge of its per-workgroup partials, launched after the rows' own count; the
-// ranks and every other result are those without it
 // launch_rank_f64's score kinds
 enum { RANK64_DOT = 0, RANK64_SIGMOID = 1, RANK64_DIST = 2, RANK64_DIST1 = 3 };
 // The margins of a set of rank rows on the device: the results [n] of every row, and the
@@ -552,10 +526,41 @@ struct MarginDev {
     return m;
   }
 };
-void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* d_t64, const double* d_kcol64,
-                     const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt, float* d_target,
-                     int64_t* d_rank, int act = 0, int topk = 0, int32_t* d_top_ids = nullptr,
-                     float* d_top_scores = nullptr, DevBuf* bits_buf = nullptr, const MarginDev* mg = nullptr);
+// A set of rows to rank, on the device (one RankRowsWs each; kp_posttrain.hpp's
+// upload_rank_rows builds every set).  Row r is (row, p, o): the family's query kernel reads
+// "row rows[3 r] of X", relation p, object o.  The inputs and results of all n rows, and the
+// fp64 operands and filter bitmaps of one chunk of rows (the chunks run one after the other on
+// the stream; the slots are one chunk).
+struct RankSet {
+  int n = 0, chunk = 0;
+  const float* X = nullptr;  // the rows rows[3 r] indexes (kp_posttrain_rank_f64: its queries hold the double rows)
+  int32_t* rows = nullptr;   // [n][3] (row, p, o)
+  int32_t* po = nullptr;     // [n] the objects
+  int32_t* filt_off = nullptr;  // the filter CSR
+  int32_t* filt = nullptr;
+  float* target = nullptr;  // [n] results
+  int64_t* rank = nullptr;  // [n]
+  // one chunk (nullptr under the fp32 diagnostic ranks): the fp64 queries [chunk][dp], the target
+  // scores [chunk] (q . E_o, or the kelpie column when o is the kelpie) and the kelpie column
+  // scores [chunk], the filter bitmaps over the n_ent + 1 columns
+  double *q = nullptr, *t = nullptr, *kcol = nullptr;
+  uint32_t* bits = nullptr;
+  int2* enc_src = nullptr;  // ConvE: [n] the rows' encoder sources (-row - 1, p)
+  float* enc_q = nullptr;   // ConvE: [chunk][dp] the chunk's encoder output
+  MarginDev mg;             // the rows' margins (cap 0: none), one chunk's workspace
+  // the slots only (kp_posttrain_rank_topk, k > 0): the k best unmasked columns of every row
+  // (better value first, equal values by column), ids and converted scores [n][k], -1 / 0 past
+  // the last unmasked column
+  int k = 0;
+  int32_t* top_ids = nullptr;
+  float* top_scores = nullptr;
+};
+// get_triple_results in fp64 (kp_rank.hip) of the rows [r0, r0 + m) of a set, whose queries
+// the family has just written into the set's chunk: rank = #{e not filtered : score_e counts
+// against the target} over the frozen entities (one sequential fp64 chain over d each) plus the
+// kelpie column, the target itself by the `own` rule; with the set's lists and margins (include/
+// kelpie_hip.h, "Rank margins"), which change neither the ranks nor any other result
+void launch_rank_f64(kp_ctx* c, const RankSet& d, int r0, int m, int act);
 void launch_rank_count(kp_ctx* c, int n_slots, const float* d_scores, int ld, int n_cols,
                        const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt,
                        int minimizer, float* d_target, int64_t* d_rank,

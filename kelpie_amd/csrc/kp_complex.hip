@@ -634,16 +634,16 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
 // fp64 ranking queries (launch_rank_f64): q_s = x_s o R[p_s] from exact fp64 products of
 // the fp32 operands; the target score q_s . E_o and the kelpie column q_s . x_s as one
 // sequential fp64 FMA chain over d (the order kp_rank_f64_count scores every entity in).
-// PROBE (kp_posttrain_rank_probes): row s is a probe, pred its (slot, p, o), and x the
-// kelpie row of that slot instead of row s; every operation and its order are the slot form's
+// Row s of a set of rank rows is pred[3 s ..] = (row, p, o): x is row `row` of X (the slots: s
+// itself; a probe: its slot's kelpie row; a mark row: its row of the mark workspace).
 // XT: the kelpie rows' type (double: kp_posttrain_rank_f64, whose row is never rounded)
-template <int DP, class Prod, bool PROBE = false, class XT = float>
+template <int DP, class Prod, class XT = float>
 __global__ void kp_cx_rankq64(const XT* __restrict__ X, const float* __restrict__ R, const float* __restrict__ E,
                               int n_ent, int half, const int32_t* __restrict__ pred, int n_slots,
                               double* __restrict__ Q, double* __restrict__ t64, double* __restrict__ kcol64) {
   const int s = blockIdx.x;
   if (s >= n_slots) return;
-  const XT* x = X + (size_t)(PROBE ? pred[3 * s] : s) * DP;
+  const XT* x = X + (size_t)pred[3 * s] * DP;
   const float* rel = R + (size_t)pred[3 * s + 1] * DP;
   double* q = Q + (size_t)s * DP;
   for (int d = threadIdx.x; d < DP; d += blockDim.x) q[d] = Prod::q64(x, rel, d, half);
@@ -771,19 +771,12 @@ void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, c
   KP_HIP(hipGetLastError());
 }
 
+// the fp64 queries of the rows [r0, r0 + m) of a set of rank rows, on the rows X, into the
+// set's chunk buffers
 template <int DB, class Prod, class XT = float>
-void launch_rankq64(kp_ctx* c, const XT* X, const int32_t* pred, int n, double* Q, double* t64, double* kcol64) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod, false, XT>), dim3(n), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
-                     Prod::extent(c->dim), pred, n, Q, t64, kcol64);
-  KP_HIP(hipGetLastError());
-}
-
-// the probe form: the rows [r0, r0 + m) of a set of rank rows into its chunk buffers
-template <int DB, class Prod>
-void launch_probeq64(kp_ctx* c, const RankRows& rr, int r0, int m) {
-  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod, true>), dim3(m), dim3(64), 0, c->stream, rr.X, c->dR, c->dE, c->n_ent,
-                     Prod::extent(c->dim), rr.trip + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol);
+void launch_rankq64(kp_ctx* c, const XT* X, const RankSet& rr, int r0, int m) {
+  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod, XT>), dim3(m), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
+                     Prod::extent(c->dim), rr.rows + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol);
   KP_HIP(hipGetLastError());
 }
 
@@ -815,10 +808,7 @@ struct CxDev {
   int2* pairs;
   int4 *acts, *stepq, *stept;
   float *contrib, *tsum, *qpair, *lsef;
-  Rank64Dev r64;
-  int32_t* pred;
-  RankDev rk;
-  RankRows probes;
+  RankSet rk, probes;  // the slots, kp_posttrain_rank_probes
   CxTraceDev trace;
   MarksDev marks;
   int32_t* mark_row = nullptr;  // [acts] the mark row an active entry's update also stores, or -1
@@ -859,9 +849,7 @@ CxDev cx_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostRe
   // the ranking's inputs and buffers now, ahead of the step loop: an upload from pageable
   // memory after the loop waited for the whole loop on the device, so the rank kernels
   // were enqueued only then (a host round trip per batch with the context idle)
-  d.r64 = rank64_buffers(c, ns);
-  d.pred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
-  d.rk = upload_rank_inputs(c, bt, rq);
+  d.rk = upload_slots(c, c->rank.slots, bt, rq, d.X);
   d.probes = upload_probes(c, bt, rq, d.X);
   // kp_posttrain_rank_marks: the mark rows (each the padded x0 until a step captures it)
   d.marks = upload_marks(c, c->cx.marks, hp, bt, rq, d.X);
@@ -1253,7 +1241,6 @@ void posttrain_rank_f64(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const Po
 
   // ---- workspaces, all sized here, ahead of the step loop (c->cx.f64, c->rank.f64)
   Complex64Ws& w = c->cx.f64;
-  Rank64Ws& rw = c->rank.f64;
   std::vector<double> xp((size_t)ns * DP, 0.0);
   for (int s = 0; s < ns; ++s) std::memcpy(&xp[(size_t)s * DP], f.x0 + (size_t)s * dim, sizeof(double) * dim);
   double* X = upload(c, w.x, xp.data(), xp.size());
@@ -1279,18 +1266,8 @@ void posttrain_rank_f64(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const Po
   double* al = ensure_n<double>(w.al, att_rows);
   double* ao = ensure_n<double>(w.ao, att_rows * DP);
   double* qs = ensure_n<double>(w.qs, (size_t)std::max(sp.max_nq, 1) * DP);
-  // the rank's inputs and buffers
-  double* rq64 = ensure_n<double>(rw.q64, (size_t)ns * DP);
-  double* rt64 = ensure_n<double>(rw.t64, 2 * (size_t)ns);
-  double* rk64 = rt64 + ns;
-  const int32_t* dpred = upload(c, rw.pred, bt->pred, (size_t)ns * 3);
-  std::vector<int32_t> po(ns);
-  for (int s = 0; s < ns; ++s) po[s] = bt->pred[3 * s + 2];
-  const int32_t* dpo = upload(c, rw.po, po.data(), po.size());
-  const int32_t* dfo = upload(c, rw.filt_off, bt->filt_off, (size_t)ns + 1);
-  const int32_t* dfl = upload(c, rw.filt, bt->filt, (size_t)bt->filt_off[ns]);
-  float* dtarget = ensure_n<float>(rw.target, (size_t)ns);
-  int64_t* drank = ensure_n<int64_t>(rw.rank, (size_t)ns);
+  // the slots as a set of rank rows of its own; its queries read the double rows X
+  const RankSet rk = upload_slots(c, c->rank.f64, bt, rq, nullptr);
 
   // ---- before the loop: target sums, the frozen-head pairs' q and frozen log-sum-exp
   KP_HIP(hipEventRecord(c->ev0, c->stream));
@@ -1366,12 +1343,13 @@ void posttrain_rank_f64(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const Po
   KP_HIP(hipEventRecord(lev.b, c->stream));
 
   // ---- the rank on the fp64 row; out_score is the fp64 target value itself
-  CX_DISPATCH(DBV, (launch_rankq64<DB, Prod, double>(c, X, dpred, ns, rq64, rt64, rk64)));
-  launch_rank_f64(c, ns, rq64, rt64, rk64, dpo, dfo, dfl, dtarget, drank, RANK64_DOT, 0, nullptr, nullptr, &rw.bits);
+  rank_rows(c, rk, RANK64_DOT, [c, X, DBV](const RankSet& rr, int r0, int m) {
+    CX_DISPATCH(DBV, (launch_rankq64<DB, Prod, double>(c, X, rr, r0, m)));
+  });
   KP_HIP(hipEventRecord(c->ev1, c->stream));
   if (f.out_x) KP_HIP(hipMemcpyAsync(xp.data(), X, sizeof(double) * xp.size(), hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(f.out_score, rt64, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(bt->out_rank, drank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipMemcpyAsync(f.out_score, rk.t, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipMemcpyAsync(bt->out_rank, rk.rank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
   KP_HIP(hipStreamSynchronize(c->stream));
   if (f.out_x)
     for (int s = 0; s < ns; ++s) std::memcpy(f.out_x + (size_t)s * dim, &xp[(size_t)s * DP], sizeof(double) * dim);
@@ -1445,15 +1423,11 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostRe
 
   // ---- ranking: scores of (kelpie, p, .) over E plus the kelpie column, in fp64
   // (launch_rank_f64: at the reference init the target's neighbours are ~1e-5 relative away)
-  CX_DISPATCH(c->dp / 16, launch_rankq64<DB, Prod>(c, d.X, d.pred, ns, d.r64.q, d.r64.t, d.r64.kcol));
-  launch_rank_f64(c, ns, d.r64.q, d.r64.t, d.r64.kcol, d.rk.po, d.rk.filt_off, d.rk.filt, d.rk.target, d.rk.rank,
-                  RANK64_DOT, rq.k, d.rk.top_ids, d.rk.top_scores, nullptr, d.rk.margins());
-  // the probes on the slots' rows, then the marks on the mark workspace
-  const auto probe_queries = [c](const RankRows& rr, int r0, int m) {
-    CX_DISPATCH(c->dp / 16, launch_probeq64<DB, Prod>(c, rr, r0, m));
+  // the slots, then the probes on the slots' rows, then the marks on the mark workspace
+  const auto queries = [c](const RankSet& rr, int r0, int m) {
+    CX_DISPATCH(c->dp / 16, launch_rankq64<DB, Prod>(c, rr.X, rr, r0, m));
   };
-  rank_rows(c, d.probes, RANK64_DOT, probe_queries);
-  rank_rows(c, d.marks.rows, RANK64_DOT, probe_queries);
+  for (const RankSet* set : {&d.rk, &d.probes, &d.marks.rows}) rank_rows(c, *set, RANK64_DOT, queries);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
 
   const double t_enq = download_results(c, bt, d.X, d.rk, xp, rq, d.probes, d.trace, d.marks);
@@ -1502,8 +1476,8 @@ void complex_all_scores(kp_ctx* c, int n, const int32_t* heads, const int32_t* r
   if (n <= 0) return;
   // the pairs go through the rank's two id buffers (idle outside complex_posttrain_rank)
   // rather than two of their own, which keeps the context's device allocations as they were
-  int32_t* dh = upload(c, c->rank.pred, heads, (size_t)n);
-  int32_t* dr = upload(c, c->rank.po, rels, (size_t)n);
+  int32_t* dh = upload(c, c->rank.slots.trip, heads, (size_t)n);
+  int32_t* dr = upload(c, c->rank.slots.po, rels, (size_t)n);
   float* dS = ensure_n<float>(c->cx.score_out, (size_t)n * c->n_ent);
   complex_scores_dev(c, n, dh, dr, dS, c->n_ent);
   KP_HIP(hipMemcpyAsync(out, dS, sizeof(float) * (size_t)n * c->n_ent, hipMemcpyDeviceToHost, c->stream));

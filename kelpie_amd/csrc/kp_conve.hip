@@ -578,10 +578,9 @@ __global__ __launch_bounds__(256) void kp_cv_update(CvConst k, const CvAct* __re
 // the order kp_rank_f64_count scores every entity in.  At the reference init the sigmoid
 // scores of ~10^5 entities lie within ~0.005 of 0.5, a few per fp32 ulp there, so fp32
 // scores tie and their rounding moves the rank; the logits order them as a fp64 run does.
-// PROBE (kp_posttrain_rank_probes): row s is a probe, po its (slot, p, o) and Qr its encoder
-// output (encode_eval on (-slot - 1, p)); x is the kelpie row of that slot instead of row s.
-// Every operation and its order are the slot form's
-template <bool PROBE = false>
+// Row s of a set of rank rows is po[3 s ..] = (row, p, o) and Qr[s] its encoder output
+// (encode_eval on (-row - 1, p)): x is row `row` of X (the slots: s itself; a probe: its slot's
+// kelpie row; a mark row: its row of the mark workspace).
 __global__ void kp_cv_rankq64(const float* __restrict__ Qr, const float* __restrict__ X,
                               const float* __restrict__ E, int n_ent, int dp, const int32_t* __restrict__ po,
                               int n_slots, double* __restrict__ Q, double* __restrict__ t64,
@@ -592,8 +591,8 @@ __global__ void kp_cv_rankq64(const float* __restrict__ Qr, const float* __restr
   for (int d = threadIdx.x; d < dp; d += blockDim.x) q[d] = (double)Qr[(size_t)s * dp + d];
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float* x = X + (size_t)(PROBE ? po[3 * s] : s) * dp;
-    const int o = PROBE ? po[3 * s + 2] : po[s];
+    const float* x = X + (size_t)po[3 * s] * dp;
+    const int o = po[3 * s + 2];
     double z = 0.0, t = 0.0;
     for (int d = 0; d < dp; ++d) z = __fma_rn(q[d], (double)x[d], z);
     if (o < n_ent) {
@@ -888,7 +887,7 @@ struct CvDev {
   CvBits* enc_bits;
   float* gscale;
   std::vector<AttnPlan> step_plan;  // [T]
-  RankRows probes;              // kp_posttrain_rank_probes
+  RankSet probes;               // kp_posttrain_rank_probes
   MarksDev marks;               // kp_posttrain_rank_marks
   int32_t* mark_row = nullptr;  // [acts] the mark row an active entry's update also stores, or -1
   float *O, *dfc, *gk, *dflat, *dl, *wt;
@@ -1283,6 +1282,9 @@ int64_t cv_step_loop(kp_ctx* c, const kp_hp* hp, const CvConst& kc, const CvStep
   return launches;
 }
 
+// what a rank row's pass through encode_eval holds: its feature maps, FC output and encoder output
+size_t cv_enc_row_bytes(const kp_ctx* c) { return sizeof(float) * ((size_t)c->hidden + c->dim + c->dp); }
+
 // the optional requests' uploads and buffers (ahead of the step loop), in the order the stream
 // has always seen them: the probes, the trace, the marks.  A chunk's rank rows also pass
 // through encode_eval's feature maps and FC output, counted into the chunk's budget (which
@@ -1290,7 +1292,7 @@ int64_t cv_step_loop(kp_ctx* c, const kp_hp* hp, const CvConst& kc, const CvStep
 // of the active lists the mark row its update also stores
 CvTraceDev cv_request_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq,
                                  const CvStepPlan& sp, CvDev& d) {
-  const size_t enc_row = sizeof(float) * ((size_t)c->hidden + c->dim + c->dp);
+  const size_t enc_row = cv_enc_row_bytes(c);
   d.probes = upload_probes(c, bt, rq, d.X, enc_row);
   const CvTraceDev tr = cv_trace_workspaces(c, bt, rq, sp);
   d.marks = upload_marks(c, c->cv.marks, hp, bt, rq, d.X, enc_row);
@@ -1301,37 +1303,31 @@ CvTraceDev cv_request_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt,
   return tr;
 }
 
-// rank: sigmoid(enc(x, R_p) . E_e), kelpie column, maximizer
-RankDev cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const PostReq& rq, const CvDev& d) {
+// rank: sigmoid(enc(x, R_p) . E_e), kelpie column, maximizer.  The slots' encoder output is
+// c->cv.q (the step's rows in the loop), not a buffer of the set's own.
+RankSet cv_rank(kp_ctx* c, const CvConst& kc, const kp_batch* bt, const PostReq& rq, const CvDev& d) {
   const int ns = bt->n_slots, K = c->n_ent, DP = c->dp;
-  std::vector<int2> rsrc(ns);
-  for (int s = 0; s < ns; ++s) rsrc[s] = make_int2(-s - 1, bt->pred[3 * s + 1]);
-  int2* dRsrc = upload(c, c->cv.rank_src, rsrc.data(), rsrc.size());
-  float* dQr = ensure_n<float>(c->cv.q, (size_t)std::max(ns, d.mk) * DP);
-  encode_eval(c, ns, dRsrc, d.X, dQr);
-  const RankDev rk = upload_rank_inputs(c, bt, rq);
+  RankSetReq sr;
+  sr.rank64 = c->cv_rank64 != 0;
+  sr.enc_row_bytes = cv_enc_row_bytes(c);
+  sr.enc_q = ensure_n<float>(c->cv.q, (size_t)std::max(ns, d.mk) * DP);
+  const RankSet rk = upload_slots(c, c->rank.slots, bt, rq, d.X, sr);
   if (c->cv_rank64) {
-    const Rank64Dev r64 = rank64_buffers(c, ns);
-    hipLaunchKernelGGL(kp_cv_rankq64<false>, dim3(ns), dim3(64), 0, c->stream, dQr, d.X, c->dE, K, DP, rk.po, ns, r64.q,
-                       r64.t, r64.kcol);
-    KP_HIP(hipGetLastError());
-    launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank, RANK64_SIGMOID,
-                    rq.k, rk.top_ids, rk.top_scores, nullptr, rk.margins());
-    // the probes on the slots' rows, then the marks on the mark workspace: a chunk's rows
-    // through the encoder (eval mode) on the set's rows, then the probe form and the count
-    const auto probe_queries = [c, K, DP](const RankRows& rr, int r0, int m) {
+    // the slots, then the probes on the slots' rows, then the marks on the mark workspace: a
+    // chunk's rows through the encoder (eval mode) on the set's rows, then the queries and the count
+    const auto queries = [c, K, DP](const RankSet& rr, int r0, int m) {
       encode_eval(c, m, rr.enc_src + r0, rr.X, rr.enc_q);
-      hipLaunchKernelGGL(kp_cv_rankq64<true>, dim3(m), dim3(64), 0, c->stream, rr.enc_q, rr.X, c->dE, K, DP,
-                         rr.trip + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol);
+      hipLaunchKernelGGL(kp_cv_rankq64, dim3(m), dim3(64), 0, c->stream, rr.enc_q, rr.X, c->dE, K, DP,
+                         rr.rows + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol);
       KP_HIP(hipGetLastError());
     };
-    rank_rows(c, d.probes, RANK64_SIGMOID, probe_queries);
-    rank_rows(c, d.marks.rows, RANK64_SIGMOID, probe_queries);
+    for (const RankSet* set : {&rk, &d.probes, &d.marks.rows}) rank_rows(c, *set, RANK64_SIGMOID, queries);
   } else {
     const int ld = round_up(K + 1, 4);
     float* dScores = ensure_n<float>(c->rank.scores, (size_t)ns * ld);
-    launch_score_gemm(c, dQr, ns, dScores, ld, 1);
-    hipLaunchKernelGGL(kp_cv_kcol, dim3(ns), dim3(64), 0, c->stream, ns, kc, dQr, d.X, dScores, ld);
+    encode_eval(c, ns, rk.enc_src, d.X, rk.enc_q);
+    launch_score_gemm(c, rk.enc_q, ns, dScores, ld, 1);
+    hipLaunchKernelGGL(kp_cv_kcol, dim3(ns), dim3(64), 0, c->stream, ns, kc, rk.enc_q, d.X, dScores, ld);
     KP_HIP(hipGetLastError());
     launch_rank_count(c, ns, dScores, ld, K + 1, rk.po, rk.filt_off, rk.filt, 0, rk.target, rk.rank);
   }
@@ -1365,7 +1361,7 @@ void conve_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const 
   const int64_t launches = cv_step_loop(c, hp, kc, sp, d, tr);
   const double t_loop = g_host_times ? host_ms() : 0.0;
 
-  const RankDev rk = cv_rank(c, kc, bt, rq, d);
+  const RankSet rk = cv_rank(c, kc, bt, rq, d);
   KP_HIP(hipEventRecord(c->ev1, c->stream));
   download_results(c, bt, d.X, rk, xp, rq, d.probes, tr, d.marks);
   if (g_host_times)

@@ -102,7 +102,7 @@ inline int kp_marks_row_at(const KpMarkPlan& plan, int s, int t) {
   return -1;
 }
 
-// The marks of a batch the batch check accepted as rank rows (kp_posttrain.hpp's RankRows):
+// The marks of a batch the batch check accepted as rank rows (kp_common.hpp's RankSet):
 // row r = s * nm + j is trip[3 r ..] = (r, p, o) of slot s (pred [n_slots][3]), po[r] its
 // object, and its filter list [fo[r], fo[r + 1]) of `f` a copy of the slot's (`f` holds at
 // least one entry).  nullptr, or the bound the rows exceed: nothing is written then, and

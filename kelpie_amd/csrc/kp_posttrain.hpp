@@ -1,14 +1,14 @@
 // kp_posttrain.hpp -- the host work the three *_posttrain_rank functions share: the check of
 // the batch and of the request (require_request), Adam's step scalars, the kelpie rows'
-// padding, the rank inputs, the rank rows (RankRows: the probes and the mark rows, one upload
-// and one chunked count for both), the trace's offsets and losses (TraceDev), the download of
-// every result and the hot-launch timing.  The model-specific step planning is pure host code
-// in headers of its own (kp_cx_plan.hpp: ComplEx / DistMult; kp_cv_plan.hpp: ConvE; TransE's
-// schedule is kp_sched.cpp), as are the request's checks and its expansion into rank rows
-// (kp_batch_check.hpp, kp_probe_check.hpp, kp_trace_check.hpp, kp_marks_check.hpp,
-// kp_margins_check.hpp); the
-// launches, and where in the call each upload happens, stay in kp_complex.hip / kp_transe.hip
-// / kp_conve.hip.
+// padding, the rank rows (kp_common.hpp's RankSet: the slots, the probes and the mark rows are
+// each one set, built by one upload, upload_rank_rows, and ranked by one chunked count,
+// rank_rows, on the family's one query callable), the trace's offsets and losses (TraceDev),
+// the download of every result and the hot-launch timing.  The model-specific step planning is
+// pure host code in headers of its own (kp_cx_plan.hpp: ComplEx / DistMult; kp_cv_plan.hpp:
+// ConvE; TransE's schedule is kp_sched.cpp), as are the request's checks and its expansion into
+// rank rows (kp_batch_check.hpp, kp_probe_check.hpp, kp_trace_check.hpp, kp_marks_check.hpp,
+// kp_margins_check.hpp); the launches, and where in the call each upload happens, stay in
+// kp_complex.hip / kp_transe.hip / kp_conve.hip.
 #pragma once
 
 #include <chrono>
@@ -120,19 +120,6 @@ inline float* upload_x0(kp_ctx* c, DevBuf& b, const kp_batch* bt, std::vector<fl
   return upload(c, b, xp.data(), xp.size());
 }
 
-// the rank's inputs and results on the device (c->rank)
-struct RankDev {
-  int32_t* po;        // [ns] the ranked objects
-  int32_t* filt_off;  // the filter CSR
-  int32_t* filt;
-  float* target;  // [ns]
-  int64_t* rank;  // [ns]
-  int32_t* top_ids = nullptr;   // [ns][k] (kp_posttrain_rank_topk, k > 0)
-  float* top_scores = nullptr;  // [ns][k]
-  MarginDev mg;                 // the slots' margins (kp_posttrain_rank_margins; cap 0: none)
-  const MarginDev* margins() const { return mg.cap > 0 ? &mg : nullptr; }
-};
-
 // The margins of n rank rows ranked `cap` rows at a launch: every result array [n] in `out`,
 // the thresholds and the per-workgroup partials of one launch in `part`.  Sized where the rank
 // inputs and the rank rows are sized, never inside the step loop.  Not wanted (or n == 0): an
@@ -176,130 +163,113 @@ inline void download_margins(kp_ctx* c, const MarginDev& d, const kp_margin_out&
   to_host(o.id_worse, d.id_worse, 4 * n);
 }
 
-// upload the ranked objects and the filter CSR, size the result buffers.  The caller
-// chooses where in its call this happens: an upload's position decides what it overlaps.
-inline RankDev upload_rank_inputs(kp_ctx* c, const kp_batch* bt, const PostReq& rq = {}) {
-  const int ns = bt->n_slots;
-  std::vector<int32_t> po(ns);
-  for (int s = 0; s < ns; ++s) po[s] = bt->pred[3 * s + 2];
-  RankDev r;
-  r.po = upload(c, c->rank.po, po.data(), po.size());
-  r.filt_off = upload(c, c->rank.filt_off, bt->filt_off, (size_t)ns + 1);
-  r.filt = upload(c, c->rank.filt, bt->filt, (size_t)bt->filt_off[ns]);
-  r.target = ensure_n<float>(c->rank.target, (size_t)ns);
-  r.rank = ensure_n<int64_t>(c->rank.rank, (size_t)ns);
-  if (rq.k > 0) {
-    r.top_ids = ensure_n<int32_t>(c->rank.top_ids, (size_t)ns * rq.k);
-    r.top_scores = ensure_n<float>(c->rank.top_scores, (size_t)ns * rq.k);
-  }
-  if (rq.margins) r.mg = margin_buffers(c, c->rank.mg_out, c->rank.mg_part, rq.margins, &rq.margins->slots, ns, ns);
-  return r;
-}
-
-// launch_rank_f64's fp64 operands: the queries [ns][dp], and the target scores [ns]
-// followed by the kelpie column scores [ns]
-struct Rank64Dev {
-  double *q, *t, *kcol;
-};
-inline Rank64Dev rank64_buffers(kp_ctx* c, int ns) {
-  Rank64Dev r;
-  r.q = ensure_n<double>(c->rank.q64, (size_t)ns * c->dp);
-  r.t = ensure_n<double>(c->rank.t64, 2 * (size_t)ns);
-  r.kcol = r.t + ns;
-  return r;
-}
-
-// A set of rank rows on the device (c->rank.probes, c->rank.marks): rows ranked like the
-// slots, each naming the kelpie row it stands on.  Row r is (row, p, o): the probe form of the
-// family's query kernel reads "row trip[3 r] of X" where the slot form reads row r.  The
-// inputs and results of all n rows, and the fp64 operands of one chunk of rows (the chunks run
-// one after the other on the stream).
-//   the probes: row r is probe r, (slot, p, o), X the slots' kelpie rows;
-//   the marks:  row s * nm + j is (s * nm + j, p, o) of slot s with the slot's filter list,
-//               X the family's mark workspace [ns][nm][dp].
+// What a set of rank rows (kp_common.hpp's RankSet) needs besides its rows:
+//   the slots:  row s is (s, p_s, o_s) (kp_slot_rows), X the post-trained kelpie rows;
+//   the probes: row r is probe r, (slot, p, o) (kp_probe_rows), X the same rows;
+//   the marks:  row s * nm + j is (s * nm + j, p, o) of slot s with the slot's filter list
+//               (kp_mark_rows), X the family's mark workspace [ns][nm][dp].
 constexpr size_t PROBE_WS_BYTES = (size_t)64 << 20;  // a chunk's query rows and bitmaps, as TOPK_WS_BYTES
 constexpr int PROBE_GROUP = 16;                      // kp_rank_f64_count's rows per workgroup row (RQ)
-struct RankRows {
-  int n = 0, chunk = 0;
-  const float* X = nullptr;  // the rows trip[3 r] indexes
-  int32_t* trip = nullptr;   // [n][3] (row, p, o)
-  int32_t* po = nullptr;     // [n]
-  int32_t* filt_off = nullptr;
-  int32_t* filt = nullptr;
-  float* target = nullptr;  // [n]
-  int64_t* rank = nullptr;  // [n]
-  double *q = nullptr, *t = nullptr, *kcol = nullptr;  // [chunk][dp], [chunk], [chunk]
-  DevBuf* bits = nullptr;                              // the chunk's filter bitmaps (launch_rank_f64 sizes them)
-  int2* enc_src = nullptr;                             // ConvE: [n] the rows' encoder sources (-row - 1, p)
-  float* enc_q = nullptr;                              // ConvE: [chunk][dp] the chunk's encoder output
-  MarginDev mg;                                        // the rows' margins (cap 0: none), one chunk's workspace
+struct RankSetReq {
+  // the diagnostic variable that forces the rows per chunk (KP_PROBE_CHUNK, KP_MARKS_CHUNK);
+  // nullptr: the set is one chunk (the slots are never chunked)
+  const char* chunk_env = nullptr;
+  // false (the fp32 diagnostic ranks, KP_TE_RANK / KP_CV_RANK = f32): the inputs and the
+  // results only, no fp64 operands and no bitmaps
+  bool rank64 = true;
+  // ConvE, else 0: what a chunk row's pass through the encoder holds, counted into the chunk's
+  // budget; the rows' encoder sources are then uploaded as well, and the chunk's encoder output
+  // is `enc_q` (the slots: ConveWs::q, sized by the caller) or, when nullptr, sized here
+  size_t enc_row_bytes = 0;
+  float* enc_q = nullptr;
+  const kp_margins* mg = nullptr;  // kp_posttrain_rank_margins, and which of its outputs are the set's
+  const kp_margin_out* mg_want = nullptr;
+  int k = 0;  // kp_posttrain_rank_topk (the slots only): the lists' length
 };
 
-// upload a set of rank rows (kp_probe_check.hpp's / kp_marks_check.hpp's expansion) and size
-// every buffer of `ws`; called with the call's other uploads, ahead of the step loop.
-// `chunk_env`: the diagnostic variable that forces the rows per chunk.  `enc_row_bytes` (ConvE,
-// else 0): what a chunk row's pass through the encoder holds, counted into the chunk's budget;
-// the rows' encoder sources are then uploaded and the chunk's encoder output sized as well.
-// The uploads read host vectors that end with the caller: pageable copies are staged before
-// hipMemcpyAsync returns.
-inline RankRows upload_rank_rows(kp_ctx* c, RankRowsWs& ws, const char* chunk_env, const float* X,
-                                 const std::vector<int32_t>& trip, const std::vector<int32_t>& po,
-                                 const int32_t* filt_off, const int32_t* filt, size_t n_filt,
-                                 size_t enc_row_bytes = 0, const kp_margins* mg = nullptr,
-                                 const kp_margin_out* mg_want = nullptr) {
-  RankRows d;
+// Upload a set of rank rows and size every buffer of `ws` it uses.  The caller chooses where in
+// its call this happens: an upload's position decides what it overlaps (an upload from pageable
+// memory after the step loop waits for the whole loop on the device, so the rank kernels are
+// enqueued only then).  The uploads read host vectors that end with the caller: pageable copies
+// are staged before hipMemcpyAsync returns.
+inline RankSet upload_rank_rows(kp_ctx* c, RankRowsWs& ws, const float* X, const std::vector<int32_t>& trip,
+                                const std::vector<int32_t>& po, const int32_t* filt_off, const int32_t* filt,
+                                size_t n_filt, const RankSetReq& rq = {}) {
+  RankSet d;
   const int n = (int)po.size();
   if (n == 0) return d;
   const int nwords = (c->n_ent + 1 + 31) / 32;
-  int forced = 0;
-  if (const char* a = std::getenv(chunk_env)) forced = std::max(0, std::atoi(a));
-  d.n = n;
-  d.chunk = kp_probe_chunk(n, sizeof(double) * c->dp + sizeof(uint32_t) * nwords + enc_row_bytes, PROBE_WS_BYTES,
-                           PROBE_GROUP, forced);
+  d.n = d.chunk = n;
+  if (rq.chunk_env) {
+    const char* a = std::getenv(rq.chunk_env);
+    d.chunk = kp_probe_chunk(n, sizeof(double) * c->dp + sizeof(uint32_t) * nwords + rq.enc_row_bytes, PROBE_WS_BYTES,
+                             PROBE_GROUP, a ? std::max(0, std::atoi(a)) : 0);
+  }
   d.X = X;
-  d.trip = upload(c, ws.trip, trip.data(), trip.size());
+  d.rows = upload(c, ws.trip, trip.data(), trip.size());
   d.po = upload(c, ws.po, po.data(), po.size());
   d.filt_off = upload(c, ws.filt_off, filt_off, (size_t)n + 1);
   d.filt = upload(c, ws.filt, filt, n_filt);
   d.target = ensure_n<float>(ws.target, (size_t)n);
   d.rank = ensure_n<int64_t>(ws.rank, (size_t)n);
-  d.q = ensure_n<double>(ws.q64, (size_t)d.chunk * c->dp);
-  d.t = ensure_n<double>(ws.t64, 2 * (size_t)d.chunk);
-  d.kcol = d.t + d.chunk;
-  d.bits = &ws.bits;
-  (void)ws.bits.ensure(sizeof(uint32_t) * (size_t)d.chunk * nwords);
-  if (enc_row_bytes > 0) {
+  if (rq.rank64) {
+    d.q = ensure_n<double>(ws.q64, (size_t)d.chunk * c->dp);
+    d.t = ensure_n<double>(ws.t64, 2 * (size_t)d.chunk);
+    d.kcol = d.t + d.chunk;
+    d.bits = ensure_n<uint32_t>(ws.bits, (size_t)d.chunk * nwords);
+  }
+  if (rq.enc_row_bytes > 0) {
     std::vector<int2> src((size_t)n);
     for (int r = 0; r < n; ++r) src[r] = make_int2(-trip[3 * (size_t)r] - 1, trip[3 * (size_t)r + 1]);
     d.enc_src = upload(c, ws.enc_src, src.data(), src.size());
-    d.enc_q = ensure_n<float>(ws.enc_q, (size_t)d.chunk * c->dp);
+    d.enc_q = rq.enc_q ? rq.enc_q : ensure_n<float>(ws.enc_q, (size_t)d.chunk * c->dp);
   }
-  if (mg) d.mg = margin_buffers(c, ws.mg_out, ws.mg_part, mg, mg_want, n, std::min(n, d.chunk));
+  if (rq.mg) d.mg = margin_buffers(c, ws.mg_out, ws.mg_part, rq.mg, rq.mg_want, n, d.chunk);
+  if (rq.k > 0) {
+    d.k = rq.k;
+    d.top_ids = ensure_n<int32_t>(c->rank.top_ids, (size_t)n * rq.k);
+    d.top_scores = ensure_n<float>(c->rank.top_scores, (size_t)n * rq.k);
+  }
   return d;
 }
 
+// the batch's slots as rank rows on the kelpie rows dX, with the call's lists and margins
+// (`ws`: c->rank.slots, or kp_posttrain_rank_f64's c->rank.f64; `sr`: the family's rank64,
+// enc_row_bytes and enc_q)
+inline RankSet upload_slots(kp_ctx* c, RankRowsWs& ws, const kp_batch* bt, const PostReq& rq, const float* dX,
+                            RankSetReq sr = {}) {
+  std::vector<int32_t> trip, po;
+  kp_slot_rows(bt->n_slots, bt->pred, trip, po);
+  sr.k = rq.k;
+  sr.mg = rq.margins;
+  sr.mg_want = rq.margins ? &rq.margins->slots : nullptr;
+  return upload_rank_rows(c, ws, dX, trip, po, bt->filt_off, bt->filt, (size_t)bt->filt_off[bt->n_slots], sr);
+}
+
 // the probes as rank rows on the slots' kelpie rows dX
-inline RankRows upload_probes(kp_ctx* c, const kp_batch* bt, const PostReq& rq, const float* dX,
-                              size_t enc_row_bytes = 0) {
+inline RankSet upload_probes(kp_ctx* c, const kp_batch* bt, const PostReq& rq, const float* dX,
+                             size_t enc_row_bytes = 0) {
   if (rq.n_probes() == 0) return {};
   std::vector<int32_t> trip, po;
   kp_probe_rows(bt->n_slots, rq.probes, trip, po);
-  return upload_rank_rows(c, c->rank.probes, "KP_PROBE_CHUNK", dX, trip, po, rq.probes->filt_off, rq.probes->filt,
-                          (size_t)rq.probes->filt_off[rq.probes->n], enc_row_bytes, rq.margins,
-                          rq.margins ? &rq.margins->probes : nullptr);
+  RankSetReq sr;
+  sr.chunk_env = "KP_PROBE_CHUNK";
+  sr.enc_row_bytes = enc_row_bytes;
+  sr.mg = rq.margins;
+  sr.mg_want = rq.margins ? &rq.margins->probes : nullptr;
+  return upload_rank_rows(c, c->rank.probes, dX, trip, po, rq.probes->filt_off, rq.probes->filt,
+                          (size_t)rq.probes->filt_off[rq.probes->n], sr);
 }
 
-// rank a set of rows, chunk by chunk: `queries(d, r0, m)` enqueues the model's probe form of
-// its query kernel for the rows [r0, r0 + m) (their fp64 rows, target and kelpie column scores
-// into d.q / d.t / d.kcol), then the slots' own count runs over those rows (k = 0)
+// rank a set of rows, chunk by chunk: `queries(d, r0, m)` enqueues the family's query kernel
+// for the rows [r0, r0 + m) (their fp64 rows, target and kelpie column scores into d.q / d.t /
+// d.kcol), then the count runs over those rows
 template <class F>
-inline void rank_rows(kp_ctx* c, const RankRows& d, int act, F&& queries) {
+inline void rank_rows(kp_ctx* c, const RankSet& d, int act, F&& queries) {
   for (int r0 = 0; r0 < d.n; r0 += d.chunk) {
     const int m = std::min(d.chunk, d.n - r0);
     queries(d, r0, m);
-    const MarginDev mg = d.mg.cap > 0 ? d.mg.at((size_t)r0) : MarginDev{};
-    launch_rank_f64(c, m, d.q, d.t, d.kcol, d.po + r0, d.filt_off + r0, d.filt, d.target + r0, d.rank + r0, act, 0,
-                    nullptr, nullptr, d.bits, d.mg.cap > 0 ? &mg : nullptr);
+    launch_rank_f64(c, d, r0, m, act);
   }
 }
 
@@ -308,7 +278,7 @@ inline void rank_rows(kp_ctx* c, const RankRows& d, int act, F&& queries) {
 struct MarksDev {
   int nm = 0;         // marks per slot (0: no marks)
   float* X = nullptr;
-  RankRows rows;      // n = ns * nm
+  RankSet rows;       // n = ns * nm
   KpMarkPlan plan;
 };
 
@@ -329,8 +299,12 @@ inline MarksDev upload_marks(kp_ctx* c, DevBuf& ws, const kp_hp* hp, const kp_ba
   for (int j = 0; j < nm; ++j)
     KP_HIP(hipMemcpy2DAsync(d.X + (size_t)j * c->dp, sizeof(float) * (size_t)nm * c->dp, dX, sizeof(float) * c->dp,
                             sizeof(float) * c->dp, ns, hipMemcpyDeviceToDevice, c->stream));
-  d.rows = upload_rank_rows(c, c->rank.marks, "KP_MARKS_CHUNK", d.X, trip, po, fo.data(), filt.data(), filt.size(),
-                            enc_row_bytes, rq.margins, rq.margins ? &rq.margins->marks : nullptr);
+  RankSetReq sr;
+  sr.chunk_env = "KP_MARKS_CHUNK";
+  sr.enc_row_bytes = enc_row_bytes;
+  sr.mg = rq.margins;
+  sr.mg_want = rq.margins ? &rq.margins->marks : nullptr;
+  d.rows = upload_rank_rows(c, c->rank.marks, d.X, trip, po, fo.data(), filt.data(), filt.size(), sr);
   return d;
 }
 
@@ -370,8 +344,8 @@ inline bool marks_at_step(const MarksDev& d, int t) {
 // kelpie rows (when out_x is set), the target scores, the ranks, the top-k lists and the
 // probes' results (each when asked for), wait for the stream once, unpad the rows into out_x.
 // Returns the host time at which the wait began (0 unless KP_HOST_TIMES).
-inline double download_results(kp_ctx* c, const kp_batch* bt, const float* dX, const RankDev& r,
-                               std::vector<float>& xp, const PostReq& rq = {}, const RankRows& pd = {},
+inline double download_results(kp_ctx* c, const kp_batch* bt, const float* dX, const RankSet& r,
+                               std::vector<float>& xp, const PostReq& rq = {}, const RankSet& pd = {},
                                const TraceDev& tr = {}, const MarksDev& md = {}) {
   const int ns = bt->n_slots;
   const auto to_host = [c](void* dst, const void* src, size_t bytes) {

@@ -1,6 +1,7 @@
 // kp_probe_check.hpp -- the structural checks of a batch's probes (kp_probes), as one pure
 // host function (no HIP: tests/native/probe_check_driver.cpp builds it alone under the
-// host sanitizers), the probes' expansion into rank rows and the chunking of rank rows.
+// host sanitizers), the slots' and the probes' expansion into rank rows and the chunking of
+// rank rows.
 #pragma once
 
 #include <algorithm>
@@ -43,9 +44,21 @@ inline const char* kp_check_probes(int n_ent, int n_rel2, int n_slots, const kp_
   return nullptr;
 }
 
-// The probes kp_check_probes accepted as rank rows (kp_posttrain.hpp's RankRows): row i is
-// trip[3 i ..] = (slot, p, o) of probe i, po[i] its object.  The probes' filter CSR is already
-// one list per row.
+// A batch's slots as rank rows (kp_common.hpp's RankSet): row s is trip[3 s ..] = (s, p, o) of
+// the slot's ranked triple pred[3 s ..] = (kelpie, p, o), po[s] its object.  The batch's filter
+// CSR is already one list per row.
+inline void kp_slot_rows(int n_slots, const int32_t* pred, std::vector<int32_t>& trip, std::vector<int32_t>& po) {
+  trip.assign((size_t)std::max(0, n_slots) * 3, 0);
+  po.assign((size_t)std::max(0, n_slots), 0);
+  for (int s = 0; s < n_slots; ++s) {
+    trip[3 * (size_t)s] = s;
+    trip[3 * (size_t)s + 1] = pred[3 * (size_t)s + 1];
+    trip[3 * (size_t)s + 2] = po[s] = pred[3 * (size_t)s + 2];
+  }
+}
+
+// The probes kp_check_probes accepted as rank rows: row i is trip[3 i ..] = (slot, p, o) of
+// probe i, po[i] its object.  The probes' filter CSR is already one list per row.
 inline void kp_probe_rows(int n_slots, const kp_probes* p, std::vector<int32_t>& trip, std::vector<int32_t>& po) {
   trip.assign((size_t)p->n * 3, 0);
   po.assign((size_t)p->n, 0);

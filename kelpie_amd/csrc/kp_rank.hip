@@ -1,5 +1,12 @@
 // kp_rank.hip -- all-entity scoring (fp32 MFMA) and the filtered rank of
 // PostTrainingEngine.get_triple_results (post_training_engine.py:101-125).
+// The fp64 rank is one path for every set of rank rows (kp_posttrain.hpp's RankSet: the slots,
+// the probes, the marks, kp_posttrain_rank_f64's slots): launch_rank_f64 ranks a range of a
+// set's rows, with the set's lists and margins when it has them.  Every kernel of it states
+// the per-column fp64 chain (rank64_chain), the count rule (rank64_counts, rank64_own), the
+// filter-bit test (filter_bit) and the conversion to a score (rank64_score) by calling the one
+// definition, so the count, its margin form, the kelpie column and the merges cannot drift
+// apart; RANK64_DISPATCH turns the score kind into the kernels' MODE.
 #include "kp_common.hpp"
 #include "kp_margins_check.hpp"
 
@@ -222,33 +229,62 @@ __global__ __launch_bounds__(256) void kp_rank_filter_bits(int n_slots, int nwor
 __device__ __forceinline__ bool sigmoid_f32_saturated(double x) { return 1.0f / (1.0f + expf(-(float)x)) == 1.0f; }
 __device__ __forceinline__ float sigmoid_f32(double x) { return 1.0f / (1.0f + expf(-(float)x)); }
 
-// kelpie column and target: one thread per slot (counts the kelpie column, writes the
-// fp32 target score)
-// act RANK64_DOT: the scores are the fp64 values (ComplEx); RANK64_SIGMOID: the scores
-// are sigmoid(logit) and the rank compares the monotone logits, with a saturated target
-// (float32 score 1.0) tied by every saturated entity as the reference's fp32 scores tie
-// them (ConvE); RANK64_DIST: a
-// minimizer whose scores are L2 distances and the rank compares their squares (TransE:
-// get_triple_results' minimizer branch, the target counting itself even when filtered);
-// RANK64_DIST1: the same minimizer on L1 distances (TransE norm p = 1)
+// The score kinds (`act`, the kernels' MODE).  RANK64_DOT: the scores are the fp64 values
+// (ComplEx, DistMult); RANK64_SIGMOID: the scores are sigmoid(logit) and the rank compares the
+// monotone logits, with a saturated target (float32 score 1.0) tied by every saturated entity
+// as the reference's fp32 scores tie them (ConvE); RANK64_DIST: a minimizer whose scores are L2
+// distances and the rank compares their squares (TransE: get_triple_results' minimizer branch);
+// RANK64_DIST1: the same minimizer on L1 distances (TransE norm p = 1).
+__device__ __forceinline__ bool rank64_minimizer(int act) { return act == RANK64_DIST || act == RANK64_DIST1; }
+
+// is column e of row s masked by the row's filter list
+__device__ __forceinline__ bool filter_bit(const uint32_t* __restrict__ bits, int nwords, int s, int e) {
+  return (bits[(size_t)s * nwords + (e >> 5)] >> (e & 31)) & 1u;
+}
+
+// The count rule: does an unmasked column of compared value c count against the threshold thr
+// of a row whose target's compared value is ct (the rank: thr = ct; the margins: thr_lo, thr_hi)
+__device__ __forceinline__ bool rank64_counts(int act, double c, double thr, double ct) {
+  if (rank64_minimizer(act)) return c <= thr;
+  return c >= thr || (act == RANK64_SIGMOID && sigmoid_f32_saturated(ct) && sigmoid_f32_saturated(c));
+}
+// `own`: does the target's column count itself, whatever the rounding of its own score (a
+// minimizer's target is restored before the count, a maximizer's filtered target is left out)
+__device__ __forceinline__ bool rank64_own(int act, bool filtered) { return rank64_minimizer(act) || !filtered; }
+
+// a compared value as the score the caller sees
+__device__ __forceinline__ float rank64_score(int act, double v) {
+  return act == RANK64_SIGMOID ? sigmoid_f32(v) : act == RANK64_DIST ? (float)sqrt(v) : (float)v;  // DOT, DIST1
+}
+
+// Host: runs the statements with `MODE` the compile-time constant of the score kind `act`
+#define RANK64_CASE(M, ...)  \
+  case M: {                  \
+    constexpr int MODE = M;  \
+    __VA_ARGS__;             \
+  } break;
+#define RANK64_DISPATCH(act, ...)                                      \
+  switch (act) {                                                       \
+    RANK64_CASE(RANK64_DOT, __VA_ARGS__)                               \
+    RANK64_CASE(RANK64_SIGMOID, __VA_ARGS__)                           \
+    RANK64_CASE(RANK64_DIST, __VA_ARGS__)                              \
+    RANK64_CASE(RANK64_DIST1, __VA_ARGS__)                             \
+    default: throw KpError{KP_EINVAL, "rank: unknown score kind"};     \
+  }
+
+// kelpie column and target: one thread per row (counts the kelpie column, writes the fp32
+// target score).  A minimizer's target counts itself even when filtered.
 __global__ void kp_rank_f64_kelpie(int n_slots, int n_ent, int nwords, const uint32_t* __restrict__ bits,
                                    const int32_t* __restrict__ pred_o, const double* __restrict__ t64,
                                    const double* __restrict__ kcol64, int act, float* __restrict__ target_out,
                                    unsigned long long* __restrict__ rank) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_slots) return;
-  const bool filtered = (bits[(size_t)s * nwords + (n_ent >> 5)] >> (n_ent & 31)) & 1u;
-  if (act == RANK64_DIST || act == RANK64_DIST1)
-    rank[s] = (pred_o[s] == n_ent || (!filtered && kcol64[s] <= t64[s])) ? 1ull : 0ull;
-  else if (act == RANK64_SIGMOID)
-    rank[s] = (!filtered && (kcol64[s] >= t64[s] || (sigmoid_f32_saturated(t64[s]) && sigmoid_f32_saturated(kcol64[s]))))
-                  ? 1ull
-                  : 0ull;
-  else
-    rank[s] = (!filtered && kcol64[s] >= t64[s]) ? 1ull : 0ull;
-  target_out[s] = act == RANK64_SIGMOID ? sigmoid_f32(t64[s])
-                  : act == RANK64_DIST  ? (float)sqrt(t64[s])
-                                        : (float)t64[s];  // DOT, DIST1
+  const bool filtered = filter_bit(bits, nwords, s, n_ent);
+  rank[s] = ((rank64_minimizer(act) && pred_o[s] == n_ent) || (!filtered && rank64_counts(act, kcol64[s], t64[s], t64[s])))
+                ? 1ull
+                : 0ull;
+  target_out[s] = rank64_score(act, t64[s]);
 }
 
 // ----------------------------------------------------------------------------
@@ -290,6 +326,38 @@ struct TopkArgs<true> {
   int32_t* cand_col;
 };
 
+// The per-column fp64 chain: v[j] for the rows s0 + j, j < ns, of this thread's column e of
+// E^T, one sequential chain over d per (row, column).  The rows q [ns][dp] are wave-uniform
+// (scalar loads).  The count and its margin form both call this, so with tol = 0 the margins'
+// band is the rank bit for bit.  (Returned by value: accumulators handed over by reference
+// cost both kernels registers, 72 against 45 and 59.)
+struct Rank64Acc {
+  double v[RQ];
+};
+template <int MODE>
+__device__ __forceinline__ Rank64Acc rank64_chain(const double* __restrict__ q, int dp, int ns,
+                                                  const float* __restrict__ ET, int ldt, int e) {
+  Rank64Acc acc;
+#pragma unroll
+  for (int j = 0; j < RQ; ++j) acc.v[j] = 0.0;
+  for (int d = 0; d < dp; ++d) {
+    const double v = (double)ET[(size_t)d * ldt + e];
+#pragma unroll
+    for (int j = 0; j < RQ; ++j)
+      if (j < ns) {
+        if constexpr (MODE == RANK64_DIST) {
+          const double df = q[(size_t)j * dp + d] - v;  // exact: fp32 operands, fp64 difference
+          acc.v[j] = __fma_rn(df, df, acc.v[j]);
+        } else if constexpr (MODE == RANK64_DIST1) {
+          acc.v[j] += fabs(q[(size_t)j * dp + d] - v);
+        } else {
+          acc.v[j] = __fma_rn(q[(size_t)j * dp + d], v, acc.v[j]);
+        }
+      }
+  }
+  return acc;
+}
+
 template <int MODE, bool TOPK = false>
 __global__ __launch_bounds__(256) void kp_rank_f64_count(int n_slots, int n_ent, int dp, const double* __restrict__ Q,
                                                          const double* __restrict__ t64,
@@ -300,42 +368,16 @@ __global__ __launch_bounds__(256) void kp_rank_f64_count(int n_slots, int n_ent,
   const int s0 = blockIdx.y * RQ;
   const int e = blockIdx.x * 256 + threadIdx.x;  // < ldt: ET is zero-padded
   const int ns = min(RQ, n_slots - s0);
-  double acc[RQ];
-#pragma unroll
-  for (int j = 0; j < RQ; ++j) acc[j] = 0.0;
-  // the slot rows are wave-uniform: scalar loads, one fp64 FMA chain over d per (slot, entity)
-  const double* q = Q + (size_t)s0 * dp;
-  for (int d = 0; d < dp; ++d) {
-    const double v = (double)ET[(size_t)d * ldt + e];
-#pragma unroll
-    for (int j = 0; j < RQ; ++j)
-      if (j < ns) {
-        if constexpr (MODE == RANK64_DIST) {
-          const double df = q[(size_t)j * dp + d] - v;  // exact: fp32 operands, fp64 difference
-          acc[j] = __fma_rn(df, df, acc[j]);
-        } else if constexpr (MODE == RANK64_DIST1) {
-          acc[j] += fabs(q[(size_t)j * dp + d] - v);
-        } else {
-          acc[j] = __fma_rn(q[(size_t)j * dp + d], v, acc[j]);
-        }
-      }
-  }
+  const Rank64Acc chain = rank64_chain<MODE>(Q + (size_t)s0 * dp, dp, ns, ET, ldt, e);
+  const double(&acc)[RQ] = chain.v;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int j = 0; j < RQ; ++j) {
     int hit = 0;
     if (j < ns && e < n_ent) {
       const int s = s0 + j;
-      const bool filtered = (bits[(size_t)s * nwords + (e >> 5)] >> (e & 31)) & 1u;
-      // the target counts itself whatever the rounding of its own score (a maximizer's
-      // only if unfiltered: its filtered score is set back after the count)
-      if constexpr (MODE == RANK64_DIST || MODE == RANK64_DIST1)
-        hit = e == pred_o[s] || (!filtered && acc[j] <= t64[s]);
-      else if constexpr (MODE == RANK64_SIGMOID)
-        hit = !filtered && (e == pred_o[s] || acc[j] >= t64[s] ||
-                            (sigmoid_f32_saturated(t64[s]) && sigmoid_f32_saturated(acc[j])));
-      else
-        hit = !filtered && (e == pred_o[s] || acc[j] >= t64[s]);
+      const bool filtered = filter_bit(bits, nwords, s, e);
+      hit = e == pred_o[s] ? rank64_own(MODE, filtered) : !filtered && rank64_counts(MODE, acc[j], t64[s], t64[s]);
     }
     for (int o = 32; o > 0; o >>= 1) hit += __shfl_xor(hit, o, 64);
     if (lane == 0) part[w][j] = hit;
@@ -347,7 +389,7 @@ __global__ __launch_bounds__(256) void kp_rank_f64_count(int n_slots, int n_ent,
     if (tot) atomicAdd(&rank[s0 + j], (unsigned long long)tot);
   }
   if constexpr (TOPK) {
-    constexpr bool MINI = MODE == RANK64_DIST || MODE == RANK64_DIST1;
+    constexpr bool MINI = MODE == RANK64_DIST || MODE == RANK64_DIST1;  // rank64_minimizer(MODE)
     const size_t lists = (size_t)4 * gridDim.x;
 #pragma unroll
     for (int j = 0; j < RQ; ++j) {
@@ -356,7 +398,7 @@ __global__ __launch_bounds__(256) void kp_rank_f64_count(int n_slots, int n_ent,
         unsigned long long key = ~0ull;
         uint32_t col = 0xffffffffu;
         if (e < n_ent) {
-          const bool filtered = (bits[(size_t)s * nwords + (e >> 5)] >> (e & 31)) & 1u;
+          const bool filtered = filter_bit(bits, nwords, s, e);
           const bool is_o = e == pred_o[s];
           if (!filtered || (MINI && is_o)) {  // a minimizer's filtered target is restored
             key = topk_key(is_o ? t64[s] : acc[j], MINI);
@@ -426,7 +468,7 @@ __global__ __launch_bounds__(256) void kp_rank_topk_merge(int n_ent, int nwords,
   __shared__ unsigned long long lk[TOPK_MAX * TOPK_MAX];  // their entries
   __shared__ uint32_t lc[TOPK_MAX * TOPK_MAX];
   const int s = blockIdx.x, tid = threadIdx.x;
-  const bool mini = act == RANK64_DIST || act == RANK64_DIST1;
+  const bool mini = rank64_minimizer(act);
   const unsigned long long* ck = cand_key + (size_t)s * lists * k;
   const int32_t* cc = cand_col + (size_t)s * lists * k;
   // phase 1: the k best heads
@@ -453,7 +495,7 @@ __global__ __launch_bounds__(256) void kp_rank_topk_merge(int n_ent, int nwords,
     lk[i] = l < 0 ? ~0ull : ck[(size_t)l * k + i % k];
     lc[i] = l < 0 ? 0xffffffffu : (uint32_t)cc[(size_t)l * k + i % k];
   }
-  const bool kfilt = (bits[(size_t)s * nwords + (n_ent >> 5)] >> (n_ent & 31)) & 1u;
+  const bool kfilt = filter_bit(bits, nwords, s, n_ent);
   const bool k_is_o = pred_o[s] == n_ent;
   const bool k_in = !kfilt || (mini && k_is_o);
   const unsigned long long kk = k_in ? topk_key(k_is_o ? t64[s] : kcol64[s], mini) : ~0ull;
@@ -470,13 +512,8 @@ __global__ __launch_bounds__(256) void kp_rank_topk_merge(int n_ent, int nwords,
     }
     topk_block_min(bk, bc, bp, sk, sc, sp);
     if (tid == 0) {
-      float sc32 = 0.f;
-      if (bc != 0xffffffffu) {
-        const double v = topk_value(bk, mini);
-        sc32 = act == RANK64_SIGMOID ? sigmoid_f32(v) : act == RANK64_DIST ? (float)sqrt(v) : (float)v;
-      }
       out_ids[(size_t)s * k + r] = (int32_t)bc;
-      out_scores[(size_t)s * k + r] = sc32;
+      out_scores[(size_t)s * k + r] = bc != 0xffffffffu ? rank64_score(act, topk_value(bk, mini)) : 0.f;
     }
     last_k = bk, last_c = bc;
   }
@@ -511,12 +548,11 @@ __global__ void kp_rank_margin_thr(int n, int act, const double* __restrict__ t6
 // worse than the target, its candidate pair for that side (written over what the caller
 // passed: a caller that holds a candidate already merges by topk_before)
 __device__ __forceinline__ int margin_column(int act, double c, uint32_t e, double ct, double thr_lo, double thr_hi,
-                                             bool t_sat, unsigned long long& bk, uint32_t& bc,
-                                             unsigned long long& wk, uint32_t& wc) {
-  const bool mini = act == RANK64_DIST || act == RANK64_DIST1;
-  bool lo = mini ? c <= thr_lo : c >= thr_lo;
-  bool hi = mini ? c <= thr_hi : c >= thr_hi;
-  if (act == RANK64_SIGMOID && t_sat && sigmoid_f32_saturated(c)) lo = hi = true;
+                                             unsigned long long& bk, uint32_t& bc, unsigned long long& wk,
+                                             uint32_t& wc) {
+  const bool mini = rank64_minimizer(act);
+  const bool lo = rank64_counts(act, c, thr_lo, ct);
+  const bool hi = rank64_counts(act, c, thr_hi, ct);
   const unsigned long long k = topk_key(c, mini);
   if (mini ? c < ct : c > ct) bk = ~k, bc = e;
   if (mini ? c > ct : c < ct) wk = k, wc = e;
@@ -548,26 +584,8 @@ __global__ __launch_bounds__(256) void kp_rank_f64_margin(int n_slots, int n_ent
   const int s0 = blockIdx.y * RQ;
   const int e = blockIdx.x * 256 + threadIdx.x;  // < ldt: ET is zero-padded
   const int ns = min(RQ, n_slots - s0);
-  double acc[RQ];
-#pragma unroll
-  for (int j = 0; j < RQ; ++j) acc[j] = 0.0;
-  // kp_rank_f64_count's chain, operation for operation: the same c_e
-  const double* q = Q + (size_t)s0 * dp;
-  for (int d = 0; d < dp; ++d) {
-    const double v = (double)ET[(size_t)d * ldt + e];
-#pragma unroll
-    for (int j = 0; j < RQ; ++j)
-      if (j < ns) {
-        if constexpr (MODE == RANK64_DIST) {
-          const double df = q[(size_t)j * dp + d] - v;
-          acc[j] = __fma_rn(df, df, acc[j]);
-        } else if constexpr (MODE == RANK64_DIST1) {
-          acc[j] += fabs(q[(size_t)j * dp + d] - v);
-        } else {
-          acc[j] = __fma_rn(q[(size_t)j * dp + d], v, acc[j]);
-        }
-      }
-  }
+  const Rank64Acc chain = rank64_chain<MODE>(Q + (size_t)s0 * dp, dp, ns, ET, ldt, e);
+  const double(&acc)[RQ] = chain.v;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int j = 0; j < RQ; ++j) {
@@ -577,12 +595,8 @@ __global__ __launch_bounds__(256) void kp_rank_f64_margin(int n_slots, int n_ent
       unsigned long long bk = ~0ull, wk = ~0ull;
       uint32_t bc = MG_NONE, wc = MG_NONE;
       if (e < n_ent && e != pred_o[s]) {
-        const bool filtered = (bits[(size_t)s * nwords + (e >> 5)] >> (e & 31)) & 1u;
-        if (!filtered) {
-          const double ct = t64[s];
-          const bool t_sat = MODE == RANK64_SIGMOID && sigmoid_f32_saturated(ct);
-          cnt = margin_column(MODE, acc[j], (uint32_t)e, ct, thr[2 * s], thr[2 * s + 1], t_sat, bk, bc, wk, wc);
-        }
+        if (!filter_bit(bits, nwords, s, e))
+          cnt = margin_column(MODE, acc[j], (uint32_t)e, t64[s], thr[2 * s], thr[2 * s + 1], bk, bc, wk, wc);
       }
       for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);  // three fields of at most 64 each
       margin_wave_min(bk, bc);
@@ -627,7 +641,7 @@ __global__ __launch_bounds__(64) void kp_rank_margin_merge(int n_ent, int nwords
                                                            const int32_t* __restrict__ pcol,
                                                            const int32_t* __restrict__ pcnt, MarginDev out) {
   const int s = blockIdx.x, lane = threadIdx.x;
-  const bool mini = act == RANK64_DIST || act == RANK64_DIST1;
+  const bool mini = rank64_minimizer(act);
   long long lo = 0, hi = 0, ties = 0;
   unsigned long long bk = ~0ull, wk = ~0ull;
   uint32_t bc = MG_NONE, wc = MG_NONE;
@@ -641,21 +655,16 @@ __global__ __launch_bounds__(64) void kp_rank_margin_merge(int n_ent, int nwords
   const double ct = t64[s];
   const int o = pred_o[s];
   if (lane == 0) {
-    const bool kfilt = (bits[(size_t)s * nwords + (n_ent >> 5)] >> (n_ent & 31)) & 1u;
-    if (o != n_ent && !kfilt) {  // the kelpie column, unless it is the target or masked
-      const bool t_sat = act == RANK64_SIGMOID && sigmoid_f32_saturated(ct);
+    if (o != n_ent && !filter_bit(bits, nwords, s, n_ent)) {  // the kelpie column, unless it is the target or masked
       unsigned long long kbk = ~0ull, kwk = ~0ull;
       uint32_t kbc = MG_NONE, kwc = MG_NONE;
       const int cnt =
-          margin_column(act, kcol64[s], (uint32_t)n_ent, ct, thr[2 * s], thr[2 * s + 1], t_sat, kbk, kbc, kwk, kwc);
+          margin_column(act, kcol64[s], (uint32_t)n_ent, ct, thr[2 * s], thr[2 * s + 1], kbk, kbc, kwk, kwc);
       lo += cnt & 0xff, hi += (cnt >> 8) & 0xff, ties += cnt >> 16;
       if (topk_before(kbk, kbc, bk, bc)) bk = kbk, bc = kbc;  // one more candidate of this lane's
       if (topk_before(kwk, kwc, wk, wc)) wk = kwk, wc = kwc;
     }
-    // own: what the rank counts for the target column itself (a minimizer's target is restored
-    // before the count, a maximizer's filtered target is left out)
-    const bool ofilt = (bits[(size_t)s * nwords + (o >> 5)] >> (o & 31)) & 1u;
-    const int own = (mini || !ofilt) ? 1 : 0;
+    const int own = rank64_own(act, filter_bit(bits, nwords, s, o)) ? 1 : 0;  // the target column itself
     lo += own, hi += own;
   }
   for (int d = 32; d > 0; d >>= 1) {
@@ -676,42 +685,18 @@ __global__ __launch_bounds__(64) void kp_rank_margin_merge(int n_ent, int nwords
     out.gap_worse[s] = wc == MG_NONE ? (double)INFINITY : fabs(kp_margin_units(act, topk_value(wk, mini)) - vt);
 }
 
-// the margins of n rows whose filter bitmaps, targets and kelpie column scores the rows' own
-// rank has just read
-static void launch_margins(kp_ctx* c, int n, const double* d_q64, const double* d_t64, const double* d_kcol64,
-                           const int32_t* d_pred_o, const uint32_t* bits, int nwords, int ldt, int act,
-                           const MarginDev& mg) {
-  const int nblk = ldt / 256;
-  KP_REQUIRE(n <= mg.cap && nblk == mg.nblk, "margins: the workspace does not hold this launch");
-  hipLaunchKernelGGL(kp_rank_margin_thr, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, act, d_t64, mg.tol, mg.thr);
-  KP_HIP(hipGetLastError());
-  const dim3 grid(nblk, (n + RQ - 1) / RQ);
-#define KP_MARGIN_LAUNCH(MODE)                                                                                  \
-  hipLaunchKernelGGL(kp_rank_f64_margin<MODE>, grid, dim3(256), 0, c->stream, n, c->n_ent, c->dp, d_q64, d_t64, \
-                     d_pred_o, c->eT.as<float>(), ldt, nwords, bits, mg.thr, mg.pkey, mg.pcol, mg.pcnt)
-  if (act == RANK64_DIST)
-    KP_MARGIN_LAUNCH(RANK64_DIST);
-  else if (act == RANK64_DIST1)
-    KP_MARGIN_LAUNCH(RANK64_DIST1);
-  else if (act == RANK64_SIGMOID)
-    KP_MARGIN_LAUNCH(RANK64_SIGMOID);
-  else
-    KP_MARGIN_LAUNCH(RANK64_DOT);
-#undef KP_MARGIN_LAUNCH
-  KP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kp_rank_margin_merge, dim3(n), dim3(64), 0, c->stream, c->n_ent, nwords, nblk, act, bits, d_pred_o,
-                     d_t64, d_kcol64, mg.thr, mg.pkey, mg.pcol, mg.pcnt, mg);
-  KP_HIP(hipGetLastError());
-}
-
 // bytes of candidate workspace a launch may hold: the slots run in chunks of whole slot rows
 constexpr size_t TOPK_WS_BYTES = (size_t)64 << 20;
 
-void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* d_t64, const double* d_kcol64,
-                     const int32_t* d_pred_o, const int32_t* d_filt_off, const int32_t* d_filt, float* d_target,
-                     int64_t* d_rank, int act, int topk, int32_t* d_top_ids, float* d_top_scores, DevBuf* bits_buf,
-                     const MarginDev* mg) {
-  if (n_slots <= 0) return;
+// Rank the rows [r0, r0 + m) of a set (m <= d.chunk; their fp64 rows, target and kelpie column
+// scores are in d.q / d.t / d.kcol): the filter bitmaps, the kelpie column and the target
+// scores, the rows' margins when the set has them (three launches, none with an atomic: the
+// thresholds, the margin form of the count, the merge of its per-workgroup partials), then the
+// count -- with the set's lists (d.k > 0, the whole set at once) in chunks of whole workgroup
+// rows that keep the waves' candidate lists within TOPK_WS_BYTES, each followed by its merge.
+void launch_rank_f64(kp_ctx* c, const RankSet& d, int r0, int m, int act) {
+  if (m <= 0) return;
+  KP_REQUIRE(m <= d.chunk && (d.k == 0 || (r0 == 0 && m == d.n)), "rank: the set does not hold this launch");
   const int ldt = (c->n_ent + 255) / 256 * 256;
   if (!c->eT_ready) {
     float* ET = ensure_n<float>(c->eT, (size_t)c->dp * ldt);
@@ -720,67 +705,57 @@ void launch_rank_f64(kp_ctx* c, int n_slots, const double* d_q64, const double* 
     KP_HIP(hipGetLastError());
     c->eT_ready = true;
   }
+  const float* ET = c->eT.as<float>();
   const int n_cols = c->n_ent + 1;
   const int nwords = (n_cols + 31) / 32;
-  DevBuf& bb = bits_buf ? *bits_buf : c->rank.bits;
-  uint32_t* bits = ensure_n<uint32_t>(bb, (size_t)n_slots * nwords);
-  unsigned long long* rank = reinterpret_cast<unsigned long long*>(d_rank);
-  hipLaunchKernelGGL(kp_rank_filter_bits, dim3(n_slots), dim3(256), 0, c->stream, n_slots, nwords, d_filt_off, d_filt,
-                     n_cols, bits);
+  const int32_t* po = d.po + r0;
+  unsigned long long* rank = reinterpret_cast<unsigned long long*>(d.rank + r0);
+  hipLaunchKernelGGL(kp_rank_filter_bits, dim3(m), dim3(256), 0, c->stream, m, nwords, d.filt_off + r0, d.filt, n_cols,
+                     d.bits);
   KP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kp_rank_f64_kelpie, dim3((n_slots + 63) / 64), dim3(64), 0, c->stream, n_slots, c->n_ent, nwords,
-                     bits, d_pred_o, d_t64, d_kcol64, act, d_target, rank);
+  hipLaunchKernelGGL(kp_rank_f64_kelpie, dim3((m + 63) / 64), dim3(64), 0, c->stream, m, c->n_ent, nwords, d.bits, po,
+                     d.t, d.kcol, act, d.target + r0, rank);
   KP_HIP(hipGetLastError());
-  if (mg) launch_margins(c, n_slots, d_q64, d_t64, d_kcol64, d_pred_o, bits, nwords, ldt, act, *mg);
-  if (topk > 0) {
-    // every wave of the scoring grid leaves a list of k candidates per slot (12 bytes each):
-    // the slots run in chunks of whole slot rows that keep the lists within TOPK_WS_BYTES
-    const int lists = 4 * (ldt / 256);
-    const size_t per_slot = (size_t)lists * topk;  // candidates
-    const int rows_fit = (int)std::max<size_t>(1, TOPK_WS_BYTES / (per_slot * 12 * RQ));
-    const int chunk = std::min(n_slots, rows_fit * RQ);
-    unsigned long long* ck =
-        reinterpret_cast<unsigned long long*>(c->rank.cand_key.ensure(sizeof(unsigned long long) * per_slot * chunk));
-    int32_t* cc = ensure_n<int32_t>(c->rank.cand_col, per_slot * chunk);
-    for (int s0 = 0; s0 < n_slots; s0 += chunk) {
-      const int m = std::min(chunk, n_slots - s0);
-      const dim3 grid(ldt / 256, (m + RQ - 1) / RQ);
-      const double* q = d_q64 + (size_t)s0 * c->dp;
-      const uint32_t* b = bits + (size_t)s0 * nwords;
-#define KP_TOPK_LAUNCH(MODE)                                                                                       \
-  hipLaunchKernelGGL((kp_rank_f64_count<MODE, true>), grid, dim3(256), 0, c->stream, m, c->n_ent, c->dp, q,        \
-                     d_t64 + s0, d_pred_o + s0, c->eT.as<float>(), ldt, nwords, b, rank + s0, TopkArgs<true>{topk, ck, cc})
-      if (act == RANK64_DIST)
-        KP_TOPK_LAUNCH(RANK64_DIST);
-      else if (act == RANK64_DIST1)
-        KP_TOPK_LAUNCH(RANK64_DIST1);
-      else if (act == RANK64_SIGMOID)
-        KP_TOPK_LAUNCH(RANK64_SIGMOID);
-      else
-        KP_TOPK_LAUNCH(RANK64_DOT);
-#undef KP_TOPK_LAUNCH
-      KP_HIP(hipGetLastError());
-      hipLaunchKernelGGL(kp_rank_topk_merge, dim3(m), dim3(256), 0, c->stream, c->n_ent, nwords, lists, topk, act, ck,
-                         cc, b, d_pred_o + s0, d_t64 + s0, d_kcol64 + s0, d_top_ids + (size_t)s0 * topk,
-                         d_top_scores + (size_t)s0 * topk);
-      KP_HIP(hipGetLastError());
-    }
+  if (d.mg.cap > 0) {
+    const MarginDev mg = d.mg.at((size_t)r0);
+    const int nblk = ldt / 256;
+    KP_REQUIRE(m <= mg.cap && nblk == mg.nblk, "margins: the workspace does not hold this launch");
+    hipLaunchKernelGGL(kp_rank_margin_thr, dim3((m + 63) / 64), dim3(64), 0, c->stream, m, act, d.t, mg.tol, mg.thr);
+    KP_HIP(hipGetLastError());
+    RANK64_DISPATCH(act, hipLaunchKernelGGL(kp_rank_f64_margin<MODE>, dim3(nblk, (m + RQ - 1) / RQ), dim3(256), 0,
+                                            c->stream, m, c->n_ent, c->dp, d.q, d.t, po, ET, ldt, nwords, d.bits,
+                                            mg.thr, mg.pkey, mg.pcol, mg.pcnt));
+    KP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kp_rank_margin_merge, dim3(m), dim3(64), 0, c->stream, c->n_ent, nwords, nblk, act, d.bits, po,
+                       d.t, d.kcol, mg.thr, mg.pkey, mg.pcol, mg.pcnt, mg);
+    KP_HIP(hipGetLastError());
+  }
+  if (d.k == 0) {
+    RANK64_DISPATCH(act, hipLaunchKernelGGL(kp_rank_f64_count<MODE>, dim3(ldt / 256, (m + RQ - 1) / RQ), dim3(256), 0,
+                                            c->stream, m, c->n_ent, c->dp, d.q, d.t, po, ET, ldt, nwords, d.bits, rank,
+                                            TopkArgs<false>{}));
+    KP_HIP(hipGetLastError());
     return;
   }
-  const dim3 grid(ldt / 256, (n_slots + RQ - 1) / RQ);
-  if (act == RANK64_DIST)
-    hipLaunchKernelGGL(kp_rank_f64_count<RANK64_DIST>, grid, dim3(256), 0, c->stream, n_slots, c->n_ent, c->dp, d_q64,
-                       d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank, TopkArgs<false>{});
-  else if (act == RANK64_DIST1)
-    hipLaunchKernelGGL(kp_rank_f64_count<RANK64_DIST1>, grid, dim3(256), 0, c->stream, n_slots, c->n_ent, c->dp, d_q64,
-                       d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank, TopkArgs<false>{});
-  else if (act == RANK64_SIGMOID)
-    hipLaunchKernelGGL(kp_rank_f64_count<RANK64_SIGMOID>, grid, dim3(256), 0, c->stream, n_slots, c->n_ent, c->dp,
-                       d_q64, d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank, TopkArgs<false>{});
-  else
-    hipLaunchKernelGGL(kp_rank_f64_count<RANK64_DOT>, grid, dim3(256), 0, c->stream, n_slots, c->n_ent, c->dp, d_q64,
-                       d_t64, d_pred_o, c->eT.as<float>(), ldt, nwords, bits, rank, TopkArgs<false>{});
-  KP_HIP(hipGetLastError());
+  // every wave of the scoring grid leaves a list of k candidates per slot (12 bytes each)
+  const int lists = 4 * (ldt / 256);
+  const size_t per_slot = (size_t)lists * d.k;  // candidates
+  const int rows_fit = (int)std::max<size_t>(1, TOPK_WS_BYTES / (per_slot * 12 * RQ));
+  const int chunk = std::min(m, rows_fit * RQ);
+  unsigned long long* ck = ensure_n<unsigned long long>(c->rank.cand_key, per_slot * chunk);
+  int32_t* cc = ensure_n<int32_t>(c->rank.cand_col, per_slot * chunk);
+  for (int s0 = 0; s0 < m; s0 += chunk) {
+    const int ms = std::min(chunk, m - s0);
+    const uint32_t* b = d.bits + (size_t)s0 * nwords;
+    RANK64_DISPATCH(act, hipLaunchKernelGGL((kp_rank_f64_count<MODE, true>), dim3(ldt / 256, (ms + RQ - 1) / RQ),
+                                            dim3(256), 0, c->stream, ms, c->n_ent, c->dp, d.q + (size_t)s0 * c->dp,
+                                            d.t + s0, po + s0, ET, ldt, nwords, b, rank + s0,
+                                            TopkArgs<true>{d.k, ck, cc}));
+    KP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kp_rank_topk_merge, dim3(ms), dim3(256), 0, c->stream, c->n_ent, nwords, lists, d.k, act, ck, cc,
+                       b, po + s0, d.t + s0, d.kcol + s0, d.top_ids + (size_t)s0 * d.k, d.top_scores + (size_t)s0 * d.k);
+    KP_HIP(hipGetLastError());
+  }
 }
 
 void launch_gemm_abt(kp_ctx* c, const float* A, int lda, int M, const float* B, int ldb, int N, int K, float* out,

@@ -597,16 +597,15 @@ void launch_te_scores(kp_ctx* c, int nq, const int32_t* dh, const int32_t* dr, c
 // chain over d, the order
 // kp_rank_f64_count scores every entity in.  An fp32 norm over 200 terms is ~1e-7
 // relative off, enough to swap near-tied entities (FB15k-237 necessary fixtures).
-// PROBE (kp_posttrain_rank_probes): row s is a probe, pred its (slot, p, o), and x the
-// kelpie row of that slot instead of row s; every operation and its order are the slot form's
-template <bool PROBE = false>
+// Row s of a set of rank rows is pred[3 s ..] = (row, p, o): x is row `row` of X (the slots: s
+// itself; a probe: its slot's kelpie row; a mark row: its row of the mark workspace).
 __global__ void kp_te_rankq64(const float* __restrict__ X, const float* __restrict__ R,
                               const float* __restrict__ E, int n_ent, int dp, const int32_t* __restrict__ pred,
                               int n_slots, double* __restrict__ Q, double* __restrict__ t64,
                               double* __restrict__ kcol64, int l1) {
   const int s = blockIdx.x;
   if (s >= n_slots) return;
-  const float* x = X + (size_t)(PROBE ? pred[3 * s] : s) * dp;
+  const float* x = X + (size_t)pred[3 * s] * dp;
   const float* r = R + (size_t)pred[3 * s + 1] * dp;
   double* q = Q + (size_t)s * dp;
   for (int d = threadIdx.x; d < dp; d += blockDim.x) q[d] = (double)x[d] + (double)r[d];
@@ -670,7 +669,7 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   } else {
     dRng = upload(c, c->te.rng, bt->rng, (size_t)std::max<int64_t>(1, nrng));
   }
-  const RankRows pd = upload_probes(c, bt, rq, dX);
+  const RankSet pd = upload_probes(c, bt, rq, dX);
   // kp_posttrain_rank_marks: the mark rows (each the padded x0 until its epoch ends) and the epochs
   const MarksDev md = upload_marks(c, c->te.marks, hp, bt, rq, dX);
   TeMarkArgs<true> mkd{nullptr};
@@ -765,24 +764,17 @@ void transe_posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const
   for (int s = 0; s < ns; ++s) rels[s] = bt->pred[3 * s + 1];
   int32_t* dH = upload(c, c->te.heads, heads.data(), heads.size());
   int32_t* dRl = upload(c, c->te.rels, rels.data(), rels.size());
-  const RankDev rk = upload_rank_inputs(c, bt, rq);
+  RankSetReq sr;
+  sr.rank64 = c->te_rank64 != 0;
+  const RankSet rk = upload_slots(c, c->rank.slots, bt, rq, dX, sr);
   if (c->te_rank64) {
-    int32_t* dPred = upload(c, c->rank.pred, bt->pred, (size_t)ns * 3);
-    const Rank64Dev r64 = rank64_buffers(c, ns);
-    hipLaunchKernelGGL(kp_te_rankq64<false>, dim3(ns), dim3(64), 0, c->stream, dX, c->dR, c->dE, c->n_ent, DP, dPred,
-                       ns, r64.q, r64.t, r64.kcol, l1 ? 1 : 0);
-    KP_HIP(hipGetLastError());
-    launch_rank_f64(c, ns, r64.q, r64.t, r64.kcol, rk.po, rk.filt_off, rk.filt, rk.target, rk.rank,
-                    l1 ? RANK64_DIST1 : RANK64_DIST, rq.k, rk.top_ids, rk.top_scores, nullptr, rk.margins());
-    // the probes on the slots' rows, then the marks on the mark workspace: the probe form
-    // reads row trip[3 r] of the set's rows instead of row r
-    const auto probe_queries = [c, DP, l1](const RankRows& rr, int r0, int m) {
-      hipLaunchKernelGGL(kp_te_rankq64<true>, dim3(m), dim3(64), 0, c->stream, rr.X, c->dR, c->dE, c->n_ent, DP,
-                         rr.trip + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol, l1 ? 1 : 0);
+    // the slots, then the probes on the slots' rows, then the marks on the mark workspace
+    const auto queries = [c, DP, l1](const RankSet& rr, int r0, int m) {
+      hipLaunchKernelGGL(kp_te_rankq64, dim3(m), dim3(64), 0, c->stream, rr.X, c->dR, c->dE, c->n_ent, DP,
+                         rr.rows + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol, l1 ? 1 : 0);
       KP_HIP(hipGetLastError());
     };
-    rank_rows(c, pd, l1 ? RANK64_DIST1 : RANK64_DIST, probe_queries);
-    rank_rows(c, md.rows, l1 ? RANK64_DIST1 : RANK64_DIST, probe_queries);
+    for (const RankSet* set : {&rk, &pd, &md.rows}) rank_rows(c, *set, l1 ? RANK64_DIST1 : RANK64_DIST, queries);
   } else {
     float* dScores = ensure_n<float>(c->rank.scores, (size_t)ns * ld);
     launch_te_scores(c, ns, dH, dRl, dX, dScores, ld, c->n_ent);

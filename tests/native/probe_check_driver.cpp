@@ -4,6 +4,7 @@
 //   * a good set of probes passes, with and without probes, with an empty slot;
 //   * errors: the good set with exactly one rule broken must yield that rule's message;
 //   * the probes as rank rows: a slot without probes between two that have some;
+//   * the slots as rank rows: 0, 1 and 3 slots, the kelpie entity among the objects;
 //   * on 400 pseudo-random valid sets the check passes and the chunks cover every probe row
 //     once, within the budget.
 // The arrays are heap vectors of their exact length, so a check that reads past one is
@@ -142,6 +143,27 @@ void rank_rows() {
   if (!trip.empty() || !po.empty()) fail("rows, no probes");
 }
 
+// the slots as rank rows (kp_slot_rows): row s is (s, p, o) of the slot's ranked triple
+// (kelpie, p, o); 0, 1 and 3 slots, the kelpie entity among the objects
+void slot_rows() {
+  struct Case {
+    const char* name;
+    std::vector<int32_t> pred, trip, po;
+  };
+  const Case cases[] = {
+      {"slot rows, no slots", {}, {}, {}},
+      {"slot rows, one slot", {K, 2, K}, {0, 2, K}, {K}},
+      {"slot rows, three slots", {K, 0, 3, K, 3, K, K, 1, 0}, {0, 0, 3, 1, 3, K, 2, 1, 0}, {3, K, 0}},
+  };
+  for (const Case& c : cases) {
+    std::vector<int32_t> trip{99, 99}, po{99};  // stale contents must go
+    kp_slot_rows((int)c.po.size(), c.pred.data(), trip, po);
+    const bool ok = trip == c.trip && po == c.po;
+    std::printf("%s: %s\n", c.name, ok ? "ok" : "wrong rows");
+    if (!ok) fail(c.name);
+  }
+}
+
 uint32_t rnd_state = 12345u;
 int rnd(int n) {  // [0, n)
   rnd_state = rnd_state * 1664525u + 1013904223u;
@@ -190,6 +212,7 @@ void random_sets() {
 int main() {
   errors();
   rank_rows();
+  slot_rows();
   random_sets();
   std::printf("%d failures\n", failures);
   return failures ? 1 : 0;

@@ -7,7 +7,13 @@ engine and context: a batch of 2 candidates, then one of 12 (every per-slot buff
 regrows: 12 + 1 slots is more than the 25 % headroom over 2 + 1), then the first 2
 again.  The third result must equal the first bit for bit, and the middle one must equal
 the same 12 candidates on a fresh context.  D = 200 for ComplEx and ConvE (the bf16x3
-attention, the fused ConvE encoder), D = 32 for TransE; 3 epochs."""
+attention, the fused ConvE encoder), D = 32 for TransE; 3 epochs.
+
+The rank's four sets of rows (the slots, the probes, the marks, the fp64 call's slots) share one
+workspace type, so the same sequence runs once more with every request on -- the lists, two
+probes, the trace, two marks and the margins -- at the narrowest widths that still reach every
+buffer (ComplEx rows of 32 floats, TransE d = 16, ConvE d = 60), and every reported value has
+to come back."""
 import pytest
 
 from golden_io import seed_all
@@ -66,5 +72,54 @@ def test_workspaces_survive_regrowth(name):
     fresh = _run(ka.NecessaryPostTrainingEngine(_model(name, ds, w), ds, HP[name]), pred, cands)
 
     assert len(first[1]) == 2 and len(middle[1]) == 12
+    assert again == first, (first, again)
+    assert middle == fresh, (middle, fresh)
+
+
+DIM_NARROW = {"ComplEx": 16, "TransE": 16, "ConvE": 60}  # ComplEx: rows of 2 * 16 floats
+
+
+def _extras_engine(name, ds, w):
+    eng = ka.NecessaryPostTrainingEngine(_model(name, ds, w), ds, HP[name])
+    eng.top_k = 3
+    eng.trace = True
+    eng.marks = [1, 3]
+    eng.margin_tol = 1e-4
+    return eng
+
+
+def _run_extras(eng, pred, cands, probes):
+    """One batch from a cleared cache and fixed seeds with every request on: the reports and the
+    whole (post-trained, base) results -- score, rank, lists, probes, loss, marks, margins."""
+    seed_all(42)
+    eng.set_cache()
+    reports = eng.compute_side_effects(pred, [[c] for c in cands], probes=probes)
+    return reports, list(eng.last_results)
+
+
+@pytest.mark.parametrize("name", ["ComplEx", "TransE", "ConvE"])
+def test_workspaces_survive_regrowth_with_every_request(name):
+    from kelpie_amd import synth
+    g = synth.make_graph("small", seed=9)
+    ds = ka.Dataset(g.num_entities, g.num_relations, g.train, g.valid, g.test)
+    extra = {"conve_random_bn": True, "trained_scale": 0.5} if name == "ConvE" else {}
+    w = synth.make_weights(name, g.num_entities, g.num_relations, DIM_NARROW[name], seed=9, **extra)
+    train = ds.entity_to_training_triples
+    pred = next(tuple(int(v) for v in t) for t in g.test if 14 <= len(train.get(int(t[0]), ())) <= 40)
+    own = sorted(train[pred[0]])
+    cands, probes = own[:12], own[12:14]  # two training triples of the subject that are no candidates
+    assert len(cands) == 12 and len(probes) == 2
+
+    eng = _extras_engine(name, ds, w)
+    first = _run_extras(eng, pred, cands[:2], probes)
+    middle = _run_extras(eng, pred, cands, probes)
+    again = _run_extras(eng, pred, cands[:2], probes)
+    fresh = _run_extras(_extras_engine(name, ds, w), pred, cands, probes)
+
+    assert len(first[1]) == 2 and len(middle[1]) == 12
+    for pt, _ in middle[1]:  # every request reached the results
+        assert 0 < len(pt["top_ids"]) == len(pt["top_scores"]) <= 3
+        assert len(pt["probes"]) == 2 and len(pt["marks"]) == 2
+        assert pt["loss"] and pt["margins"]["tol"] == 1e-4
     assert again == first, (first, again)
     assert middle == fresh, (middle, fresh)

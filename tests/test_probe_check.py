@@ -6,7 +6,8 @@ the host sanitizers.
 ``-fsanitize=address,undefined``.  The driver passes a good set of probes (an empty slot
 between full ones; no probes at all with null arrays), breaks each rule of the check once in
 the good set and requires that rule's message, expands the good set into rank rows (the
-empty slot between two that have probes), and on 400 pseudo-random valid sets requires
+empty slot between two that have probes) and a batch's slots likewise (0, 1 and 3 slots, the
+kelpie entity among the objects), and on 400 pseudo-random valid sets requires
 that the check passes and that the chunks cover every probe row once, in whole groups of 16
 rows, within their budget (or as KP_PROBE_CHUNK forces them).  No kernel runs: malformed
 probes never reach a GPU."""
@@ -43,6 +44,8 @@ def test_probe_check(target):
     assert "random sets: 400" in lines, p.stdout
     assert "good: ok" in lines and "no probes, null arrays: ok" in lines, p.stdout
     assert "rows, empty middle slot: ok" in lines and "rows, no probes: ok" in lines, p.stdout
+    for n in ("no slots", "one slot", "three slots"):
+        assert f"slot rows, {n}: ok" in lines, p.stdout
     # every rule was broken at least once and reported
     told = [ln.split(": ", 1)[1] for ln in lines if ": " in ln]
     assert all(m in told for m in MESSAGES), p.stdout

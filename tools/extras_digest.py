@@ -3,8 +3,9 @@
     python tools/extras_digest.py [> profiles/<dir>/digest_<build>.txt]
 
 For marks_cases' four family cases (the ones tests/test_marks_gpu.py calls FAMILY) the first
-engine batch runs again directly with topk = 5, seven probes per slot, the trace and the
-case's marks; one sha256 per output is printed, then the median ``last_timing()["device_s"]``
+engine batch runs again directly with topk = 5, seven probes per slot, the trace, the case's
+marks and the margins at tol = 1e-4; one sha256 per output is printed (one per margin array of
+the slots, the probes and the marks), then the median ``last_timing()["device_s"]``
 of five repeats after one warm-up.  Only ``Context.posttrain_rank``'s public keywords and
 ``marks_cases.run`` are used, so the same file runs on an older checkout: two builds compute
 the same bits exactly when their lines are equal (KELPIE_HIP_LIB selects the library).
@@ -54,16 +55,20 @@ def main():
         batches, model = mc.run(case, lambda m: m.ctx)
         ctx = model.ctx._ctx  # (model.ctx is marks_cases.Capture around the device's)
         args = batches[0]["args"]
-        kw = {"topk": 5, "probes": probes_of(args, ctx.n_ent), "trace": True, "marks": mc.marks_of(case)}
+        kw = {"topk": 5, "probes": probes_of(args, ctx.n_ent), "trace": True, "marks": mc.marks_of(case),
+              "margins": 1e-4}
 
         def call():
             return ctx.posttrain_rank(*args, want_x=True, **kw)
 
-        s, r, x, (ids, top), (ps, pr), losses, (ms, mr, mx) = call()
+        s, r, x, (ids, top), (ps, pr), losses, (ms, mr, mx), margins = call()
         for name, arrays in (("score", (s,)), ("rank", (r,)), ("rows", (x,)), ("list_ids", (ids,)),
                              ("list_scores", (top,)), ("probe_score", (ps,)), ("probe_rank", (pr,)),
                              ("losses", losses), ("mark_score", (ms,)), ("mark_rank", (mr,)), ("mark_rows", (mx,))):
             print(f"{case['id']} {name} {sha(*arrays)}")
+        for kind, fields in zip(("slots", "probes", "marks"), margins):
+            for field in sorted(fields):
+                print(f"{case['id']} margin_{kind}_{field} {sha(fields[field])}")
         times = []
         for _ in range(5):
             call()
