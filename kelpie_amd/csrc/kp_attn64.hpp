@@ -20,7 +20,7 @@
 // Keys past the range's end are masked (p = 0 and the row of zeros), a range without keys
 // writes the empty partial (m = -inf, l = 0, O = 0).  No atomics: a rerun is bitwise equal.
 // The partials of the ranges are merged by log-sum-exp in range order by the consumers
-// (kp_complex.hip: kp_cx_contrib64, kp_cx_lse_merge64).
+// (kp_complex.hip: kp_cx_contrib64, kp_cx_lse_merge<double>).
 // LDS: 16 (16 DB + 1) floats + 8 KiB of partials (33.7 KiB at DB = 25); registers: DB doubles
 // of Q and 4 ceil(DB / 4) doubles of O per lane; no scratch.
 #pragma once

@@ -170,34 +170,34 @@ struct RankWs {
 };
 KP_WS_COMPLETE(RankWs);
 
-// kp_complex.hip, kp_posttrain_rank_f64: the fp64 step's own workspaces (rows, optimizer state,
-// the plan's uploads, contributions, target sums, pair queries and attention partials in
-// double), none shared with the fp32 path
-struct Complex64Ws {
-  DevBuf x, s1, s2;                // kelpie rows [ns][dp] and their moments, double
-  DevBuf plans, queries, targets;  // the step plan's uploads, as ComplexWs's
-  DevBuf pairs, acts, stepq, stept;
-  DevBuf contrib;                  // per-step gradient contributions [items][dp], double
-  DevBuf tsum, qpair, lsef;        // target sums, pair queries, their frozen lse, double
-  DevBuf am, al, ao;               // kp_attn64's partials per key range (max, sum, output), double
-  DevBuf qs;                       // the step's queries [nq][dp], double
-  auto all() {
-    return std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
-                      &tsum, &qpair, &lsef, &am, &al, &ao, &qs};
-  }
-};
-KP_WS_COMPLETE(Complex64Ws);
-
-// kp_complex.hip
-struct ComplexWs {
+// kp_complex.hip: the workspaces of the post-training step in one precision (kp_complex.hip's
+// CxDev<T> is their device side; rows, state, sums, queries and partials are T, the plan's
+// uploads the same in either)
+struct CxStepWs {
   DevBuf x, s1, s2;                // kelpie rows [ns][dp] and their Adagrad / Adam moments
   DevBuf plans, queries, targets;  // CxPlan, CxQuery, the queries' frozen targets
   DevBuf pairs, acts;              // frozen-head (h, r) pairs; per-step active slots
   DevBuf stepq, stept;             // per-step query / tail items
   DevBuf contrib;                  // per-step gradient contributions [items][dp]
   DevBuf tsum, qpair, lsef;        // target sums [queries][dp]; pair queries [pairs][dp], their frozen lse
-  DevBuf am, al, ao;               // attention split results (max, sum, output)
+  DevBuf am, al, ao;               // attention partials per split / key range (max, sum, output)
   DevBuf qs;                       // the step's queries [nq][dp]
+  auto all() {
+    return std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
+                      &tsum, &qpair, &lsef, &am, &al, &ao, &qs};
+  }
+};
+KP_WS_COMPLETE(CxStepWs);
+
+// kp_complex.hip: the step's workspaces once per precision -- f32, and f64 for
+// kp_posttrain_rank_f64 -- two objects that share a type and no buffer (an fp64 call leaves
+// every buffer of the fp32 path as it was), and what only the fp32 path has
+struct ComplexWs {
+  CxStepWs f32, f64;
+  template <class T>
+  CxStepWs& step() {
+    return sizeof(T) == sizeof(double) ? f64 : f32;
+  }
   DevBuf score_q, score_out;       // complex_scores_dev's queries, complex_all_scores' scores
   // kp_posttrain_rank_trace: the step's fp64 loss term per item [items] and the frozen rows'
   // regulariser factors [n_ent] / [n_rel2] (fp64, once per batch)
@@ -205,11 +205,8 @@ struct ComplexWs {
   // kp_posttrain_rank_marks: the mark rows [ns][marks][dp] and, per entry of acts, the mark
   // row its update also stores (-1: none)
   DevBuf marks, mark_row;
-  Complex64Ws f64;  // kp_posttrain_rank_f64
   auto all() {
-    return kp_join(std::array{&x, &s1, &s2, &plans, &queries, &targets, &pairs, &acts, &stepq, &stept, &contrib,
-                              &tsum, &qpair, &lsef, &am, &al, &ao, &qs, &score_q, &score_out, &tr_term, &tr_fe,
-                              &tr_fr, &marks, &mark_row},
+    return kp_join(f32.all(), std::array{&score_q, &score_out, &tr_term, &tr_fe, &tr_fr, &marks, &mark_row},
                    f64.all());
   }
 };

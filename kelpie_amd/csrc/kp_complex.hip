@@ -31,6 +31,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <type_traits>
 
 #include "kp_attn.hpp"
 #include "kp_attn3.hpp"
@@ -166,31 +167,43 @@ __global__ void kp_cx_qpair(const float* __restrict__ E, const float* __restrict
   for (int d = threadIdx.x; d < dp; d += blockDim.x) out[(size_t)p * dp + d] = cx_q_as<Prod, QT>(lhs, rel, d, half);
 }
 
-// lsef[p] = the frozen-head pair's log-sum-exp over the frozen entities, merged from the
-// attention's split statistics (one thread per pair; fp64 sum of the rescaled l's)
-__global__ void kp_cx_lse_merge(int npairs, int n_split, const float* __restrict__ am, const float* __restrict__ al,
-                                float* __restrict__ lsef) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npairs) return;
-  float mm = kNegInf;
-  for (int s = 0; s < n_split; ++s) mm = fmaxf(mm, am[(size_t)s * npairs + p]);
+// the log-sum-exp over the frozen entities from the attention's per-split (kp_attn / kp_attn3,
+// ST = float) or per-range (kp_attn64, ST = double) statistics (m, l), in split order: the max
+// in ST, the sum of the rescaled l's in fp64.  An empty part (m = -inf) adds nothing.
+template <class ST>
+__device__ __forceinline__ double lse_ranges64(const ST* __restrict__ am, const ST* __restrict__ al, int n,
+                                               int ranges, int item) {
+  ST mm = kNegInf;
+  for (int s = 0; s < ranges; ++s) mm = fmax(mm, am[(size_t)s * n + item]);
   double ll = 0.0;
-  for (int s = 0; s < n_split; ++s) {
-    const float ms = am[(size_t)s * npairs + p];
-    if (ms != kNegInf) ll += (double)al[(size_t)s * npairs + p] * exp((double)ms - (double)mm);
+  for (int s = 0; s < ranges; ++s) {
+    const ST ms = am[(size_t)s * n + item];
+    if (ms != kNegInf) ll += (double)al[(size_t)s * n + item] * exp((double)ms - (double)mm);
   }
-  lsef[p] = (float)((double)mm + log(ll));
+  return (double)mm + log(ll);
 }
 
-// Tsum[q] = sum of frozen target rows of a plan query
+// lsef[p] = the frozen-head pair's log-sum-exp over the frozen entities, merged from the
+// attention's partial statistics (one thread per pair), rounded once to ST at the store
+template <class ST>
+__global__ void kp_cx_lse_merge(int npairs, int n_split, const ST* __restrict__ am, const ST* __restrict__ al,
+                                ST* __restrict__ lsef) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npairs) return;
+  lsef[p] = (ST)lse_ranges64(am, al, npairs, n_split, p);
+}
+
+// Tsum[q] = sum of frozen target rows of a plan query, in list order (AT: the accumulator's
+// and the sums' type)
+template <class AT>
 __global__ void kp_cx_tsum(const float* __restrict__ E, int dp, const CxQuery* __restrict__ pq, int nq,
-                           const int32_t* __restrict__ targets, float* __restrict__ tsum) {
+                           const int32_t* __restrict__ targets, AT* __restrict__ tsum) {
   int q = blockIdx.x;
   if (q >= nq) return;
   CxQuery Q = pq[q];
   for (int d = threadIdx.x; d < dp; d += blockDim.x) {
-    float acc = 0.f;
-    for (int i = 0; i < Q.tg_count; ++i) acc += E[(size_t)targets[Q.tg_begin + i] * dp + d];
+    AT acc = 0;
+    for (int i = 0; i < Q.tg_count; ++i) acc += (AT)E[(size_t)targets[Q.tg_begin + i] * dp + d];
     tsum[(size_t)q * dp + d] = acc;
   }
 }
@@ -200,15 +213,19 @@ __global__ void kp_cx_tsum(const float* __restrict__ E, int dp, const CxQuery* _
 // single-row gradient of the minibatch loss and applies the
 // optimizer with torch's op order (optim/adagrad.py, optim/adam.py).
 // ----------------------------------------------------------------------------
-struct CxOpt {
+// (T: the state's type; CxOpt64 is kp_posttrain_rank_f64's)
+template <class T>
+struct CxOptT {
   int kind;
-  float lr, b1, b2, eps;
-  float one_minus_b1, one_minus_b2;
-  float step_size;  // Adam: lr / (1 - b1^t)
-  float bc2_sqrt;   // Adam: sqrt(1 - b2^t)
-  float reg_w;
+  T lr, b1, b2, eps;
+  T one_minus_b1, one_minus_b2;
+  T step_size;  // Adam: lr / (1 - b1^t)
+  T bc2_sqrt;   // Adam: sqrt(1 - b2^t)
+  T reg_w;
   int reg_n2;  // KP_REG_N2: N2 on the whole row's L2 norm (regularizers.py:25-35) instead of N3
 };
+using CxOpt = CxOptT<float>;
+using CxOpt64 = CxOptT<double>;
 
 #define UPD_MAXSPLIT 16
 
@@ -631,395 +648,19 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
   }
 }
 
-// fp64 ranking queries (launch_rank_f64): q_s = x_s o R[p_s] from exact fp64 products of
-// the fp32 operands; the target score q_s . E_o and the kelpie column q_s . x_s as one
-// sequential fp64 FMA chain over d (the order kp_rank_f64_count scores every entity in).
-// Row s of a set of rank rows is pred[3 s ..] = (row, p, o): x is row `row` of X (the slots: s
-// itself; a probe: its slot's kelpie row; a mark row: its row of the mark workspace).
-// XT: the kelpie rows' type (double: kp_posttrain_rank_f64, whose row is never rounded)
-template <int DP, class Prod, class XT = float>
-__global__ void kp_cx_rankq64(const XT* __restrict__ X, const float* __restrict__ R, const float* __restrict__ E,
-                              int n_ent, int half, const int32_t* __restrict__ pred, int n_slots,
-                              double* __restrict__ Q, double* __restrict__ t64, double* __restrict__ kcol64) {
-  const int s = blockIdx.x;
-  if (s >= n_slots) return;
-  const XT* x = X + (size_t)pred[3 * s] * DP;
-  const float* rel = R + (size_t)pred[3 * s + 1] * DP;
-  double* q = Q + (size_t)s * DP;
-  for (int d = threadIdx.x; d < DP; d += blockDim.x) q[d] = Prod::q64(x, rel, d, half);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int o = pred[3 * s + 2];
-    double z = 0.0, t = 0.0;
-    for (int d = 0; d < DP; ++d) z = __fma_rn(q[d], (double)x[d], z);
-    if (o < n_ent) {
-      const float* eo = E + (size_t)o * DP;
-      for (int d = 0; d < DP; ++d) t = __fma_rn(q[d], (double)eo[d], t);
-    } else {
-      t = z;  // the kelpie entity is its own object
-    }
-    kcol64[s] = z;
-    t64[s] = t;
-  }
-}
-
-template <class Prod>
-__global__ void kp_cx_scoreq(const float* __restrict__ E, const float* __restrict__ R, int dp, int half,
-                             const int32_t* __restrict__ heads, const int32_t* __restrict__ rels, int n,
-                             float* __restrict__ Q) {
-  int s = blockIdx.x;
-  if (s >= n) return;
-  const float* lhs = E + (size_t)heads[s] * dp;
-  const float* rel = R + (size_t)rels[s] * dp;
-  for (int d = threadIdx.x; d < dp; d += blockDim.x) Q[(size_t)s * dp + d] = Prod::q(lhs, rel, d, half);
-}
-
-// ----------------------------------------------------------------------------
-// host side
-// ----------------------------------------------------------------------------
-// step queries q_j = x_slot o R_rel (complex.py:65-72), one row per step query
-// (XT: the rows' and the queries' type; double: kp_posttrain_rank_f64)
-template <int DP, class Prod, class XT = float>
-__global__ void kp_cx_stepq(const XT* __restrict__ X, const float* __restrict__ R, int half,
-                            const int4* __restrict__ stepq, int nq, XT* __restrict__ Q) {
-  const int j = blockIdx.x;
-  if (j >= nq) return;
-  const int4 sq = stepq[j];
-  const XT* x = X + (size_t)sq.x * DP;
-  const float* rel = R + (size_t)sq.y * DP;
-  for (int d = threadIdx.x; d < DP; d += blockDim.x) Q[(size_t)j * DP + d] = cx_q_as<Prod, XT>(x, rel, d, half);
-}
-
-template <int DB, class Prod, class XT = float>
-void launch_stepq(kp_ctx* c, const int4* stepq, const XT* X, int nq, XT* Q) {
-  if (nq <= 0) return;
-  hipLaunchKernelGGL((kp_cx_stepq<16 * DB, Prod, XT>), dim3(nq), dim3(64), 0, c->stream, X, c->dR, Prod::extent(c->dim), stepq,
-                     nq, Q);
-  KP_HIP(hipGetLastError());
-}
-
-// co-resident attention workgroups: LDS and registers allow two per CU for rows up
-// to 208 floats, one for wider rows
-// (kp_attn3: as many as the occupancy API reports)
-template <int DB>
-int attn_slots_db(kp_ctx* c) {
-  if (c->attn_mode == 1) return c->n_cu * attn3_wpc<DB>(c);
-  return c->n_cu * (DB <= 13 ? 2 : 1);
-}
-
-template <int DB>
-void launch_attn(kp_ctx* c, bool with_o, const float* Q, int nq, const AttnPlan& plan, float* m, float* l,
-                 float* O) {
-  if (nq <= 0) return;
-  if (c->attn_mode == 1) {
-    if (with_o)
-      launch_attn3<DB, ATT_SOFTMAX_O>(c, c->n_ent, Q, nq, plan, m, l, O, nullptr, 0.f);
-    else
-      launch_attn3<DB, ATT_SOFTMAX>(c, c->n_ent, Q, nq, plan, m, l, O, nullptr, 0.f);
-    return;
-  }
-  const size_t shm = attn_lds_bytes(DB);
-  if (with_o)
-    hipLaunchKernelGGL((kp_attn<DB, ATT_SOFTMAX_O>), dim3(plan.n_wg), dim3(256), shm, c->stream, c->dE, c->n_ent, Q,
-                       nq, plan.wk, m, l, O, nullptr, 0.f);
-  else
-    hipLaunchKernelGGL((kp_attn<DB, ATT_SOFTMAX>), dim3(plan.n_wg), dim3(256), shm, c->stream, c->dE, c->n_ent, Q,
-                       nq, plan.wk, m, l, O, nullptr, 0.f);
-  KP_HIP(hipGetLastError());
-}
-
-// kp_posttrain_rank_trace's device side (loss == nullptr: no trace): the common part and
-// ComplEx's own workspaces
-struct CxTraceDev : TraceDev {
-  double *term = nullptr, *freg_e = nullptr, *freg_r = nullptr;
-  const int32_t* targets = nullptr;
-  const int2* pairs = nullptr;
-};
-
-template <int DB, class Prod>
-void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, const CxQuery* pq,
-                   const int4* stepq, int nq, const int4* stept, int nt, const float* tsum, const float* qpair,
-                   const float* lsef, const float* am, const float* al, const float* aO, int n_split, float* contrib,
-                   float* X, float* S1, float* S2, const CxOpt& opt, const CxTraceDev& tr = {}, int step = 0,
-                   const CxMarkArgs<true>* mk = nullptr) {
-  if (n_act <= 0) return;
-  const int half = Prod::extent(c->dim);
-  KP_REQUIRE(n_split >= 1 && n_split <= 64, "cx contrib: one attention split per lane");
-  if (nq + nt > 0 && !tr.loss) {
-    hipLaunchKernelGGL((kp_cx_contrib<16 * DB, Prod>), dim3((nq + nt + 3) / 4), dim3(256), 0, c->stream, half, stepq, nq,
-                       stept, nt, pq, X, c->dR, tsum, qpair, lsef, am, al, aO, n_split, contrib, CxTraceArgs<false>{});
-    KP_HIP(hipGetLastError());
-  }
-  if (tr.loss) {  // kp_posttrain_rank_trace: the items' loss terms, then the slots' losses, before x moves
-    if (nq + nt > 0) {
-      hipLaunchKernelGGL((kp_cx_contrib<16 * DB, Prod, true>), dim3((nq + nt + 3) / 4), dim3(256), 0, c->stream, half,
-                         stepq, nq, stept, nt, pq, X, c->dR, tsum, qpair, lsef, am, al, aO, n_split, contrib,
-                         CxTraceArgs<true>{tr.term});
-      KP_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL((kp_cx_trace_sum<16 * DB, Prod>), dim3(n_act), dim3(64), 0, c->stream, half, act, plans, pq,
-                       tr.targets, tr.pairs, stept, nq, X, tr.term, tr.freg_e, tr.freg_r, opt.reg_w, opt.reg_n2,
-                       tr.off, step, tr.loss);
-    KP_HIP(hipGetLastError());
-  }
-  if (mk)  // a step that ends a marked epoch of one of its slots: the MARKS form instead, not a further launch
-    hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod, true>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq,
-                       contrib, X, S1, S2, opt, *mk);
-  else
-    hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq, contrib,
-                       X, S1, S2, opt, CxMarkArgs<false>{});
-  KP_HIP(hipGetLastError());
-}
-
-// the fp64 queries of the rows [r0, r0 + m) of a set of rank rows, on the rows X, into the
-// set's chunk buffers
-template <int DB, class Prod, class XT = float>
-void launch_rankq64(kp_ctx* c, const XT* X, const RankSet& rr, int r0, int m) {
-  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod, XT>), dim3(m), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
-                     Prod::extent(c->dim), rr.rows + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol);
-  KP_HIP(hipGetLastError());
-}
-
-#define CX_DISPATCH(DBV, ...) \
-  KP_DB_DISPATCH(DBV, 1, "ComplEx / DistMult: unsupported padded dimension", __VA_ARGS__)
-
-// the optimizer's constants of a call (step_size and bc2_sqrt follow per step)
-CxOpt make_opt(const kp_hp* hp, const std::string& who) {
-  CxOpt opt{};
-  opt.kind = hp->optimizer;
-  opt.lr = hp->lr;
-  opt.b1 = hp->beta1;
-  opt.b2 = hp->beta2;
-  opt.eps = hp->eps;
-  opt.one_minus_b1 = (float)(1.0 - (double)hp->beta1);
-  opt.one_minus_b2 = (float)(1.0 - (double)hp->beta2);
-  opt.reg_w = hp->reg_weight;
-  KP_REQUIRE(hp->reg_kind == KP_REG_N3 || hp->reg_kind == KP_REG_N2, who + ": unknown regulariser");
-  opt.reg_n2 = hp->reg_kind == KP_REG_N2;
-  return opt;
-}
-
-// the device side of one call: the plan's uploads and the workspaces (c->cx, c->rank)
-struct CxDev {
-  float *X, *S1, *S2;  // kelpie rows and optimizer state [ns][dp]
-  CxPlan* plans;
-  CxQuery* pq;
-  int32_t* tg;
-  int2* pairs;
-  int4 *acts, *stepq, *stept;
-  float *contrib, *tsum, *qpair, *lsef;
-  RankSet rk, probes;  // the slots, kp_posttrain_rank_probes
-  CxTraceDev trace;
-  MarksDev marks;
-  int32_t* mark_row = nullptr;  // [acts] the mark row an active entry's update also stores, or -1
-  // the attention's: sized and planned by cx_preloop
-  float *am = nullptr, *al = nullptr, *ao = nullptr, *qs = nullptr;
-  std::vector<AttnPlan> step_plan;  // [T]
-};
-
-// the plan's element types are the HIP vector types' layout: their arrays are uploaded as such
-static_assert(sizeof(CxI2) == sizeof(int2) && alignof(CxI2) == alignof(int2), "CxI2 is int2");
-static_assert(sizeof(CxI4) == sizeof(int4) && alignof(CxI4) == alignof(int4), "CxI4 is int4");
-inline const int2* as_dev(const CxI2* p) { return reinterpret_cast<const int2*>(p); }
-inline const int4* as_dev(const CxI4* p) { return reinterpret_cast<const int4*>(p); }
-
-CxDev cx_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq, const CxStepPlan& sp,
-                    std::vector<float>& xp) {
-  const int ns = bt->n_slots, DP = c->dp;
-  CxDev d;
-  d.X = upload_x0(c, c->cx.x, bt, xp, rq.keyed);
-  d.S1 = ensure_n<float>(c->cx.s1, (size_t)ns * DP);
-  d.S2 = ensure_n<float>(c->cx.s2, (size_t)ns * DP);
-  KP_HIP(hipMemsetAsync(d.S1, 0, sizeof(float) * (size_t)ns * DP, c->stream));
-  KP_HIP(hipMemsetAsync(d.S2, 0, sizeof(float) * (size_t)ns * DP, c->stream));
-  d.plans = upload(c, c->cx.plans, sp.plans.data(), sp.plans.size());
-  d.pq = upload(c, c->cx.queries, sp.pqs.data(), sp.pqs.size());
-  d.tg = upload(c, c->cx.targets, sp.targets.data(), sp.targets.size());
-  d.pairs = upload(c, c->cx.pairs, as_dev(sp.pairs.data()), sp.pairs.size());
-  d.acts = upload(c, c->cx.acts, as_dev(sp.acts.data()), sp.acts.size());
-  // (empty without a step, epochs == 0: upload() then only sizes the buffer)
-  d.stepq = upload(c, c->cx.stepq, as_dev(sp.stepq.data()), sp.stepq.size());
-  d.stept = upload(c, c->cx.stept, as_dev(sp.stept.data()), sp.stept.size());
-  d.contrib = ensure_n<float>(c->cx.contrib, (size_t)std::max(1, sp.max_items) * DP);
-  const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
-  d.tsum = ensure_n<float>(c->cx.tsum, (size_t)std::max(npq, 1) * DP);
-  d.qpair = ensure_n<float>(c->cx.qpair, (size_t)std::max(npairs, 1) * DP);
-  d.lsef = ensure_n<float>(c->cx.lsef, (size_t)std::max(npairs, 1));
-
-  // the ranking's inputs and buffers now, ahead of the step loop: an upload from pageable
-  // memory after the loop waited for the whole loop on the device, so the rank kernels
-  // were enqueued only then (a host round trip per batch with the context idle)
-  d.rk = upload_slots(c, c->rank.slots, bt, rq, d.X);
-  d.probes = upload_probes(c, bt, rq, d.X);
-  // kp_posttrain_rank_marks: the mark rows (each the padded x0 until a step captures it)
-  d.marks = upload_marks(c, c->cx.marks, hp, bt, rq, d.X);
-  if (d.marks.nm > 0) {
-    const std::vector<int32_t> mr = marks_act_rows(d.marks, sp.act_off, sp.T, [&](int i) { return sp.acts[i].x; });
-    d.mark_row = upload(c, c->cx.mark_row, mr.data(), mr.size());
-  }
-  if (rq.trace) {  // the trace's offsets and workspaces, with the call's other uploads
-    CxTraceDev& t = d.trace;
-    static_cast<TraceDev&>(t) = upload_trace(c, bt, rq);
-    t.term = ensure_n<double>(c->cx.tr_term, (size_t)std::max(1, sp.max_items));
-    t.freg_e = ensure_n<double>(c->cx.tr_fe, (size_t)c->n_ent);
-    t.freg_r = ensure_n<double>(c->cx.tr_fr, (size_t)c->n_rel2);
-    t.targets = d.tg;
-    t.pairs = d.pairs;
-  }
-  return d;
-}
-
-// before the loop: the queries' frozen-target sums, the attention plans and workspaces of
-// every step, and the frozen-head pairs' q and frozen log-sum-exp
-template <class Prod>
-void cx_preloop(kp_ctx* c, const CxStepPlan& sp, CxDev& d, float reg_w, int reg_n2) {
-  const int DP = c->dp, DBV = DP / 16;
-  const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
-  KP_HIP(hipEventRecord(c->ev0, c->stream));
-  if (npq > 0) {
-    hipLaunchKernelGGL(kp_cx_tsum, dim3(npq), dim3(128), 0, c->stream, c->dE, DP, d.pq, npq, d.tg, d.tsum);
-    KP_HIP(hipGetLastError());
-  }
-  if (d.trace.loss && reg_w != 0.f && sp.T > 0) {  // the frozen rows' regulariser factors, once per batch
-    const int half = Prod::extent(c->dim);
-    hipLaunchKernelGGL(kp_cx_rowreg<Prod>, dim3((c->n_ent + 3) / 4), dim3(256), 0, c->stream, c->dE, c->n_ent, DP, half,
-                       reg_n2, d.trace.freg_e);
-    KP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(kp_cx_rowreg<Prod>, dim3((c->n_rel2 + 3) / 4), dim3(256), 0, c->stream, c->dR, c->n_rel2, DP,
-                       half, reg_n2, d.trace.freg_r);
-    KP_HIP(hipGetLastError());
-  }
-  int slots_attn = 0;
-  CX_DISPATCH(DBV, slots_attn = attn_slots_db<DB>(c));
-  const AttnPlan plan_pairs = attn_plan_ctx(c, std::max(npairs, 1), c->n_ent, slots_attn, true);
-  const int split_pairs = plan_pairs.wk.n_parts;
-  size_t att_rows = (size_t)std::max(npairs, 1) * split_pairs;
-  d.step_plan.resize(sp.T);
-  c->attn_last = {};
-  for (int t = 0; t < sp.T; ++t) {
-    const int nq = sp.q_off[t + 1] - sp.q_off[t];
-    d.step_plan[t] = attn_plan_ctx(c, std::max(nq, 1), c->n_ent, slots_attn, true);
-    if (nq > 0) attn_plan_note(c, d.step_plan[t], nq, true);
-    att_rows = std::max(att_rows, (size_t)nq * d.step_plan[t].wk.n_parts);
-  }
-  d.am = ensure_n<float>(c->cx.am, att_rows);
-  d.al = ensure_n<float>(c->cx.al, att_rows);
-  d.ao = ensure_n<float>(c->cx.ao, att_rows * DP);
-  d.qs = ensure_n<float>(c->cx.qs, (size_t)std::max(sp.max_nq, 1) * DP);
-  if (npairs > 0) {
-    hipLaunchKernelGGL(kp_cx_qpair<Prod>, dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP, Prod::extent(c->dim),
-                       d.pairs, npairs, d.qpair);
-    KP_HIP(hipGetLastError());
-    CX_DISPATCH(DBV, launch_attn<DB>(c, false, d.qpair, npairs, plan_pairs, d.am, d.al, nullptr));
-    // combine the splits into lsef on the device (no host round trip inside the batch)
-    hipLaunchKernelGGL(kp_cx_lse_merge, dim3((npairs + 255) / 256), dim3(256), 0, c->stream, npairs, split_pairs, d.am,
-                       d.al, d.lsef);
-    KP_HIP(hipGetLastError());
-  }
-}
-
-// the epoch/step loop: per step the queries, their attention over the frozen entities and
-// the update of every active slot.  Returns the hot (attention) launches; t_steps: the host
-// time after enqueueing steps 0, 1, T/2, T-1 (KP_HOST_TIMES)
-template <class Prod>
-int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxDev& d, CxOpt opt, double* t_steps) {
-  const int DBV = c->dp / 16, T = sp.T;
-  int64_t hot_launches = 0;
-  c->hot_pairs.clear();
-  c->hot_iv.clear();
-  for (int t = 0; t < T; ++t) {
-    const int nq = sp.q_off[t + 1] - sp.q_off[t];
-    const int na = sp.act_off[t + 1] - sp.act_off[t];
-    const int sp_n = d.step_plan[t].wk.n_parts;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (nq > 0 && c->time_hot) {
-      ea = c->event(2 * hot_launches);
-      eb = c->event(2 * hot_launches + 1);
-    }
-    CX_DISPATCH(DBV, launch_stepq<DB, Prod>(c, d.stepq + sp.q_off[t], d.X, nq, d.qs));
-    if (nq > 0 && c->time_hot) KP_HIP(hipEventRecord(ea, c->stream));
-    CX_DISPATCH(DBV, launch_attn<DB>(c, true, d.qs, nq, d.step_plan[t], d.am, d.al, d.ao));
-    if (nq > 0) {
-      if (c->time_hot) {
-        KP_HIP(hipEventRecord(eb, c->stream));
-        c->hot_pairs.push_back({(double)nq, 0.0});
-      }
-      ++hot_launches;
-    }
-    const AdamStep as = adam_step(hp, t);
-    opt.step_size = as.step_size;
-    opt.bc2_sqrt = as.bc2_sqrt;
-    const CxMarkArgs<true> mk{d.mark_row ? d.mark_row + sp.act_off[t] : nullptr, d.marks.X};
-    CX_DISPATCH(DBV, launch_update<DB, Prod>(c, na, d.acts + sp.act_off[t], d.plans, d.pq, d.stepq + sp.q_off[t], nq,
-                                             d.stept + sp.t_off[t], sp.t_off[t + 1] - sp.t_off[t], d.tsum, d.qpair,
-                                             d.lsef, d.am, d.al, d.ao, sp_n, d.contrib, d.X, d.S1, d.S2, opt,
-                                             d.trace, t, marks_at_step(d.marks, t) ? &mk : nullptr));
-    if (g_host_times) {
-      if (t == 0) t_steps[0] = host_ms();
-      if (t == 1) t_steps[1] = host_ms();
-      if (t == T / 2) t_steps[2] = host_ms();
-      if (t == T - 1) t_steps[3] = host_ms();
-    }
-  }
-  return hot_launches;
-}
-
 // ============================================================================
 // kp_posttrain_rank_f64 (include/kelpie_hip.h, "fp64"): the same decomposition with the row,
 // the queries, the attention (kp_attn64.hpp), the merge, the gradient, the regulariser term,
-// the optimizer state and the update in fp64.  The small kernels above are compiled over the
-// row type (kp_cx_stepq, kp_cx_qpair, kp_cx_rankq64); the merge and the update are the forms
-// below: one partial per key range merged in range order where the fp32 form merges one per
-// lane, and no trace or mark arguments.  Every sum has a fixed order.
+// the optimizer state and the update in fp64.  The small kernels are compiled over the row
+// type (kp_cx_stepq, kp_cx_qpair, kp_cx_tsum, kp_cx_lse_merge, kp_cx_rankq64) and the host
+// side below is written once over it; the merge and the update are the forms below: one
+// partial per key range merged in range order where the fp32 form merges one per lane, and
+// no trace or mark arguments.  Every sum has a fixed order.
 // ============================================================================
-struct CxOpt64 {
-  int kind;
-  double lr, b2, eps;
-  double one_minus_b1, one_minus_b2;
-  double step_size;  // Adam: lr / (1 - b1^t)
-  double bc2_sqrt;   // Adam: sqrt(1 - b2^t)
-  double reg_w;
-  int reg_n2;
-};
-
 __device__ __forceinline__ double wave_sum64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-// Tsum in fp64 (the targets in list order)
-__global__ void kp_cx_tsum64(const float* __restrict__ E, int dp, const CxQuery* __restrict__ pq, int nq,
-                             const int32_t* __restrict__ targets, double* __restrict__ tsum) {
-  int q = blockIdx.x;
-  if (q >= nq) return;
-  CxQuery Q = pq[q];
-  for (int d = threadIdx.x; d < dp; d += blockDim.x) {
-    double acc = 0.0;
-    for (int i = 0; i < Q.tg_count; ++i) acc += (double)E[(size_t)targets[Q.tg_begin + i] * dp + d];
-    tsum[(size_t)q * dp + d] = acc;
-  }
-}
-
-// the log-sum-exp over the frozen entities from kp_attn64's per-range (m, l), in range order;
-// m_out: the merged max.  An empty range (m = -inf) adds nothing.
-__device__ __forceinline__ double lse_ranges64(const double* __restrict__ am, const double* __restrict__ al, int n,
-                                               int ranges, int item) {
-  double mm = -__builtin_inf();
-  for (int s = 0; s < ranges; ++s) mm = fmax(mm, am[(size_t)s * n + item]);
-  double ll = 0.0;
-  for (int s = 0; s < ranges; ++s) {
-    const double ms = am[(size_t)s * n + item];
-    if (ms != -__builtin_inf()) ll += al[(size_t)s * n + item] * exp(ms - mm);
-  }
-  return mm + log(ll);
-}
-
-__global__ void kp_cx_lse_merge64(int npairs, int ranges, const double* __restrict__ am,
-                                  const double* __restrict__ al, double* __restrict__ lsef) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npairs) return;
-  lsef[p] = lse_ranges64(am, al, npairs, ranges, p);
 }
 
 // kp_cx_contrib in fp64: one wave per (query or frozen-head row) of the step.  The formulas
@@ -1200,170 +841,520 @@ __global__ __launch_bounds__(256) void kp_cx_update64(int half, const int4* __re
   }
 }
 
-// the key ranges of a call's fp64 attention launches: the planner's S for the call's largest
-// launch (attn_plan_ranges; KP_ATTN_RANGES=S forces S as it does for kp_attn3), in whole
-// 32-key planner tiles.  One S for the whole call keeps the partials' layout fixed.
-struct Attn64Plan {
-  int ranges, keys_per_range;
-};
-inline Attn64Plan attn64_plan(const kp_ctx* c, int max_nq) {
-  const int slots = c->n_cu;
-  const AttnPlan p = c->attn_ranges > 0 ? attn_plan_oneshot(std::max(1, max_nq), c->n_ent, c->attn_ranges)
-                                        : attn_plan_ranges(std::max(1, max_nq), c->n_ent, slots);
-  const int S = std::max(1, p.wk.ranges);
-  const int tiles = (p.wk.ktq + S - 1) / S;
-  return {S, tiles * 32};
+// fp64 ranking queries (launch_rank_f64): q_s = x_s o R[p_s] from exact fp64 products of
+// the fp32 operands; the target score q_s . E_o and the kelpie column q_s . x_s as one
+// sequential fp64 FMA chain over d (the order kp_rank_f64_count scores every entity in).
+// Row s of a set of rank rows is pred[3 s ..] = (row, p, o): x is row `row` of X (the slots: s
+// itself; a probe: its slot's kelpie row; a mark row: its row of the mark workspace).
+// XT: the kelpie rows' type (double: kp_posttrain_rank_f64, whose row is never rounded)
+template <int DP, class Prod, class XT = float>
+__global__ void kp_cx_rankq64(const XT* __restrict__ X, const float* __restrict__ R, const float* __restrict__ E,
+                              int n_ent, int half, const int32_t* __restrict__ pred, int n_slots,
+                              double* __restrict__ Q, double* __restrict__ t64, double* __restrict__ kcol64) {
+  const int s = blockIdx.x;
+  if (s >= n_slots) return;
+  const XT* x = X + (size_t)pred[3 * s] * DP;
+  const float* rel = R + (size_t)pred[3 * s + 1] * DP;
+  double* q = Q + (size_t)s * DP;
+  for (int d = threadIdx.x; d < DP; d += blockDim.x) q[d] = Prod::q64(x, rel, d, half);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int o = pred[3 * s + 2];
+    double z = 0.0, t = 0.0;
+    for (int d = 0; d < DP; ++d) z = __fma_rn(q[d], (double)x[d], z);
+    if (o < n_ent) {
+      const float* eo = E + (size_t)o * DP;
+      for (int d = 0; d < DP; ++d) t = __fma_rn(q[d], (double)eo[d], t);
+    } else {
+      t = z;  // the kelpie entity is its own object
+    }
+    kcol64[s] = z;
+    t64[s] = t;
+  }
 }
 
-// kp_posttrain_rank_f64 for a context of product Prod
 template <class Prod>
-void posttrain_rank_f64(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq) {
-  const std::string who = kp_model_name(c->model);
-  const kp_f64& f = *rq.f64;
-  const int ns = bt->n_slots, DP = c->dp, DBV = DP / 16, dim = c->dim;
-  const int half = Prod::extent(dim);
-  KP_REQUIRE(hp->batch_size > 0 && hp->epochs >= 0, who + ": bad batch_size/epochs");
-  require_request(c, hp, bt, rq, true, kp_model_name(c->model));
-  KP_REQUIRE(hp->reg_kind == KP_REG_N3 || hp->reg_kind == KP_REG_N2, who + ": unknown regulariser");
-  CxOpt64 opt{};
-  opt.kind = hp->optimizer;
-  opt.lr = f.lr;
-  opt.b2 = f.beta2;
-  opt.eps = f.eps;
-  opt.one_minus_b1 = 1.0 - f.beta1;
-  opt.one_minus_b2 = 1.0 - f.beta2;
-  opt.reg_w = f.reg_weight;
-  opt.reg_n2 = hp->reg_kind == KP_REG_N2;
+__global__ void kp_cx_scoreq(const float* __restrict__ E, const float* __restrict__ R, int dp, int half,
+                             const int32_t* __restrict__ heads, const int32_t* __restrict__ rels, int n,
+                             float* __restrict__ Q) {
+  int s = blockIdx.x;
+  if (s >= n) return;
+  const float* lhs = E + (size_t)heads[s] * dp;
+  const float* rel = R + (size_t)rels[s] * dp;
+  for (int d = threadIdx.x; d < dp; d += blockDim.x) Q[(size_t)s * dp + d] = Prod::q(lhs, rel, d, half);
+}
 
-  CxStepPlan sp;
-  if (const char* why = cx_step_plan(c->n_ent, c->n_rel2, hp->batch_size, hp->epochs, bt, sp))
-    throw KpError{KP_EINVAL, who + ": " + why};
+// ----------------------------------------------------------------------------
+// host side
+// ----------------------------------------------------------------------------
+// step queries q_j = x_slot o R_rel (complex.py:65-72), one row per step query
+// (XT: the rows' and the queries' type; double: kp_posttrain_rank_f64)
+template <int DP, class Prod, class XT = float>
+__global__ void kp_cx_stepq(const XT* __restrict__ X, const float* __restrict__ R, int half,
+                            const int4* __restrict__ stepq, int nq, XT* __restrict__ Q) {
+  const int j = blockIdx.x;
+  if (j >= nq) return;
+  const int4 sq = stepq[j];
+  const XT* x = X + (size_t)sq.x * DP;
+  const float* rel = R + (size_t)sq.y * DP;
+  for (int d = threadIdx.x; d < DP; d += blockDim.x) Q[(size_t)j * DP + d] = cx_q_as<Prod, XT>(x, rel, d, half);
+}
 
-  // ---- workspaces, all sized here, ahead of the step loop (c->cx.f64, c->rank.f64)
-  Complex64Ws& w = c->cx.f64;
-  std::vector<double> xp((size_t)ns * DP, 0.0);
-  for (int s = 0; s < ns; ++s) std::memcpy(&xp[(size_t)s * DP], f.x0 + (size_t)s * dim, sizeof(double) * dim);
-  double* X = upload(c, w.x, xp.data(), xp.size());
-  double* S1 = ensure_n<double>(w.s1, (size_t)ns * DP);
-  double* S2 = ensure_n<double>(w.s2, (size_t)ns * DP);
-  KP_HIP(hipMemsetAsync(S1, 0, sizeof(double) * (size_t)ns * DP, c->stream));
-  KP_HIP(hipMemsetAsync(S2, 0, sizeof(double) * (size_t)ns * DP, c->stream));
-  const CxPlan* plans = upload(c, w.plans, sp.plans.data(), sp.plans.size());
-  const CxQuery* pq = upload(c, w.queries, sp.pqs.data(), sp.pqs.size());
-  const int32_t* tg = upload(c, w.targets, sp.targets.data(), sp.targets.size());
-  const int2* pairs = upload(c, w.pairs, as_dev(sp.pairs.data()), sp.pairs.size());
-  const int4* acts = upload(c, w.acts, as_dev(sp.acts.data()), sp.acts.size());
-  const int4* stepq = upload(c, w.stepq, as_dev(sp.stepq.data()), sp.stepq.size());
-  const int4* stept = upload(c, w.stept, as_dev(sp.stept.data()), sp.stept.size());
-  const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
-  double* contrib = ensure_n<double>(w.contrib, (size_t)std::max(1, sp.max_items) * DP);
-  double* tsum = ensure_n<double>(w.tsum, (size_t)std::max(npq, 1) * DP);
-  double* qpair = ensure_n<double>(w.qpair, (size_t)std::max(npairs, 1) * DP);
-  double* lsef = ensure_n<double>(w.lsef, (size_t)std::max(npairs, 1));
-  const Attn64Plan ap = attn64_plan(c, std::max(sp.max_nq, npairs));
-  const size_t att_rows = (size_t)std::max(1, std::max(sp.max_nq, npairs)) * ap.ranges;
-  double* am = ensure_n<double>(w.am, att_rows);
-  double* al = ensure_n<double>(w.al, att_rows);
-  double* ao = ensure_n<double>(w.ao, att_rows * DP);
-  double* qs = ensure_n<double>(w.qs, (size_t)std::max(sp.max_nq, 1) * DP);
-  // the slots as a set of rank rows of its own; its queries read the double rows X
-  const RankSet rk = upload_slots(c, c->rank.f64, bt, rq, nullptr);
+template <int DB, class Prod, class XT = float>
+void launch_stepq(kp_ctx* c, const int4* stepq, const XT* X, int nq, XT* Q) {
+  if (nq <= 0) return;
+  hipLaunchKernelGGL((kp_cx_stepq<16 * DB, Prod, XT>), dim3(nq), dim3(64), 0, c->stream, X, c->dR, Prod::extent(c->dim), stepq,
+                     nq, Q);
+  KP_HIP(hipGetLastError());
+}
 
-  // ---- before the loop: target sums, the frozen-head pairs' q and frozen log-sum-exp
-  KP_HIP(hipEventRecord(c->ev0, c->stream));
-  c->attn_last = {};
-  if (npq > 0) {
-    hipLaunchKernelGGL(kp_cx_tsum64, dim3(npq), dim3(128), 0, c->stream, c->dE, DP, pq, npq, tg, tsum);
+// co-resident attention workgroups: LDS and registers allow two per CU for rows up
+// to 208 floats, one for wider rows
+// (kp_attn3: as many as the occupancy API reports)
+template <int DB>
+int attn_slots_db(kp_ctx* c) {
+  if (c->attn_mode == 1) return c->n_cu * attn3_wpc<DB>(c);
+  return c->n_cu * (DB <= 13 ? 2 : 1);
+}
+
+template <int DB>
+void launch_attn(kp_ctx* c, bool with_o, const float* Q, int nq, const AttnPlan& plan, float* m, float* l,
+                 float* O) {
+  if (nq <= 0) return;
+  if (c->attn_mode == 1) {
+    if (with_o)
+      launch_attn3<DB, ATT_SOFTMAX_O>(c, c->n_ent, Q, nq, plan, m, l, O, nullptr, 0.f);
+    else
+      launch_attn3<DB, ATT_SOFTMAX>(c, c->n_ent, Q, nq, plan, m, l, O, nullptr, 0.f);
+    return;
+  }
+  const size_t shm = attn_lds_bytes(DB);
+  if (with_o)
+    hipLaunchKernelGGL((kp_attn<DB, ATT_SOFTMAX_O>), dim3(plan.n_wg), dim3(256), shm, c->stream, c->dE, c->n_ent, Q,
+                       nq, plan.wk, m, l, O, nullptr, 0.f);
+  else
+    hipLaunchKernelGGL((kp_attn<DB, ATT_SOFTMAX>), dim3(plan.n_wg), dim3(256), shm, c->stream, c->dE, c->n_ent, Q,
+                       nq, plan.wk, m, l, O, nullptr, 0.f);
+  KP_HIP(hipGetLastError());
+}
+
+// kp_posttrain_rank_trace's device side (loss == nullptr: no trace): the common part and
+// ComplEx's own workspaces
+struct CxTraceDev : TraceDev {
+  double *term = nullptr, *freg_e = nullptr, *freg_r = nullptr;
+  const int32_t* targets = nullptr;
+  const int2* pairs = nullptr;
+};
+
+template <int DB, class Prod>
+void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, const CxQuery* pq,
+                   const int4* stepq, int nq, const int4* stept, int nt, const float* tsum, const float* qpair,
+                   const float* lsef, const float* am, const float* al, const float* aO, int n_split, float* contrib,
+                   float* X, float* S1, float* S2, const CxOpt& opt, const CxTraceDev& tr = {}, int step = 0,
+                   const CxMarkArgs<true>* mk = nullptr) {
+  if (n_act <= 0) return;
+  const int half = Prod::extent(c->dim);
+  KP_REQUIRE(n_split >= 1 && n_split <= 64, "cx contrib: one attention split per lane");
+  if (nq + nt > 0 && !tr.loss) {
+    hipLaunchKernelGGL((kp_cx_contrib<16 * DB, Prod>), dim3((nq + nt + 3) / 4), dim3(256), 0, c->stream, half, stepq, nq,
+                       stept, nt, pq, X, c->dR, tsum, qpair, lsef, am, al, aO, n_split, contrib, CxTraceArgs<false>{});
     KP_HIP(hipGetLastError());
   }
-  if (npairs > 0) {
-    hipLaunchKernelGGL((kp_cx_qpair<Prod, double>), dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP, half,
-                       pairs, npairs, qpair);
-    KP_HIP(hipGetLastError());
-    CX_DISPATCH(DBV, launch_attn64<DB>(c, false, qpair, npairs, ap.ranges, ap.keys_per_range, am, al, nullptr));
-    hipLaunchKernelGGL(kp_cx_lse_merge64, dim3((npairs + 255) / 256), dim3(256), 0, c->stream, npairs, ap.ranges, am,
-                       al, lsef);
-    KP_HIP(hipGetLastError());
-  }
-
-  struct LoopEvents {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~LoopEvents() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
+  if (tr.loss) {  // kp_posttrain_rank_trace: the items' loss terms, then the slots' losses, before x moves
+    if (nq + nt > 0) {
+      hipLaunchKernelGGL((kp_cx_contrib<16 * DB, Prod, true>), dim3((nq + nt + 3) / 4), dim3(256), 0, c->stream, half,
+                         stepq, nq, stept, nt, pq, X, c->dR, tsum, qpair, lsef, am, al, aO, n_split, contrib,
+                         CxTraceArgs<true>{tr.term});
+      KP_HIP(hipGetLastError());
     }
-  } lev;
-  KP_HIP(hipEventCreate(&lev.a));
-  KP_HIP(hipEventCreate(&lev.b));
-  KP_HIP(hipEventRecord(lev.a, c->stream));
+    hipLaunchKernelGGL((kp_cx_trace_sum<16 * DB, Prod>), dim3(n_act), dim3(64), 0, c->stream, half, act, plans, pq,
+                       tr.targets, tr.pairs, stept, nq, X, tr.term, tr.freg_e, tr.freg_r, opt.reg_w, opt.reg_n2,
+                       tr.off, step, tr.loss);
+    KP_HIP(hipGetLastError());
+  }
+  if (mk)  // a step that ends a marked epoch of one of its slots: the MARKS form instead, not a further launch
+    hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod, true>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq,
+                       contrib, X, S1, S2, opt, *mk);
+  else
+    hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq, contrib,
+                       X, S1, S2, opt, CxMarkArgs<false>{});
+  KP_HIP(hipGetLastError());
+}
+
+// kp_posttrain_rank_f64's: the fp64 forms, any number of key ranges, no trace and no marks
+template <int DB, class Prod>
+void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, const CxQuery* pq,
+                   const int4* stepq, int nq, const int4* stept, int nt, const double* tsum, const double* qpair,
+                   const double* lsef, const double* am, const double* al, const double* aO, int ranges,
+                   double* contrib, double* X, double* S1, double* S2, const CxOpt64& opt, const CxTraceDev& = {},
+                   int = 0, const CxMarkArgs<true>* = nullptr) {
+  if (n_act <= 0) return;
+  const int half = Prod::extent(c->dim);
+  if (nq + nt > 0) {
+    hipLaunchKernelGGL((kp_cx_contrib64<16 * DB, Prod>), dim3((nq + nt + 3) / 4), dim3(256), 0, c->stream, half, stepq,
+                       nq, stept, nt, pq, X, c->dR, tsum, qpair, lsef, am, al, aO, ranges, contrib);
+    KP_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL((kp_cx_update64<16 * DB, Prod>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq,
+                     contrib, X, S1, S2, opt);
+  KP_HIP(hipGetLastError());
+}
+
+// the fp64 queries of the rows [r0, r0 + m) of a set of rank rows, on the rows X, into the
+// set's chunk buffers
+template <int DB, class Prod, class XT = float>
+void launch_rankq64(kp_ctx* c, const XT* X, const RankSet& rr, int r0, int m) {
+  hipLaunchKernelGGL((kp_cx_rankq64<16 * DB, Prod, XT>), dim3(m), dim3(64), 0, c->stream, X, c->dR, c->dE, c->n_ent,
+                     Prod::extent(c->dim), rr.rows + 3 * (size_t)r0, m, rr.q, rr.t, rr.kcol);
+  KP_HIP(hipGetLastError());
+}
+
+#define CX_DISPATCH(DBV, ...) \
+  KP_DB_DISPATCH(DBV, 1, "ComplEx / DistMult: unsupported padded dimension", __VA_ARGS__)
+
+// Everything below is written once over the row type T: float, or double for
+// kp_posttrain_rank_f64 (rq.f64).  What a precision has of its own is an overload or an
+// `if constexpr`: the hyper-parameters' source, x0, the attention (CxAttn), launch_update,
+// the downloads.
+template <class T>
+constexpr bool is_f64 = std::is_same_v<T, double>;
+
+// the optimizer's constants of a call (step_size and bc2_sqrt follow per step): kp_hp's
+// floats, or kp_f64's doubles
+template <class T>
+CxOptT<T> make_opt(const kp_hp* hp, const kp_f64* f) {
+  CxOptT<T> opt{};
+  opt.kind = hp->optimizer;
+  if constexpr (is_f64<T>)
+    opt.lr = f->lr, opt.b1 = f->beta1, opt.b2 = f->beta2, opt.eps = f->eps, opt.reg_w = f->reg_weight;
+  else
+    opt.lr = hp->lr, opt.b1 = hp->beta1, opt.b2 = hp->beta2, opt.eps = hp->eps, opt.reg_w = hp->reg_weight;
+  opt.one_minus_b1 = (T)(1.0 - (double)opt.b1);
+  opt.one_minus_b2 = (T)(1.0 - (double)opt.b2);
+  opt.reg_n2 = hp->reg_kind == KP_REG_N2;
+  return opt;
+}
+// Adam's scalars of step t: adam_step's, or torch's on the double hyper-parameters
+inline void set_adam_step(CxOpt& opt, const kp_hp* hp, int t) {
+  const AdamStep as = adam_step(hp, t);
+  opt.step_size = as.step_size;
+  opt.bc2_sqrt = as.bc2_sqrt;
+}
+inline void set_adam_step(CxOpt64& opt, const kp_hp*, int t) {
+  const double step = (double)(t + 1);
+  opt.step_size = opt.lr / (1.0 - std::pow(opt.b1, step));
+  opt.bc2_sqrt = std::sqrt(1.0 - std::pow(opt.b2, step));
+}
+
+// The attention of a call: plan() plans the frozen-head pairs' launch and every step's, notes
+// the largest hot one (kp_last_attn_plan) and returns the partial rows (queries x parts) the
+// largest launch writes; launch() and parts() take the step t, or -1 for the pairs' launch.
+// fp32: a plan per launch for the batches in flight (attn_plan_ctx), kp_attn / kp_attn3
+struct CxAttn32 {
+  AttnPlan pairs;
+  std::vector<AttnPlan> step;  // [T]
+  size_t plan(kp_ctx* c, const CxStepPlan& sp, int npairs) {
+    int slots = 0;
+    CX_DISPATCH(c->dp / 16, slots = attn_slots_db<DB>(c));
+    pairs = attn_plan_ctx(c, std::max(npairs, 1), c->n_ent, slots, true);
+    size_t rows = (size_t)std::max(npairs, 1) * pairs.wk.n_parts;
+    step.resize(sp.T);
+    for (int t = 0; t < sp.T; ++t) {
+      const int nq = sp.q_off[t + 1] - sp.q_off[t];
+      step[t] = attn_plan_ctx(c, std::max(nq, 1), c->n_ent, slots, true);
+      if (nq > 0) attn_plan_note(c, step[t], nq, true);
+      rows = std::max(rows, (size_t)nq * step[t].wk.n_parts);
+    }
+    return rows;
+  }
+  int parts(int t) const { return (t < 0 ? pairs : step[t]).wk.n_parts; }
+  template <int DB>
+  void launch(kp_ctx* c, int t, bool with_o, const float* Q, int nq, float* m, float* l, float* O) const {
+    launch_attn<DB>(c, with_o, Q, nq, t < 0 ? pairs : step[t], m, l, O);
+  }
+};
+// fp64: the key ranges of the call's largest launch for every launch (the planner's S,
+// attn_plan_ranges; KP_ATTN_RANGES=S forces S as it does for kp_attn3), in whole 32-key planner
+// tiles: one S for the whole call keeps the partials' layout fixed.  kp_attn64, one workgroup
+// per (16 queries, range), never shared with a batch in flight
+struct CxAttn64 {
+  int ranges = 1, keys_per_range = 0;
+  size_t plan(kp_ctx* c, const CxStepPlan& sp, int npairs) {
+    const int max_nq = std::max(1, std::max(sp.max_nq, npairs));
+    const AttnPlan p = c->attn_ranges > 0 ? attn_plan_oneshot(max_nq, c->n_ent, c->attn_ranges)
+                                          : attn_plan_ranges(max_nq, c->n_ent, c->n_cu);
+    ranges = std::max(1, p.wk.ranges);
+    keys_per_range = (p.wk.ktq + ranges - 1) / ranges * 32;
+    for (int t = 0; t < sp.T; ++t) {
+      const int nq = sp.q_off[t + 1] - sp.q_off[t];
+      if (nq > 0 && nq >= c->attn_last.nq) c->attn_last = {nq, 1, ranges, ranges, (nq + A64_QT - 1) / A64_QT * ranges};
+    }
+    return (size_t)max_nq * ranges;
+  }
+  int parts(int) const { return ranges; }
+  template <int DB>
+  void launch(kp_ctx* c, int, bool with_o, const double* Q, int nq, double* m, double* l, double* O) const {
+    launch_attn64<DB>(c, with_o, Q, nq, ranges, keys_per_range, m, l, O);
+  }
+};
+
+// the device side of one call: the plan's uploads and the workspaces (c->cx.step<T>(), c->rank)
+template <class T>
+struct CxDev {
+  T *X, *S1, *S2;  // kelpie rows and optimizer state [ns][dp]
+  CxPlan* plans;
+  CxQuery* pq;
+  int32_t* tg;
+  int2* pairs;
+  int4 *acts, *stepq, *stept;
+  T *contrib, *tsum, *qpair, *lsef;
+  // the slots, kp_posttrain_rank_probes; the trace; the marks (fp64: offered none of the three,
+  // so the empty ones their upload_* return)
+  RankSet rk, probes;
+  CxTraceDev trace;
+  MarksDev marks;
+  int32_t* mark_row = nullptr;  // [acts] the mark row an active entry's update also stores, or -1
+  // the attention's: sized and planned by cx_preloop
+  T *am = nullptr, *al = nullptr, *ao = nullptr, *qs = nullptr;
+  std::conditional_t<is_f64<T>, CxAttn64, CxAttn32> attn;
+};
+
+// the plan's element types are the HIP vector types' layout: their arrays are uploaded as such
+static_assert(sizeof(CxI2) == sizeof(int2) && alignof(CxI2) == alignof(int2), "CxI2 is int2");
+static_assert(sizeof(CxI4) == sizeof(int4) && alignof(CxI4) == alignof(int4), "CxI4 is int4");
+inline const int2* as_dev(const CxI2* p) { return reinterpret_cast<const int2*>(p); }
+inline const int4* as_dev(const CxI4* p) { return reinterpret_cast<const int4*>(p); }
+
+// x0 zero-padded to [ns][dp] in `xp` and uploaded: the batch's fp32 rows (or the keyed draws,
+// upload_x0), or kp_f64's double rows
+inline float* cx_upload_x0(kp_ctx* c, DevBuf& b, const kp_batch* bt, const PostReq& rq, std::vector<float>& xp) {
+  return upload_x0(c, b, bt, xp, rq.keyed);
+}
+inline double* cx_upload_x0(kp_ctx* c, DevBuf& b, const kp_batch* bt, const PostReq& rq, std::vector<double>& xp) {
+  xp.assign((size_t)bt->n_slots * c->dp, 0.0);
+  for (int s = 0; s < bt->n_slots; ++s)
+    std::memcpy(&xp[(size_t)s * c->dp], rq.f64->x0 + (size_t)s * c->dim, sizeof(double) * c->dim);
+  return upload(c, b, xp.data(), xp.size());
+}
+// the fp32 rows a set of rank rows names as its X; the fp64 call's sets name none (their
+// queries read the double rows)
+inline const float* rank_x(const float* X) { return X; }
+inline const float* rank_x(const double*) { return nullptr; }
+inline const float* query_x(const RankSet& rr, const float*) { return rr.X; }
+inline const double* query_x(const RankSet&, const double* X) { return X; }
+
+template <class T>
+CxDev<T> cx_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq, const CxStepPlan& sp,
+                       std::vector<T>& xp) {
+  const int ns = bt->n_slots, DP = c->dp;
+  CxStepWs& w = c->cx.step<T>();
+  CxDev<T> d;
+  d.X = cx_upload_x0(c, w.x, bt, rq, xp);
+  d.S1 = ensure_n<T>(w.s1, (size_t)ns * DP);
+  d.S2 = ensure_n<T>(w.s2, (size_t)ns * DP);
+  KP_HIP(hipMemsetAsync(d.S1, 0, sizeof(T) * (size_t)ns * DP, c->stream));
+  KP_HIP(hipMemsetAsync(d.S2, 0, sizeof(T) * (size_t)ns * DP, c->stream));
+  d.plans = upload(c, w.plans, sp.plans.data(), sp.plans.size());
+  d.pq = upload(c, w.queries, sp.pqs.data(), sp.pqs.size());
+  d.tg = upload(c, w.targets, sp.targets.data(), sp.targets.size());
+  d.pairs = upload(c, w.pairs, as_dev(sp.pairs.data()), sp.pairs.size());
+  d.acts = upload(c, w.acts, as_dev(sp.acts.data()), sp.acts.size());
+  // (empty without a step, epochs == 0: upload() then only sizes the buffer)
+  d.stepq = upload(c, w.stepq, as_dev(sp.stepq.data()), sp.stepq.size());
+  d.stept = upload(c, w.stept, as_dev(sp.stept.data()), sp.stept.size());
+  d.contrib = ensure_n<T>(w.contrib, (size_t)std::max(1, sp.max_items) * DP);
+  const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
+  d.tsum = ensure_n<T>(w.tsum, (size_t)std::max(npq, 1) * DP);
+  d.qpair = ensure_n<T>(w.qpair, (size_t)std::max(npairs, 1) * DP);
+  d.lsef = ensure_n<T>(w.lsef, (size_t)std::max(npairs, 1));
+
+  // the ranking's inputs and buffers now, ahead of the step loop: an upload from pageable
+  // memory after the loop waited for the whole loop on the device, so the rank kernels
+  // were enqueued only then (a host round trip per batch with the context idle)
+  // (the fp64 call's slots are a set of rank rows of its own, c->rank.f64)
+  const float* xr = rank_x(d.X);
+  d.rk = upload_slots(c, is_f64<T> ? c->rank.f64 : c->rank.slots, bt, rq, xr);
+  d.probes = upload_probes(c, bt, rq, xr);
+  // kp_posttrain_rank_marks: the mark rows (each the padded x0 until a step captures it)
+  d.marks = upload_marks(c, c->cx.marks, hp, bt, rq, xr);
+  if (d.marks.nm > 0) {
+    const std::vector<int32_t> mr = marks_act_rows(d.marks, sp.act_off, sp.T, [&](int i) { return sp.acts[i].x; });
+    d.mark_row = upload(c, c->cx.mark_row, mr.data(), mr.size());
+  }
+  if (rq.trace) {  // the trace's offsets and workspaces, with the call's other uploads
+    CxTraceDev& t = d.trace;
+    static_cast<TraceDev&>(t) = upload_trace(c, bt, rq);
+    t.term = ensure_n<double>(c->cx.tr_term, (size_t)std::max(1, sp.max_items));
+    t.freg_e = ensure_n<double>(c->cx.tr_fe, (size_t)c->n_ent);
+    t.freg_r = ensure_n<double>(c->cx.tr_fr, (size_t)c->n_rel2);
+    t.targets = d.tg;
+    t.pairs = d.pairs;
+  }
+  return d;
+}
+
+// before the loop: the queries' frozen-target sums, the attention plans and workspaces of
+// every step, and the frozen-head pairs' q and frozen log-sum-exp
+template <class Prod, class T>
+void cx_preloop(kp_ctx* c, const CxStepPlan& sp, CxDev<T>& d, const CxOptT<T>& opt) {
+  const int DP = c->dp, DBV = DP / 16;
+  const int npq = (int)sp.pqs.size(), npairs = (int)sp.pairs.size();
+  CxStepWs& w = c->cx.step<T>();
+  KP_HIP(hipEventRecord(c->ev0, c->stream));
+  if (npq > 0) {
+    hipLaunchKernelGGL(kp_cx_tsum<T>, dim3(npq), dim3(128), 0, c->stream, c->dE, DP, d.pq, npq, d.tg, d.tsum);
+    KP_HIP(hipGetLastError());
+  }
+  if (d.trace.loss && opt.reg_w != 0 && sp.T > 0) {  // the frozen rows' regulariser factors, once per batch
+    const int half = Prod::extent(c->dim);
+    hipLaunchKernelGGL(kp_cx_rowreg<Prod>, dim3((c->n_ent + 3) / 4), dim3(256), 0, c->stream, c->dE, c->n_ent, DP, half,
+                       opt.reg_n2, d.trace.freg_e);
+    KP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kp_cx_rowreg<Prod>, dim3((c->n_rel2 + 3) / 4), dim3(256), 0, c->stream, c->dR, c->n_rel2, DP,
+                       half, opt.reg_n2, d.trace.freg_r);
+    KP_HIP(hipGetLastError());
+  }
+  c->attn_last = {};
+  const size_t att_rows = d.attn.plan(c, sp, npairs);
+  d.am = ensure_n<T>(w.am, att_rows);
+  d.al = ensure_n<T>(w.al, att_rows);
+  d.ao = ensure_n<T>(w.ao, att_rows * DP);
+  d.qs = ensure_n<T>(w.qs, (size_t)std::max(sp.max_nq, 1) * DP);
+  if (npairs > 0) {
+    hipLaunchKernelGGL((kp_cx_qpair<Prod, T>), dim3(npairs), dim3(128), 0, c->stream, c->dE, c->dR, DP,
+                       Prod::extent(c->dim), d.pairs, npairs, d.qpair);
+    KP_HIP(hipGetLastError());
+    CX_DISPATCH(DBV, d.attn.template launch<DB>(c, -1, false, d.qpair, npairs, d.am, d.al, nullptr));
+    // combine the partials into lsef on the device (no host round trip inside the batch)
+    hipLaunchKernelGGL(kp_cx_lse_merge<T>, dim3((npairs + 255) / 256), dim3(256), 0, c->stream, npairs,
+                       d.attn.parts(-1), d.am, d.al, d.lsef);
+    KP_HIP(hipGetLastError());
+  }
+}
+
+// the epoch/step loop: per step the queries, their attention over the frozen entities and
+// the update of every active slot.  Returns the hot (attention) launches; t_steps: the host
+// time after enqueueing steps 0, 1, T/2, T-1 (KP_HOST_TIMES)
+template <class Prod, class T>
+int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxDev<T>& d, CxOptT<T> opt,
+                     double* t_steps) {
+  const int DBV = c->dp / 16, steps = sp.T;
   int64_t hot_launches = 0;
   c->hot_pairs.clear();
   c->hot_iv.clear();
-  for (int t = 0; t < sp.T; ++t) {
+  for (int t = 0; t < steps; ++t) {
     const int nq = sp.q_off[t + 1] - sp.q_off[t];
-    const int nt = sp.t_off[t + 1] - sp.t_off[t];
     const int na = sp.act_off[t + 1] - sp.act_off[t];
     hipEvent_t ea = nullptr, eb = nullptr;
     if (nq > 0 && c->time_hot) {
       ea = c->event(2 * hot_launches);
       eb = c->event(2 * hot_launches + 1);
     }
-    CX_DISPATCH(DBV, (launch_stepq<DB, Prod, double>(c, stepq + sp.q_off[t], X, nq, qs)));
+    CX_DISPATCH(DBV, (launch_stepq<DB, Prod, T>(c, d.stepq + sp.q_off[t], d.X, nq, d.qs)));
     if (nq > 0 && c->time_hot) KP_HIP(hipEventRecord(ea, c->stream));
-    CX_DISPATCH(DBV, launch_attn64<DB>(c, true, qs, nq, ap.ranges, ap.keys_per_range, am, al, ao));
+    CX_DISPATCH(DBV, d.attn.template launch<DB>(c, t, true, d.qs, nq, d.am, d.al, d.ao));
     if (nq > 0) {
       if (c->time_hot) {
         KP_HIP(hipEventRecord(eb, c->stream));
         c->hot_pairs.push_back({(double)nq, 0.0});
       }
       ++hot_launches;
-      if (nq >= c->attn_last.nq) {
-        c->attn_last.nq = nq;
-        c->attn_last.inflight = 1;
-        c->attn_last.ranges = ap.ranges;
-        c->attn_last.n_parts = ap.ranges;
-        c->attn_last.n_wg = (nq + A64_QT - 1) / A64_QT * ap.ranges;
-      }
     }
-    if (na <= 0) continue;
-    // Adam's step scalars from the double hyper-parameters (torch: lr / (1 - b1^t), sqrt(1 - b2^t))
-    const double step = (double)(t + 1);
-    opt.step_size = f.lr / (1.0 - std::pow(f.beta1, step));
-    opt.bc2_sqrt = std::sqrt(1.0 - std::pow(f.beta2, step));
-    if (nq + nt > 0) {
-      CX_DISPATCH(DBV, hipLaunchKernelGGL((kp_cx_contrib64<16 * DB, Prod>), dim3((nq + nt + 3) / 4), dim3(256), 0,
-                                          c->stream, half, stepq + sp.q_off[t], nq, stept + sp.t_off[t], nt, pq, X,
-                                          c->dR, tsum, qpair, lsef, am, al, ao, ap.ranges, contrib));
-      KP_HIP(hipGetLastError());
+    set_adam_step(opt, hp, t);
+    const CxMarkArgs<true> mk{d.mark_row ? d.mark_row + sp.act_off[t] : nullptr, d.marks.X};
+    CX_DISPATCH(DBV, launch_update<DB, Prod>(c, na, d.acts + sp.act_off[t], d.plans, d.pq, d.stepq + sp.q_off[t], nq,
+                                             d.stept + sp.t_off[t], sp.t_off[t + 1] - sp.t_off[t], d.tsum, d.qpair,
+                                             d.lsef, d.am, d.al, d.ao, d.attn.parts(t), d.contrib, d.X, d.S1, d.S2,
+                                             opt, d.trace, t, marks_at_step(d.marks, t) ? &mk : nullptr));
+    if (g_host_times) {
+      if (t == 0) t_steps[0] = host_ms();
+      if (t == 1) t_steps[1] = host_ms();
+      if (t == steps / 2) t_steps[2] = host_ms();
+      if (t == steps - 1) t_steps[3] = host_ms();
     }
-    CX_DISPATCH(DBV, hipLaunchKernelGGL((kp_cx_update64<16 * DB, Prod>), dim3(na), dim3(256), 0, c->stream, half,
-                                        acts + sp.act_off[t], plans, nq, contrib, X, S1, S2, opt));
-    KP_HIP(hipGetLastError());
   }
-  KP_HIP(hipEventRecord(lev.b, c->stream));
+  return hot_launches;
+}
 
-  // ---- the rank on the fp64 row; out_score is the fp64 target value itself
-  rank_rows(c, rk, RANK64_DOT, [c, X, DBV](const RankSet& rr, int r0, int m) {
-    CX_DISPATCH(DBV, (launch_rankq64<DB, Prod, double>(c, X, rr, r0, m)));
-  });
-  KP_HIP(hipEventRecord(c->ev1, c->stream));
-  if (f.out_x) KP_HIP(hipMemcpyAsync(xp.data(), X, sizeof(double) * xp.size(), hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(f.out_score, rk.t, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
-  KP_HIP(hipMemcpyAsync(bt->out_rank, rk.rank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
+// the tail of a call (returns the host time at which the wait began, KP_HOST_TIMES): every
+// result the fp32 call was asked for (download_results); or the fp64 call's rows (when out_x
+// is set), its fp64 target values as out_score and its ranks, one wait, the rows' unpadding
+inline double cx_download(kp_ctx* c, const kp_batch* bt, const PostReq& rq, const CxDev<float>& d,
+                          std::vector<float>& xp) {
+  return download_results(c, bt, d.X, d.rk, xp, rq, d.probes, d.trace, d.marks);
+}
+inline double cx_download(kp_ctx* c, const kp_batch* bt, const PostReq& rq, const CxDev<double>& d,
+                          std::vector<double>& xp) {
+  const kp_f64& f = *rq.f64;
+  const int ns = bt->n_slots;
+  if (f.out_x) KP_HIP(hipMemcpyAsync(xp.data(), d.X, sizeof(double) * xp.size(), hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipMemcpyAsync(f.out_score, d.rk.t, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
+  KP_HIP(hipMemcpyAsync(bt->out_rank, d.rk.rank, sizeof(int64_t) * ns, hipMemcpyDeviceToHost, c->stream));
+  const double t_wait = g_host_times ? host_ms() : 0.0;
   KP_HIP(hipStreamSynchronize(c->stream));
   if (f.out_x)
-    for (int s = 0; s < ns; ++s) std::memcpy(f.out_x + (size_t)s * dim, &xp[(size_t)s * DP], sizeof(double) * dim);
+    for (int s = 0; s < ns; ++s)
+      std::memcpy(f.out_x + (size_t)s * c->dim, &xp[(size_t)s * c->dp], sizeof(double) * c->dim);
+  return t_wait;
+}
+
+// loop-interval events, destroyed on every exit path (a KP_HIP / KP_REQUIRE throws)
+struct LoopEvents {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~LoopEvents() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+
+// a checked and planned call on the device, in the row type T: workspaces, the step loop, the
+// ranks, the downloads and the timing
+template <class Prod, class T>
+void cx_run(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq, const CxStepPlan& sp, double t_in,
+            double t_plan) {
+  const CxOptT<T> opt = make_opt<T>(hp, rq.f64);
+  std::vector<T> xp;
+  CxDev<T> d = cx_workspaces<T>(c, hp, bt, rq, sp, xp);
+  cx_preloop<Prod>(c, sp, d, opt);
+
+  LoopEvents lev;
+  KP_HIP(hipEventCreate(&lev.a));
+  KP_HIP(hipEventCreate(&lev.b));
+  KP_HIP(hipEventRecord(lev.a, c->stream));
+  const double t_loop0 = g_host_times ? host_ms() : 0.0;
+  double t_steps[4] = {0, 0, 0, 0};
+  const int64_t hot_launches = cx_step_loop<Prod>(c, hp, sp, d, opt, t_steps);
+  KP_HIP(hipEventRecord(lev.b, c->stream));
+
+  // ---- ranking: scores of (kelpie, p, .) over E plus the kelpie column, in fp64
+  // (launch_rank_f64: at the reference init the target's neighbours are ~1e-5 relative away)
+  // the slots, then the probes on the slots' rows, then the marks on the mark workspace; the
+  // fp64 call's slots on its double rows (its out_score is the set's fp64 target value itself)
+  const auto queries = [c, X = d.X](const RankSet& rr, int r0, int m) {
+    CX_DISPATCH(c->dp / 16, (launch_rankq64<DB, Prod, T>(c, query_x(rr, X), rr, r0, m)));
+  };
+  for (const RankSet* set : {&d.rk, &d.probes, &d.marks.rows}) rank_rows(c, *set, RANK64_DOT, queries);
+  KP_HIP(hipEventRecord(c->ev1, c->stream));
+
+  const double t_enq = cx_download(c, bt, rq, d, xp);
+  const double t_done = g_host_times ? host_ms() : 0.0;
+  if (g_host_times)
+    std::fprintf(stderr,
+                 "[kp_cx] slots %d steps %d: plan %.2f ms, enqueue %.2f ms (uploads+pairs %.2f, step 0 %.2f, step 1 "
+                 "%.2f, to T/2 %.2f, to T-1 %.2f), wait %.2f ms\n",
+                 bt->n_slots, sp.T, t_plan - t_in, t_enq - t_plan, t_loop0 - t_plan, t_steps[0] - t_loop0,
+                 t_steps[1] - t_steps[0], t_steps[2] - t_steps[1], t_steps[3] - t_steps[2], t_done - t_enq);
   record_hot_timing(c, hot_launches, lev.a, lev.b);
 }
 
 // The batched post-training and rank of a model whose step is a 1-vs-all softmax over
 // q = lhs o rel (product policy Prod): planning (kp_cx_plan.hpp), workspaces, attention
-// planning and timing are the model's only through Prod.
+// planning and timing are the model's only through Prod, and the precision's
+// (kp_posttrain_rank_f64: rq.f64) only through cx_run's row type.
 // KP_HOST_TIMES=1 (kp_posttrain.hpp) prints the host time before the first upload (checks
 // and planning), up to the last launch enqueued, and waiting for the device
 template <class Prod>
 void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostReq& rq) {
-  if (rq.f64) return posttrain_rank_f64<Prod>(c, hp, bt, rq);  // kp_posttrain_rank_f64
   const std::string who = kp_model_name(c->model);
   const double t_in = g_host_times ? host_ms() : 0.0;
   const int ns = bt->n_slots;
@@ -1371,7 +1362,7 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostRe
   // every id is checked before it indexes a host vector or a device table, as in every
   // model family (kp_batch_check.hpp)
   require_request(c, hp, bt, rq, true, kp_model_name(c->model));
-  const CxOpt opt = make_opt(hp, who);
+  KP_REQUIRE(hp->reg_kind == KP_REG_N3 || hp->reg_kind == KP_REG_N2, who + ": unknown regulariser");
 
   // an armed call (kp_ctx_arm_keyed): the step plan is host work, so the permutations of the
   // multi-step slots (R > batch_size; none in most batches) are generated on the device and
@@ -1400,46 +1391,12 @@ void posttrain_rank(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const PostRe
   if (const char* why = cx_step_plan(c->n_ent, c->n_rel2, hp->batch_size, hp->epochs, bt, sp))
     throw KpError{KP_EINVAL, who + ": " + why};
   const double t_plan = g_host_times ? host_ms() : 0.0;
-
-  std::vector<float> xp;
-  CxDev d = cx_workspaces(c, hp, bt, rq, sp, xp);
-  cx_preloop<Prod>(c, sp, d, opt.reg_w, opt.reg_n2);
-
-  // loop-interval events, destroyed on every exit path (a KP_HIP / KP_REQUIRE below throws)
-  struct LoopEvents {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~LoopEvents() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } lev;
-  KP_HIP(hipEventCreate(&lev.a));
-  KP_HIP(hipEventCreate(&lev.b));
-  KP_HIP(hipEventRecord(lev.a, c->stream));
-  const double t_loop0 = g_host_times ? host_ms() : 0.0;
-  double t_steps[4] = {0, 0, 0, 0};
-  const int64_t hot_launches = cx_step_loop<Prod>(c, hp, sp, d, opt, t_steps);
-  KP_HIP(hipEventRecord(lev.b, c->stream));
-
-  // ---- ranking: scores of (kelpie, p, .) over E plus the kelpie column, in fp64
-  // (launch_rank_f64: at the reference init the target's neighbours are ~1e-5 relative away)
-  // the slots, then the probes on the slots' rows, then the marks on the mark workspace
-  const auto queries = [c](const RankSet& rr, int r0, int m) {
-    CX_DISPATCH(c->dp / 16, launch_rankq64<DB, Prod>(c, rr.X, rr, r0, m));
-  };
-  for (const RankSet* set : {&d.rk, &d.probes, &d.marks.rows}) rank_rows(c, *set, RANK64_DOT, queries);
-  KP_HIP(hipEventRecord(c->ev1, c->stream));
-
-  const double t_enq = download_results(c, bt, d.X, d.rk, xp, rq, d.probes, d.trace, d.marks);
-  const double t_done = g_host_times ? host_ms() : 0.0;
-  if (g_host_times)
-    std::fprintf(stderr,
-                 "[kp_cx] slots %d steps %d: plan %.2f ms, enqueue %.2f ms (uploads+pairs %.2f, step 0 %.2f, step 1 "
-                 "%.2f, to T/2 %.2f, to T-1 %.2f), wait %.2f ms\n",
-                 ns, sp.T, t_plan - t_in, t_enq - t_plan, t_loop0 - t_plan, t_steps[0] - t_loop0,
-                 t_steps[1] - t_steps[0], t_steps[2] - t_steps[1], t_steps[3] - t_steps[2], t_done - t_enq);
-  record_hot_timing(c, hot_launches, lev.a, lev.b);
+  if (rq.f64)
+    cx_run<Prod, double>(c, hp, bt, rq, sp, t_in, t_plan);
+  else
+    cx_run<Prod, float>(c, hp, bt, rq, sp, t_in, t_plan);
 }
+
 
 }  // namespace
 

@@ -13,7 +13,12 @@ The rank's four sets of rows (the slots, the probes, the marks, the fp64 call's 
 workspace type, so the same sequence runs once more with every request on -- the lists, two
 probes, the trace, two marks and the margins -- at the narrowest widths that still reach every
 buffer (ComplEx rows of 32 floats, TransE d = 16, ConvE d = 60), and every reported value has
-to come back."""
+to come back.
+
+The ComplEx / DistMult step's workspaces are one type held twice, for fp32 and for fp64: two
+instances bound, sized or indexed as each other would again only give wrong numbers.  So the
+sequence runs with ``precision = "fp64"`` as well, and once with an fp32 batch of every request
+regrowing the fp32 instance between two equal fp64 batches on one context."""
 import pytest
 
 from golden_io import seed_all
@@ -79,8 +84,8 @@ def test_workspaces_survive_regrowth(name):
 DIM_NARROW = {"ComplEx": 16, "TransE": 16, "ConvE": 60}  # ComplEx: rows of 2 * 16 floats
 
 
-def _extras_engine(name, ds, w):
-    eng = ka.NecessaryPostTrainingEngine(_model(name, ds, w), ds, HP[name])
+def _extras_engine(name, ds, w, model=None):
+    eng = ka.NecessaryPostTrainingEngine(model or _model(name, ds, w), ds, HP[name])
     eng.top_k = 3
     eng.trace = True
     eng.marks = [1, 3]
@@ -121,5 +126,68 @@ def test_workspaces_survive_regrowth_with_every_request(name):
         assert 0 < len(pt["top_ids"]) == len(pt["top_scores"]) <= 3
         assert len(pt["probes"]) == 2 and len(pt["marks"]) == 2
         assert pt["loss"] and pt["margins"]["tol"] == 1e-4
+    assert again == first, (first, again)
+    assert middle == fresh, (middle, fresh)
+
+
+FP64 = {"ComplEx": 16, "DistMult": 24}  # rows of 32 floats (DB 2) and of 24 padded to 32 (DB 2)
+
+
+def _fp64_model(name, ds, g, seed=9):
+    from kelpie_amd import synth
+    w = synth.make_weights(name, g.num_entities, g.num_relations, FP64[name], seed=seed)
+    cls = ka.ComplEx if name == "ComplEx" else ka.DistMult
+    return cls(ds, w["entity_embeddings"], w["relation_embeddings"], init_scale=1e-3)
+
+
+def _fp64_engine(model, ds):
+    eng = ka.NecessaryPostTrainingEngine(model, ds, HP["ComplEx"])
+    eng.precision = "fp64"
+    return eng
+
+
+@pytest.mark.parametrize("name", ["ComplEx", "DistMult"])
+def test_workspaces_survive_regrowth_fp64(name):
+    from kelpie_amd import synth
+    g = synth.make_graph("small", seed=9)
+    ds = ka.Dataset(g.num_entities, g.num_relations, g.train, g.valid, g.test)
+    deg = ds.entity_to_degree
+    pred = next(tuple(int(v) for v in t) for t in g.test if 12 <= deg.get(int(t[0]), 0) <= 40)
+    cands = sorted(ds.entity_to_training_triples[pred[0]])[:12]
+    assert len(cands) == 12
+
+    eng = _fp64_engine(_fp64_model(name, ds, g), ds)
+    first = _run(eng, pred, cands[:2])
+    middle = _run(eng, pred, cands)
+    again = _run(eng, pred, cands[:2])
+    fresh = _run(_fp64_engine(_fp64_model(name, ds, g), ds), pred, cands)
+
+    assert len(first[1]) == 2 and len(middle[1]) == 12
+    assert all(isinstance(v[1], float) and v[1] == v[1] for v in middle[1])  # the fp64 scores, none a NaN
+    assert again == first, (first, again)
+    assert middle == fresh, (middle, fresh)
+
+
+def test_fp64_survives_fp32_requests():
+    """The mirror of test_f64_gpu.py's test_fp32_results_are_unchanged_by_an_fp64_call, with
+    regrowth between: an fp64 batch of 2, an fp32 batch of 12 with every request on, the fp64
+    batch of 2 again, all on one context."""
+    from kelpie_amd import synth
+    g = synth.make_graph("small", seed=9)
+    ds = ka.Dataset(g.num_entities, g.num_relations, g.train, g.valid, g.test)
+    w = synth.make_weights("ComplEx", g.num_entities, g.num_relations, FP64["ComplEx"], seed=9)
+    train = ds.entity_to_training_triples
+    pred = next(tuple(int(v) for v in t) for t in g.test if 14 <= len(train.get(int(t[0]), ())) <= 40)
+    own = sorted(train[pred[0]])
+    cands, probes = own[:12], own[12:14]
+
+    model = _model("ComplEx", ds, w)
+    eng64 = _fp64_engine(model, ds)
+    first = _run(eng64, pred, cands[:2])
+    middle = _run_extras(_extras_engine("ComplEx", ds, w, model), pred, cands, probes)
+    again = _run(eng64, pred, cands[:2])
+    fresh = _run_extras(_extras_engine("ComplEx", ds, w), pred, cands, probes)
+
+    assert len(first[1]) == 2 and len(middle[1]) == 12
     assert again == first, (first, again)
     assert middle == fresh, (middle, fresh)

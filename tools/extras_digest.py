@@ -6,9 +6,11 @@ For marks_cases' four family cases (the ones tests/test_marks_gpu.py calls FAMIL
 engine batch runs again directly with topk = 5, seven probes per slot, the trace, the case's
 marks and the margins at tol = 1e-4; one sha256 per output is printed (one per margin array of
 the slots, the probes and the marks), then the median ``last_timing()["device_s"]``
-of five repeats after one warm-up.  Only ``Context.posttrain_rank``'s public keywords and
-``marks_cases.run`` are used, so the same file runs on an older checkout: two builds compute
-the same bits exactly when their lines are equal (KELPIE_HIP_LIB selects the library).
+of five repeats after one warm-up.  Then, for kp_posttrain_rank_f64, one sha256 per case of
+f64_cases.ALL over every slot's fp64 score, rank and row.  Only ``Context.posttrain_rank``'s
+public keywords, ``marks_cases.run`` and ``f64_cases.run`` are used, so the same file runs on an
+older checkout: two builds compute the same bits exactly when their lines are equal
+(KELPIE_HIP_LIB selects the library).
 """
 import hashlib
 import os
@@ -74,6 +76,25 @@ def main():
             call()
             times.append(ctx.last_timing()["device_s"])
         print(f"{case['id']} device_s_median {statistics.median(times):.6e}")
+    fp64_block()
+
+
+def fp64_block():
+    """kp_posttrain_rank_f64: for every case of f64_cases.ALL one sha256 over every recorded
+    slot's fp64 score, rank and row, through a recording wrapper of the device's context as
+    tests/test_f64_gpu.py runs them (the forced key ranges under KP_ATTN_RANGES)."""
+    import f64_cases as fc
+    from f64_backend import F64Recording
+
+    for case in fc.ALL:
+        if "ranges" in case:
+            os.environ["KP_ATTN_RANGES"] = str(case["ranges"])  # read when the context is created
+        try:
+            slots = fc.run(case, lambda m: F64Recording(m.ctx))
+        finally:
+            os.environ.pop("KP_ATTN_RANGES", None)
+        digest = sha(*(a for s in slots for a in (np.float64(s["score"]), np.int64(s["rank"]), s["x"])))
+        print(f"fp64 {case['id']} slots {len(slots)} {digest}")
 
 
 if __name__ == "__main__":
