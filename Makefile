@@ -73,8 +73,10 @@ build/san/host_tsan: $(SAN_SRC) include/kelpie_hip.h
 #   marks_check  the epoch marks' check, plan and rank rows (kp_marks_check.hpp)
 #   keyed        the keyed draws' generator, streams, word counts and request check (kp_keyed.hpp)
 #   margins      the rank margins' request check and threshold rule (kp_margins_check.hpp)
-DRIVERS := batch_check attn_plan step_plan probe_check trace_check marks_check keyed margins
+#   attrib       the attributions' request check and the step plan's row map (kp_attrib_check.hpp, kp_cx_rowmap.hpp)
+DRIVERS := batch_check attn_plan step_plan probe_check trace_check marks_check keyed margins attrib
 DRIVER_DEP := $(wildcard kelpie_amd/csrc/kp_*_check.hpp kelpie_amd/csrc/kp_*_plan.hpp) kelpie_amd/csrc/kp_keyed.hpp \
+              kelpie_amd/csrc/kp_cx_rowmap.hpp \
               include/kelpie_hip.h
 $(DRIVERS) $(DRIVERS:%=%_asan): %: build/san/%
 batch_asan: build/san/batch_check_asan

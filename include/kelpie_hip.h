@@ -368,6 +368,55 @@ int kp_posttrain_rank_margins(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batc
                               float* out_scores, const kp_probes* probes, const kp_trace* trace,
                               const kp_marks* marks, const kp_margins* margins);
 
+/* ---- Attributions: every post-training's score change split over its training rows ----
+ * For the bilinear families (ComplEx, DistMult) the target score is linear in the kelpie row,
+ * s(x) = <c, x> with c = grad_x score(kelpie, p, o), and every Adagrad or SGD step is a
+ * diagonal matrix applied to a sum of per-row gradients, so s(x_T) - s(x_0) splits exactly
+ * into one number per training row plus the regulariser's share.  This is the only definition.
+ *
+ * Per slot, x_t is the kelpie row before step t and B_t the step's minibatch of b_t rows (the
+ * rows of kp_batch.rows: the kelpie triples followed by their inverses).  All columns
+ * 0 .. n_ent count, the kelpie column included.
+ *
+ * Row gradient gamma_i(x) = grad_x [lse_i(x) - s_{i,target}(x)], everything but x frozen:
+ *   row (K, r, t), t frozen:  J_r^T (<E> - E_t) + p_k q,   q = x o r,
+ *                             <E> = sum_e p_e E_e + p_k x,  p_k the kelpie column's softmax weight
+ *   row (K, r, K):            J_r^T (<E> - x) + (p_k - 1) q
+ *   row (h, r, K), h frozen:  (p_k - 1) q_pair
+ * Regulariser gradient rho_i(x) = occ_i * 3 w |x| o x (N3) or occ_i * 3 w ||f|| x (N2), occ_i in
+ * {1, 2} the number of times the kelpie occurs in the row; |.| and ||.|| are the family's moduli
+ * (the complex modulus of a (re, im) pair for ComplEx, |x_i| for DistMult).
+ *
+ * Step: g_t = (1 / b_t) sum_{i in B_t} (gamma_i + rho_i) and x_{t+1} - x_t = -D_t o g_t, with
+ * D_t = lr (SGD) or lr / (sqrt(s_t) + eps) (Adagrad, s_t the state after this step's
+ * accumulation), in the step's own fp32 arithmetic.
+ *
+ * Attributions, accumulated in fp64 in a fixed order with one writer per row:
+ *   fit_i = sum_{t: i in B_t} -(1 / b_t) <c o D_t, gamma_i(x_t)>
+ *   reg_i = sum_{t: i in B_t} -(1 / b_t) <c o D_t, rho_i(x_t)>
+ * delta = <c, x_T - x_0> in fp64 from the fp32 rows; sum_i (fit_i + reg_i) = delta up to the
+ * fp32 rounding of the updates, and s(x_0) = out_score - delta.  Rows that are never stepped
+ * (epochs = 0) keep 0; a slot without rows writes nothing to out_fit / out_reg.  Duplicate rows
+ * of a slot get equal values only when they share every minibatch (R <= batch_size). */
+typedef struct {
+  double* out_fit;   /* [row_off[n_slots]] */
+  double* out_reg;   /* [row_off[n_slots]] */
+  double* out_delta; /* [n_slots] */
+} kp_attrib;
+
+/* kp_posttrain_rank_margins, plus the attributions.  Every other output of the call (out_x,
+ * out_score, out_rank, the lists, the probes, the trace, the marks, the margins) is bit for bit
+ * what it is without attributions.  attrib == NULL is kp_posttrain_rank_margins.  Refusals,
+ * after the margins check and before any upload, the first rule broken: KP_EINVAL for a NULL
+ * out_fit, out_reg or out_delta with rows to write; KP_ENOTSUP for a context that is not ComplEx
+ * or DistMult (TransE's and ConvE's scores are not linear in the row), for
+ * hp->optimizer == KP_OPT_ADAM (its momentum would need one vector per training row), and for
+ * a slot whose pred tail is the kelpie entity (its score is quadratic in x).  Keyed draws are
+ * served.  Not offered on kp_posttrain_rank_f64. */
+int kp_posttrain_rank_attrib(kp_ctx* ctx, const kp_hp* hp, const kp_batch* batch, int32_t k, int32_t* out_ids,
+                             float* out_scores, const kp_probes* probes, const kp_trace* trace,
+                             const kp_marks* marks, const kp_margins* margins, const kp_attrib* attrib);
+
 /* ---- fp64: post-train and rank in double precision on the device (ComplEx, DistMult) ----
  * The fp64 result of a slot is what the reference returns when every tensor of the run is a
  * float64 one (the `fp64` variant of tools/conditioning.py):

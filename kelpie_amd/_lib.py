@@ -32,7 +32,7 @@ EXPORTS = ["kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_posttrain_ran
            "kp_conve_train_step", "kp_conve_train_read", "kp_host_alloc", "kp_host_free", "kp_ctx_set_inflight",
            "kp_last_attn_plan", "kp_posttrain_rank_topk", "kp_posttrain_rank_probes", "kp_trace_steps",
            "kp_posttrain_rank_trace", "kp_posttrain_rank_marks", "kp_posttrain_rank_f64", "kp_ctx_arm_keyed",
-           "kp_keyed_rng_words", "kp_keyed_draws", "kp_posttrain_rank_margins"]
+           "kp_keyed_rng_words", "kp_keyed_draws", "kp_posttrain_rank_margins", "kp_posttrain_rank_attrib"]
 
 
 class ModelDesc(C.Structure):
@@ -101,6 +101,11 @@ class Margins(C.Structure):
     """kp_margins: the tolerance and the slots', probes' and marks' outputs (include/kelpie_hip.h,
     "Rank margins")."""
     _fields_ = [("tol", C.c_double), ("slots", MarginOut), ("probes", MarginOut), ("marks", MarginOut)]
+
+
+class Attrib(C.Structure):
+    """kp_attrib: the attributions' outputs (include/kelpie_hip.h, "Attributions")."""
+    _fields_ = [("out_fit", C.c_void_p), ("out_reg", C.c_void_p), ("out_delta", C.c_void_p)]
 
 
 MARGIN_FIELDS = (("rank_lo", np.int64), ("rank_hi", np.int64), ("ties", np.int64), ("gap_better", np.float64),
@@ -192,6 +197,10 @@ def lib():
             L.kp_posttrain_rank_margins.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
                                                     C.c_void_p, C.POINTER(Probes), C.POINTER(Trace), C.POINTER(Marks),
                                                     C.POINTER(Margins)]
+        if hasattr(L, "kp_posttrain_rank_attrib"):  # KELPIE_HIP_LIB may name a build from before the attributions
+            L.kp_posttrain_rank_attrib.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.c_int32, C.c_void_p,
+                                                   C.c_void_p, C.POINTER(Probes), C.POINTER(Trace), C.POINTER(Marks),
+                                                   C.POINTER(Margins), C.POINTER(Attrib)]
         if hasattr(L, "kp_posttrain_rank_f64"):  # KELPIE_HIP_LIB may name a build from before the fp64 path
             L.kp_posttrain_rank_f64.argtypes = [C.c_void_p, C.POINTER(HP), C.POINTER(Batch), C.POINTER(F64)]
         if hasattr(L, "kp_ctx_arm_keyed"):  # KELPIE_HIP_LIB may name a build from before the keyed draws
@@ -498,14 +507,15 @@ class RankResult(NamedTuple):
     loss: object = None    # one array per slot
     marks: object = None   # (scores, ranks, rows or None)
     margins: object = None  # (slots, probes or None, marks or None): dicts of MARGIN_FIELDS arrays
+    attrib: object = None  # (fit float64 [rows], reg float64 [rows], delta float64 [n])
 
 
-def split_rank_result(out, topk=0, probes=None, trace=False, marks=None, margins=None) -> RankResult:
+def split_rank_result(out, topk=0, probes=None, trace=False, marks=None, margins=None, attrib=False) -> RankResult:
     """``Context.posttrain_rank``'s tuple (of a context or of a stand-in that follows its
     convention) by name, given the requests the call was made with: the optional elements
-    follow (scores, ranks, rows) in the order topk, probes, trace, marks, margins, each only
-    when asked for."""
-    asked = (bool(topk), probes is not None, bool(trace), marks is not None, margins is not None)
+    follow (scores, ranks, rows) in the order topk, probes, trace, marks, margins, attrib, each
+    only when asked for."""
+    asked = (bool(topk), probes is not None, bool(trace), marks is not None, margins is not None, bool(attrib))
     if len(out) != 3 + sum(asked):
         raise ValueError(f"posttrain_rank returned {len(out)} elements for {sum(asked)} optional requests")
     rest = iter(out[3:])
@@ -549,7 +559,7 @@ class Context:
             pass
 
     def posttrain_rank(self, hp: HP, x0, row_off, rows, rng_off, rng, pred, filt_off, filt, want_x=False, topk=0,
-                       probes=None, trace=False, marks=None, margins=None):
+                       probes=None, trace=False, marks=None, margins=None, attrib=False):
         """kp_posttrain_rank: (target scores, ranks, final rows or None).  With ``topk`` > 0
         (kp_posttrain_rank_topk) a fourth element: (ids int32 [n][topk], scores float32
         [n][topk]), the slots' best unmasked tails, -1 / 0 past the last one.  With ``probes``
@@ -564,7 +574,11 @@ class Context:
         ``margins`` = a tolerance in [0, 1] (kp_posttrain_rank_margins) a last element after
         that: (slots, probes, marks), each a dict of arrays ``rank_lo``, ``rank_hi``, ``ties``
         (int64), ``gap_better``, ``gap_worse`` (float64), ``id_better``, ``id_worse`` (int32)
-        shaped as that kind's ranks ([n], [m], [n][marks]), None for a kind the call has not."""
+        shaped as that kind's ranks ([n], [m], [n][marks]), None for a kind the call has not.
+        With ``attrib`` (kp_posttrain_rank_attrib; ComplEx and DistMult, Adagrad and SGD) a last
+        element after that: (fit float64 [rows], reg float64 [rows], delta float64 [n]), the
+        split of every slot's score change over its training rows (include/kelpie_hip.h,
+        "Attributions")."""
         topk = int(topk)
         if not 0 <= topk <= 32:
             raise ValueError(f"topk must be in [0, 32], got {topk}")
@@ -583,7 +597,7 @@ class Context:
         out_r = np.zeros(n, np.int64)
         b = Batch(n, _ptr(x0), _ptr(row_off), _ptr(rows), _ptr(rng_off), _ptr(rng), _ptr(pred), _ptr(filt_off),
                   _ptr(filt), _ptr(out_x), _ptr(out_s), _ptr(out_r))
-        if topk == 0 and probes is None and not trace and marks is None and margins is None:
+        if topk == 0 and probes is None and not trace and marks is None and margins is None and not attrib:
             check(lib().kp_posttrain_rank(self.h, C.byref(hp), C.byref(b)), self.h)
             return out_s, out_r, out_x
         # the optional requests, each marshalled once; the entry point is the first that takes
@@ -622,6 +636,7 @@ class Context:
             ret += ((m_s, m_r, m_x),)
         ref = lambda st: C.byref(st) if st is not None else None  # noqa: E731
         head = (self.h, C.byref(hp), C.byref(b), topk, _ptr(ids), _ptr(top))
+        mg = None
         if margins is not None:
             # the tolerance as given: the library checks its range
             mg = Margins(float(margins))
@@ -632,6 +647,15 @@ class Context:
             if mk is not None:
                 mg_m, mg.marks = _margin_arrays((n, mk.n))
             ret += ((mg_s, mg_p, mg_m),)
+        if attrib:
+            n_rows = int(row_off[-1]) if n > 0 else 0
+            a_fit = np.zeros(max(1, n_rows), np.float64)
+            a_reg = np.zeros(max(1, n_rows), np.float64)
+            a_delta = np.zeros(max(1, n), np.float64)
+            at = Attrib(_ptr(a_fit), _ptr(a_reg), _ptr(a_delta))
+            ret += ((a_fit[:n_rows], a_reg[:n_rows], a_delta[:n]),)
+            rc = lib().kp_posttrain_rank_attrib(*head, ref(pr), ref(tr), ref(mk), ref(mg), C.byref(at))
+        elif mg is not None:
             rc = lib().kp_posttrain_rank_margins(*head, ref(pr), ref(tr), ref(mk), C.byref(mg))
         elif mk is not None:
             rc = lib().kp_posttrain_rank_marks(*head, ref(pr), ref(tr), ref(mk))

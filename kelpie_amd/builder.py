@@ -65,6 +65,14 @@ from changing (``engine.margin_tol``), and each record gains ``"margins"``, alig
 competitors (the sufficient engine: ``"conversions"``, one such pair per conversion entity,
 with its label).  A base result cached without margins gives None for its figures and for the
 band.  Not offered with a pipelined builder.
+
+With ``attributions`` = True every post-training also splits its score change over its facts
+(``engine.attributions``; ComplEx and DistMult under Adagrad or SGD), and each record gains
+``"attributions"``, aligned with ``rule_to_relevance``: per rule
+``engine.compute_attributions``' report of it -- ``"base"`` / ``"post"`` with ``"score0"``,
+``"delta"`` and the slot's labelled facts with their ``"fit"`` and ``"reg"`` (the sufficient
+engine: ``"conversions"``, one such pair per conversion entity, with its label).  A base result
+cached without attributions gives None.  Not offered with a pipelined builder.
 """
 from __future__ import annotations
 
@@ -77,7 +85,8 @@ class StochasticBuilder:
     AUTO_MIN, AUTO_MAX = 4, 32
 
     def __init__(self, xsi, engine, summarization: str = None, max_explanation_length: int = 4, window=32,
-                 pipelined=False, top_k=0, side_effects=0, trace=False, draws=None, seed=None, margins=None):
+                 pipelined=False, top_k=0, side_effects=0, trace=False, draws=None, seed=None, margins=None,
+                 attributions=False):
         if summarization is not None:
             raise NotImplementedError("summarisation (simulation / bisimulation) is out of scope")
         # the source of the post-training draws (PostTrainingEngine.draws / .seed; None: as the
@@ -113,6 +122,12 @@ class StochasticBuilder:
             self.margins = engine.margin_tol
             if pipelined:
                 raise NotImplementedError("margins with a pipelined builder: batches with margins run one at a time")
+        self.attributions = bool(attributions)
+        if self.attributions:
+            if pipelined:
+                raise NotImplementedError("attributions with a pipelined builder: batches with attributions run "
+                                          "one at a time")
+            engine.attributions = True
         self._details = {}  # rule -> the engine's (post-trained, base) results of its evaluation
         self.stats = {"batches": 0, "evaluated": 0, "wasted": 0, "batch_s": 0.0, "schedule_s": 0.0, "pack_s": 0.0,
                       "lib_s": 0.0}
@@ -158,11 +173,13 @@ class StochasticBuilder:
             out["traces"] = [self._trace_of(self._details[rule]) for rule, _ in rule_to_rel]
         if self.margins is not None:
             out["margins"] = [self._margins_of(rel, self._details[rule]) for rule, rel in rule_to_rel]
+        if self.attributions:
+            out["attributions"] = [self._attributions_of(pred, rel, self._details[rule]) for rule, rel in rule_to_rel]
         return out
 
     def _keep_details(self, rules, n):
         """The engine's per-rule results of its last batch, for the first ``n`` of ``rules``."""
-        if self.top_k or self.side_effects or self.trace or self.margins is not None:
+        if self.top_k or self.side_effects or self.trace or self.margins is not None or self.attributions:
             for rule, det in zip(rules[:n], self.engine.last_results):
                 self._details[tuple(rule)] = det
 
@@ -188,6 +205,18 @@ class StochasticBuilder:
         out = self.engine._mg_rule(rel, det, self.margins)
         for c in out.get("conversions", ()):
             c["entity"] = self.dataset.id_to_entity[c["entity"]]
+        return out
+
+    def _attributions_of(self, pred, rel, det):
+        """engine.compute_attributions' report of one rule, entities and facts by their labels."""
+        out = self.engine._at_rule(pred, rel, det)
+        sides = [out] if "base" in out else out["conversions"]
+        for c in sides:
+            if "entity" in c:
+                c["entity"] = self.dataset.id_to_entity[c["entity"]]
+            for side in (c["base"], c["post"]):
+                for f in side["facts"] or ():
+                    f["triple"] = self.dataset.labels_triple(f["triple"])
         return out
 
     def _trace_of(self, det):

@@ -210,7 +210,7 @@ int kp_ctx_destroy(kp_ctx* c) {
 static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k = 0, int32_t* out_ids = nullptr,
                                float* out_scores = nullptr, const kp_probes* probes = nullptr,
                                const kp_trace* trace = nullptr, const kp_marks* marks = nullptr,
-                               const kp_margins* margins = nullptr) {
+                               const kp_margins* margins = nullptr, const kp_attrib* attrib = nullptr) {
   if (!c || !hp || !b) return KP_EINVAL;
   PostReq rq;
   rq.k = k;
@@ -220,6 +220,7 @@ static int posttrain_rank_call(kp_ctx* c, const kp_hp* hp, const kp_batch* b, in
   rq.trace = trace;
   rq.marks = marks;
   rq.margins = margins;
+  rq.attrib = attrib;
   // an armed context (kp_ctx_arm_keyed) generates the draws of a call that brings none of the
   // three buffers, and is disarmed by it; a failing call disarms whatever it brought
   const bool keyed = c->keyed_armed && !b->x0 && !b->rng_off && !b->rng;
@@ -280,6 +281,14 @@ int kp_posttrain_rank_margins(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int
                               float* out_scores, const kp_probes* probes, const kp_trace* trace,
                               const kp_marks* marks, const kp_margins* margins) {
   return posttrain_rank_call(c, hp, b, k, out_ids, out_scores, probes, trace, marks, margins);
+}
+
+// kp_posttrain_rank_margins with the attributions of every training row: the split of the slot's
+// score change over its rows (include/kelpie_hip.h, "Attributions"; ComplEx / DistMult)
+int kp_posttrain_rank_attrib(kp_ctx* c, const kp_hp* hp, const kp_batch* b, int32_t k, int32_t* out_ids,
+                             float* out_scores, const kp_probes* probes, const kp_trace* trace, const kp_marks* marks,
+                             const kp_margins* margins, const kp_attrib* attrib) {
+  return posttrain_rank_call(c, hp, b, k, out_ids, out_scores, probes, trace, marks, margins, attrib);
 }
 
 // kp_posttrain_rank in fp64 (include/kelpie_hip.h, "fp64"): the request carries the double

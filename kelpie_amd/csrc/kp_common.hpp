@@ -205,8 +205,13 @@ struct ComplexWs {
   // kp_posttrain_rank_marks: the mark rows [ns][marks][dp] and, per entry of acts, the mark
   // row its update also stores (-1: none)
   DevBuf marks, mark_row;
+  // kp_posttrain_rank_attrib: the row map's index lists (kp_cx_rowmap.hpp); the slots' score
+  // gradients c [ns][dp] (fp64); per slot the step's D_t and x_t, the initial rows and the N2
+  // norm (fp32: [3][ns][dp] + [ns]); the results fit | reg [rows] and delta [ns] (fp64)
+  DevBuf at_map, at_c, at_f, at_out;
   auto all() {
-    return kp_join(f32.all(), std::array{&score_q, &score_out, &tr_term, &tr_fe, &tr_fr, &marks, &mark_row},
+    return kp_join(f32.all(), std::array{&score_q, &score_out, &tr_term, &tr_fe, &tr_fr, &marks, &mark_row, &at_map,
+                                         &at_c, &at_f, &at_out},
                    f64.all());
   }
 };
@@ -440,6 +445,8 @@ struct PostReq {
   int n_marks() const { return marks ? marks->n : 0; }
   // kp_posttrain_rank_margins' request (nullptr: no margins)
   const kp_margins* margins = nullptr;
+  // kp_posttrain_rank_attrib's request (nullptr: no attributions)
+  const kp_attrib* attrib = nullptr;
   // kp_posttrain_rank_f64's request (nullptr: the fp32 / bf16x3 step): the double inputs,
   // hyper-parameters and outputs.  ComplEx / DistMult; the lists, the probes, the trace and
   // the marks are not offered with it yet (require_request)

@@ -37,6 +37,7 @@
 #include "kp_attn3.hpp"
 #include "kp_attn64.hpp"
 #include "kp_cx_plan.hpp"
+#include "kp_cx_rowmap.hpp"
 #include "kp_posttrain.hpp"
 
 namespace {
@@ -97,6 +98,15 @@ struct CxProd {  // ComplEx (complex.py:59-112)
     out[i] = dre * cc + dim_ * ee + cf * qre;
     out[i + w] = -dre * ee + dim_ * cc + cf * qim;
   }
+  // kp_posttrain_rank_attrib: J_r v = v o r and J_r^T v at one coordinate, (re, im) pairs
+  static __device__ __forceinline__ void fwd(const double* v, const double* rv, double* out) {
+    out[0] = v[0] * rv[0] - v[1] * rv[1];
+    out[1] = v[0] * rv[1] + v[1] * rv[0];
+  }
+  static __device__ __forceinline__ void bwd(const double* v, const double* rv, double* out) {
+    out[0] = v[0] * rv[0] + v[1] * rv[1];
+    out[1] = -v[0] * rv[1] + v[1] * rv[0];
+  }
   // the factor of one (re, im) pair: the complex modulus (complex.py:80-84)
   static __device__ __forceinline__ float mod(const float* xv) { return sqrtf(xv[0] * xv[0] + xv[1] * xv[1]); }
   static __device__ __forceinline__ double mod64(const float* xv) {
@@ -134,6 +144,9 @@ struct DmProd {  // DistMult (distmult.py:38-68): plain [d] rows, q = lhs * rel
     const double q = xv[0] * rv[0];
     out[i] = dv[0] * rv[0] + cf * q;
   }
+  // kp_posttrain_rank_attrib: J_r v = J_r^T v = r * v
+  static __device__ __forceinline__ void fwd(const double* v, const double* rv, double* out) { out[0] = v[0] * rv[0]; }
+  static __device__ __forceinline__ void bwd(const double* v, const double* rv, double* out) { out[0] = v[0] * rv[0]; }
   // the factor of one coordinate: |x_i| (distmult.py:66, sqrt(x_i^2))
   static __device__ __forceinline__ float mod(const float* xv) { return fabsf(xv[0]); }
   static __device__ __forceinline__ double mod64(const float* xv) { return fabs((double)xv[0]); }
@@ -466,16 +479,29 @@ struct CxMarkArgs<true> {
   float* rows;
 };
 
+// kp_posttrain_rank_attrib: per slot [slots][DP] the step's D_t (the diagonal the update applies
+// to the gradient: lr, or Adagrad's lr / (sqrt(s) + eps) in the update's fp32) and the row x_t
+// before it moves, and per slot the N2 norm the update used.  Without the flag the struct is
+// empty and kp_cx_update is what it was.
+template <bool ATTRIB>
+struct CxAttribArgs {};
+template <>
+struct CxAttribArgs<true> {
+  float *D, *xprev, *n2;
+};
+
 // Sum a slot's contributions, add the N3 term, apply the optimizer (torch op order).
 // (`half` is the policy's extent w, as in kp_cx_contrib)
 // MARKS: the thread that stores an updated element stores it to the slot's mark row as well
 // when the plan marks this (slot, step); a plain vector store, no launch of its own
-template <int DP, class Prod, bool MARKS = false>
+// ATTRIB: the thread also stores the element's D_t and its value before the update (plain
+// vector stores; kp_cx_attrib reads them after this kernel)
+template <int DP, class Prod, bool MARKS = false, bool ATTRIB = false>
 __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __restrict__ act,
                                                     const CxPlan* __restrict__ plans, int nq,
                                                     const float* __restrict__ contrib, float* __restrict__ X,
                                                     float* __restrict__ S1, float* __restrict__ S2, CxOpt opt,
-                                                    CxMarkArgs<MARKS> mk) {
+                                                    CxMarkArgs<MARKS> mk, CxAttribArgs<ATTRIB> at) {
   constexpr int G = Prod::G;
   const int tid = threadIdx.x;
   const int4 a4 = act[blockIdx.x];  // slot, plan, qoff, toff
@@ -569,6 +595,9 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
     __syncthreads();
     n2 = sqrtf((n2red[0] + n2red[1]) + (n2red[2] + n2red[3]));
   }
+  if constexpr (ATTRIB) {
+    if (tid == 0) at.n2[slot] = n2;
+  }
 #pragma unroll
   for (int u = 0; u < (DP / G + 255) / 256; ++u) {
     const int i = tid + 256 * u;
@@ -627,6 +656,7 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
         const float stdv = sqrtf(s1) + opt.eps;
         xd = xd + (-opt.lr * gd) / stdv;
         S1[o] = s1;
+        if constexpr (ATTRIB) at.D[o] = opt.lr / stdv;
       } else if (opt.kind == KP_OPT_ADAM) {
         float m1 = S1[o], v2 = S2[o];
         m1 = m1 + opt.one_minus_b1 * (gd - m1);
@@ -638,14 +668,195 @@ __global__ __launch_bounds__(256) void kp_cx_update(int half, const int4* __rest
         S2[o] = v2;
       } else {
         xd = xd + (-opt.lr) * gd;
+        if constexpr (ATTRIB) at.D[o] = opt.lr;
       }
       x[d] = xd;
+      if constexpr (ATTRIB) at.xprev[o] = xv[h];
       if constexpr (MARKS) {
         const int mrow = mk.row[blockIdx.x];  // block-uniform
         if (mrow >= 0) mk.rows[(size_t)mrow * DP + d] = xd;
       }
     }
   }
+}
+
+// ----------------------------------------------------------------------------
+// kp_posttrain_rank_attrib (include/kelpie_hip.h, "Attributions").  The kernels below run only
+// in a call that asks for attributions.
+// ----------------------------------------------------------------------------
+__device__ __forceinline__ double at_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// the device side of the request: the row map (kp_cx_rowmap.hpp), the slots' score gradients,
+// what kp_cx_update<ATTRIB> leaves per slot, and the results
+struct CxAttribDev {
+  const int32_t *tg_row = nullptr, *qk_off = nullptr, *qk_row = nullptr, *t_off = nullptr, *t_row = nullptr;
+  double* c = nullptr;  // [ns][DP]
+  float *D = nullptr, *xprev = nullptr, *x0 = nullptr, *n2 = nullptr;
+  double *fit = nullptr, *reg = nullptr, *delta = nullptr;
+  int rows = 0;
+};
+
+// c_s = grad_x score(kelpie, p, o) = J_{R_p}^T E_o, once per slot before the loop: exact fp64
+// products of the fp32 operands, each sum rounded once; the padding is 0.  rank rows (s, p, o).
+template <int DP, class Prod>
+__global__ __launch_bounds__(64) void kp_cx_attrib_c(int half, const float* __restrict__ E,
+                                                     const float* __restrict__ R, const int32_t* __restrict__ pred,
+                                                     int ns, double* __restrict__ C) {
+  constexpr int G = Prod::G;
+  const int s = blockIdx.x;
+  if (s >= ns) return;
+  const float* rel = R + (size_t)pred[3 * s + 1] * DP;
+  const float* eo = E + (size_t)pred[3 * s + 2] * DP;
+  double* c = C + (size_t)s * DP;
+  for (int d = threadIdx.x; d < DP; d += 64) c[d] = 0.0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < half; i += 64) {
+    double ev[G], rv[G], out[G];
+#pragma unroll
+    for (int h = 0; h < G; ++h) ev[h] = eo[i + h * half], rv[h] = rel[i + h * half];
+    Prod::bwd(ev, rv, out);
+#pragma unroll
+    for (int h = 0; h < G; ++h) c[i + h * half] = out[h];
+  }
+}
+
+// One workgroup per active slot of the step, after kp_cx_update<ATTRIB> and while the step's
+// contribution rows are still in the workspace; its four waves take the slot's items (queries,
+// then frozen-head pairs) in turn.  With v = c o D_t, u = J_r v and the item's fp32 contribution
+// row g (kp_cx_contrib), all dots in fp64 (lane-strided, then a butterfly: a fixed order):
+//   query (c rows, ck of them with the kelpie as tail):  every row shares
+//       S = (<v, g> + sum_t <u, E_t> + ck kk) / c,   kk = <u, x> + <v, x o r>,
+//     a row with the frozen tail t gets S - <u, E_t>, one with the kelpie as tail S - kk, so the
+//     rows of a query sum to <v, g> whatever the rounding of the targets' sum was;
+//   frozen-head pair (c rows):  every row gets <v, g> / c.
+// fit[row] -= value / b; reg[row] -= occ <v, 3 w mod x> / b with the update's own moduli.  A row
+// belongs to one item of the step, the item to one wave, and a row's two additions are the same
+// lane's: one writer per row, no atomics.
+// Nothing of a row is held in registers across a loop: v, x_t and u are re-formed from memory
+// (they stay in cache) wherever a dot needs them, so a wave takes few registers and fits beside a
+// resident kp_attn3 wave (104 per lane are free, see kp_cx_contrib).
+template <int DP, class Prod>
+__global__ __launch_bounds__(256) void kp_cx_attrib(int half, const int4* __restrict__ act,
+                                                    const CxPlan* __restrict__ plans, const CxQuery* __restrict__ pq,
+                                                    const int32_t* __restrict__ targets, const int4* __restrict__ stept,
+                                                    int nq, const float* __restrict__ contrib,
+                                                    const float* __restrict__ E, const float* __restrict__ R,
+                                                    float reg_w, int reg_n2, CxAttribDev at) {
+  constexpr int G = Prod::G;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int4 a4 = act[blockIdx.x];  // slot, plan, qoff, toff
+  const CxPlan P = plans[a4.y];
+  const double* cs = at.c + (size_t)a4.x * DP;
+  const float* Ds = at.D + (size_t)a4.x * DP;
+  const float* xs = at.xprev + (size_t)a4.x * DP;
+  const double fb = (double)P.b;
+  const auto load_v = [&](int i, double* vv) {
+#pragma unroll
+    for (int h = 0; h < G; ++h) vv[h] = cs[i + h * half] * (double)Ds[i + h * half];
+  };
+  double regu = 0.0;  // <v, 3 w mod x>
+  if (reg_w != 0.f) {
+    const float n2 = reg_n2 ? at.n2[a4.x] : 0.f;
+    for (int i = lane; i < half; i += 64) {
+      double vv[G];
+      float xf[G];
+      load_v(i, vv);
+#pragma unroll
+      for (int h = 0; h < G; ++h) xf[h] = xs[i + h * half];
+      const double mod = reg_n2 ? (double)n2 : (double)Prod::mod(xf);
+#pragma unroll
+      for (int h = 0; h < G; ++h) regu += vv[h] * (3.0 * (double)reg_w * mod * (double)xf[h]);
+    }
+    regu = at_wave_sum(regu);
+  }
+  for (int j = w; j < P.q_count; j += 4) {
+    const int qi = P.q_begin + j;
+    const CxQuery Q = pq[qi];
+    const float* rel = R + (size_t)Q.rel * DP;
+    const float* g = contrib + (size_t)(a4.z + j) * DP;
+    double a = 0.0, kk = 0.0;
+    for (int i = lane; i < half; i += 64) {
+      double vv[G], rv[G], xv[G], uv[G], qv[G];
+      load_v(i, vv);
+#pragma unroll
+      for (int h = 0; h < G; ++h) rv[h] = (double)rel[i + h * half], xv[h] = (double)xs[i + h * half];
+      Prod::fwd(vv, rv, uv);
+      Prod::fwd(xv, rv, qv);
+#pragma unroll
+      for (int h = 0; h < G; ++h) {
+        a += vv[h] * (double)g[i + h * half];
+        kk += uv[h] * xv[h] + vv[h] * qv[h];
+      }
+    }
+    a = at_wave_sum(a);
+    kk = at_wave_sum(kk);
+    double tsum = 0.0;
+    for (int t = 0; t < Q.tg_count; ++t) {
+      const float* et = E + (size_t)targets[Q.tg_begin + t] * DP;
+      double dt = 0.0;
+      for (int i = lane; i < half; i += 64) {
+        double vv[G], rv[G], uv[G];
+        load_v(i, vv);
+#pragma unroll
+        for (int h = 0; h < G; ++h) rv[h] = (double)rel[i + h * half];
+        Prod::fwd(vv, rv, uv);
+#pragma unroll
+        for (int h = 0; h < G; ++h) dt += uv[h] * (double)et[i + h * half];
+      }
+      dt = at_wave_sum(dt);
+      tsum += dt;
+      if (lane == (t & 63)) at.fit[at.tg_row[Q.tg_begin + t]] += dt / fb;
+    }
+    const double S = (a + tsum + (double)Q.ck * kk) / (double)Q.c;
+    for (int t = lane; t < Q.tg_count; t += 64) {
+      const int row = at.tg_row[Q.tg_begin + t];
+      at.fit[row] -= S / fb;
+      at.reg[row] -= regu / fb;
+    }
+    const int k0 = at.qk_off[qi];
+    for (int t = lane; t < Q.ck; t += 64) {
+      const int row = at.qk_row[k0 + t];
+      at.fit[row] -= (S - kk) / fb;
+      at.reg[row] -= 2.0 * regu / fb;
+    }
+  }
+  for (int j = w; j < P.t_count; j += 4) {
+    const int cnt = stept[a4.w + j].z;
+    const float* g = contrib + (size_t)(nq + a4.w + j) * DP;
+    double a = 0.0;
+    for (int i = lane; i < half; i += 64) {
+      double vv[G];
+      load_v(i, vv);
+#pragma unroll
+      for (int h = 0; h < G; ++h) a += vv[h] * (double)g[i + h * half];
+    }
+    a = at_wave_sum(a);
+    const int t0 = at.t_off[P.t_begin + j];
+    for (int t = lane; t < cnt; t += 64) {
+      const int row = at.t_row[t0 + t];
+      at.fit[row] -= a / (double)cnt / fb;
+      at.reg[row] -= regu / fb;
+    }
+  }
+}
+
+// delta_s = <c_s, x_T - x_0> in fp64 from the fp32 rows: one wave per slot, lane-strided, then a
+// butterfly
+__global__ __launch_bounds__(256) void kp_cx_attrib_delta(int dp, int ns, const double* __restrict__ C,
+                                                          const float* __restrict__ X, const float* __restrict__ X0,
+                                                          double* __restrict__ delta) {
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= ns) return;
+  const size_t so = (size_t)s * dp;
+  double acc = 0.0;
+  for (int d = lane; d < dp; d += 64) acc += C[so + d] * ((double)X[so + d] - (double)X0[so + d]);
+  acc = at_wave_sum(acc);
+  if (lane == 0) delta[s] = acc;
 }
 
 // ============================================================================
@@ -951,7 +1162,8 @@ void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, c
                    const int4* stepq, int nq, const int4* stept, int nt, const float* tsum, const float* qpair,
                    const float* lsef, const float* am, const float* al, const float* aO, int n_split, float* contrib,
                    float* X, float* S1, float* S2, const CxOpt& opt, const CxTraceDev& tr = {}, int step = 0,
-                   const CxMarkArgs<true>* mk = nullptr) {
+                   const CxMarkArgs<true>* mk = nullptr, const CxAttribDev* at = nullptr,
+                   const int32_t* targets = nullptr) {
   if (n_act <= 0) return;
   const int half = Prod::extent(c->dim);
   KP_REQUIRE(n_split >= 1 && n_split <= 64, "cx contrib: one attention split per lane");
@@ -972,12 +1184,26 @@ void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, c
                        tr.off, step, tr.loss);
     KP_HIP(hipGetLastError());
   }
+  if (at) {  // kp_posttrain_rank_attrib: the ATTRIB forms, then the step's attributions from what they left
+    const CxAttribArgs<true> aa{at->D, at->xprev, at->n2};
+    if (mk)
+      hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod, true, true>), dim3(n_act), dim3(256), 0, c->stream, half, act,
+                         plans, nq, contrib, X, S1, S2, opt, *mk, aa);
+    else
+      hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod, false, true>), dim3(n_act), dim3(256), 0, c->stream, half, act,
+                         plans, nq, contrib, X, S1, S2, opt, CxMarkArgs<false>{}, aa);
+    KP_HIP(hipGetLastError());
+    hipLaunchKernelGGL((kp_cx_attrib<16 * DB, Prod>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, pq, targets,
+                       stept, nq, contrib, c->dE, c->dR, opt.reg_w, opt.reg_n2, *at);
+    KP_HIP(hipGetLastError());
+    return;
+  }
   if (mk)  // a step that ends a marked epoch of one of its slots: the MARKS form instead, not a further launch
     hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod, true>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq,
-                       contrib, X, S1, S2, opt, *mk);
+                       contrib, X, S1, S2, opt, *mk, CxAttribArgs<false>{});
   else
     hipLaunchKernelGGL((kp_cx_update<16 * DB, Prod>), dim3(n_act), dim3(256), 0, c->stream, half, act, plans, nq, contrib,
-                       X, S1, S2, opt, CxMarkArgs<false>{});
+                       X, S1, S2, opt, CxMarkArgs<false>{}, CxAttribArgs<false>{});
   KP_HIP(hipGetLastError());
 }
 
@@ -987,7 +1213,8 @@ void launch_update(kp_ctx* c, int n_act, const int4* act, const CxPlan* plans, c
                    const int4* stepq, int nq, const int4* stept, int nt, const double* tsum, const double* qpair,
                    const double* lsef, const double* am, const double* al, const double* aO, int ranges,
                    double* contrib, double* X, double* S1, double* S2, const CxOpt64& opt, const CxTraceDev& = {},
-                   int = 0, const CxMarkArgs<true>* = nullptr) {
+                   int = 0, const CxMarkArgs<true>* = nullptr, const CxAttribDev* = nullptr,
+                   const int32_t* = nullptr) {
   if (n_act <= 0) return;
   const int half = Prod::extent(c->dim);
   if (nq + nt > 0) {
@@ -1114,6 +1341,8 @@ struct CxDev {
   CxTraceDev trace;
   MarksDev marks;
   int32_t* mark_row = nullptr;  // [acts] the mark row an active entry's update also stores, or -1
+  CxAttribDev attrib;           // kp_posttrain_rank_attrib, when with_attrib
+  bool with_attrib = false;
   // the attention's: sized and planned by cx_preloop
   T *am = nullptr, *al = nullptr, *ao = nullptr, *qs = nullptr;
   std::conditional_t<is_f64<T>, CxAttn64, CxAttn32> attn;
@@ -1181,6 +1410,37 @@ CxDev<T> cx_workspaces(kp_ctx* c, const kp_hp* hp, const kp_batch* bt, const Pos
     const std::vector<int32_t> mr = marks_act_rows(d.marks, sp.act_off, sp.T, [&](int i) { return sp.acts[i].x; });
     d.mark_row = upload(c, c->cx.mark_row, mr.data(), mr.size());
   }
+  if constexpr (!is_f64<T>) {
+    if (rq.attrib) {  // the row map and the attributions' workspaces, with the call's other uploads
+      CxRowMap m;
+      if (const char* why = cx_row_map(c->n_ent, hp->batch_size, hp->epochs, bt, sp, m))
+        throw KpError{KP_EINVAL, std::string(kp_model_name(c->model)) + ": attributions: " + why};
+      // one upload: tg_row | qk_off | qk_row | t_off | t_row
+      std::vector<int32_t> pack;
+      const auto put = [&pack](const std::vector<int32_t>& v) {
+        const size_t at = pack.size();
+        pack.insert(pack.end(), v.begin(), v.end());
+        return at;
+      };
+      const size_t o0 = put(m.tg_row), o1 = put(m.qk_off), o2 = put(m.qk_row), o3 = put(m.t_off), o4 = put(m.t_row);
+      const int32_t* dm = upload(c, c->cx.at_map, pack.data(), pack.size());
+      CxAttribDev& a = d.attrib;
+      a.tg_row = dm + o0, a.qk_off = dm + o1, a.qk_row = dm + o2, a.t_off = dm + o3, a.t_row = dm + o4;
+      const size_t nx = (size_t)ns * DP;
+      a.rows = bt->row_off[ns];
+      a.c = ensure_n<double>(c->cx.at_c, nx);
+      a.D = ensure_n<float>(c->cx.at_f, 3 * nx + (size_t)ns);
+      a.xprev = a.D + nx;
+      a.x0 = a.xprev + nx;
+      a.n2 = a.x0 + nx;
+      a.fit = ensure_n<double>(c->cx.at_out, 2 * (size_t)a.rows + (size_t)ns);
+      a.reg = a.fit + a.rows;
+      a.delta = a.reg + a.rows;
+      KP_HIP(hipMemsetAsync(a.fit, 0, sizeof(double) * (2 * (size_t)a.rows + (size_t)ns), c->stream));
+      KP_HIP(hipMemcpyAsync(a.x0, d.X, sizeof(float) * nx, hipMemcpyDeviceToDevice, c->stream));
+      d.with_attrib = true;
+    }
+  }
   if (rq.trace) {  // the trace's offsets and workspaces, with the call's other uploads
     CxTraceDev& t = d.trace;
     static_cast<TraceDev&>(t) = upload_trace(c, bt, rq);
@@ -1213,6 +1473,14 @@ void cx_preloop(kp_ctx* c, const CxStepPlan& sp, CxDev<T>& d, const CxOptT<T>& o
     hipLaunchKernelGGL(kp_cx_rowreg<Prod>, dim3((c->n_rel2 + 3) / 4), dim3(256), 0, c->stream, c->dR, c->n_rel2, DP,
                        half, opt.reg_n2, d.trace.freg_r);
     KP_HIP(hipGetLastError());
+  }
+  if constexpr (!is_f64<T>) {
+    if (d.with_attrib) {  // the slots' score gradients, once per batch (the slots' rank rows are (s, p, o))
+      const int ns = d.rk.n;
+      CX_DISPATCH(DBV, hipLaunchKernelGGL((kp_cx_attrib_c<16 * DB, Prod>), dim3(ns), dim3(64), 0, c->stream,
+                                          Prod::extent(c->dim), c->dE, c->dR, d.rk.rows, ns, d.attrib.c));
+      KP_HIP(hipGetLastError());
+    }
   }
   c->attn_last = {};
   const size_t att_rows = d.attn.plan(c, sp, npairs);
@@ -1265,7 +1533,8 @@ int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxD
     CX_DISPATCH(DBV, launch_update<DB, Prod>(c, na, d.acts + sp.act_off[t], d.plans, d.pq, d.stepq + sp.q_off[t], nq,
                                              d.stept + sp.t_off[t], sp.t_off[t + 1] - sp.t_off[t], d.tsum, d.qpair,
                                              d.lsef, d.am, d.al, d.ao, d.attn.parts(t), d.contrib, d.X, d.S1, d.S2,
-                                             opt, d.trace, t, marks_at_step(d.marks, t) ? &mk : nullptr));
+                                             opt, d.trace, t, marks_at_step(d.marks, t) ? &mk : nullptr,
+                                             d.with_attrib ? &d.attrib : nullptr, d.tg));
     if (g_host_times) {
       if (t == 0) t_steps[0] = host_ms();
       if (t == 1) t_steps[1] = host_ms();
@@ -1281,6 +1550,18 @@ int64_t cx_step_loop(kp_ctx* c, const kp_hp* hp, const CxStepPlan& sp, const CxD
 // is set), its fp64 target values as out_score and its ranks, one wait, the rows' unpadding
 inline double cx_download(kp_ctx* c, const kp_batch* bt, const PostReq& rq, const CxDev<float>& d,
                           std::vector<float>& xp) {
+  if (d.with_attrib) {  // delta from the final rows, then the three results with the call's other downloads
+    const CxAttribDev& a = d.attrib;
+    const int ns = bt->n_slots;
+    hipLaunchKernelGGL(kp_cx_attrib_delta, dim3((ns + 3) / 4), dim3(256), 0, c->stream, c->dp, ns, a.c, d.X, a.x0,
+                       a.delta);
+    KP_HIP(hipGetLastError());
+    if (a.rows > 0) {
+      KP_HIP(hipMemcpyAsync(rq.attrib->out_fit, a.fit, sizeof(double) * a.rows, hipMemcpyDeviceToHost, c->stream));
+      KP_HIP(hipMemcpyAsync(rq.attrib->out_reg, a.reg, sizeof(double) * a.rows, hipMemcpyDeviceToHost, c->stream));
+    }
+    KP_HIP(hipMemcpyAsync(rq.attrib->out_delta, a.delta, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
+  }
   return download_results(c, bt, d.X, d.rk, xp, rq, d.probes, d.trace, d.marks);
 }
 inline double cx_download(kp_ctx* c, const kp_batch* bt, const PostReq& rq, const CxDev<double>& d,

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "kp_attrib_check.hpp"
 #include "kp_batch_check.hpp"
 #include "kp_common.hpp"
 #include "kp_keyed.hpp"
@@ -35,7 +36,7 @@ inline double host_ms() {
 // leaves no device work in flight; the first rule broken is the one reported, as KP_EINVAL
 // under the model's name: the batch (kp_batch_check.hpp), the top-k request, the probes
 // (kp_probe_check.hpp), the trace (kp_trace_check.hpp), the marks (kp_marks_check.hpp), the
-// margins (kp_margins_check.hpp).
+// margins (kp_margins_check.hpp), the attributions (kp_attrib_check.hpp).
 // `rank64`: the call ranks on launch_rank_f64's fp64 operands; the lists, the probes and the
 // marks need them (KP_ENOTSUP under the fp32 diagnostic ranks, KP_TE_RANK / KP_CV_RANK = f32,
 // once well formed), the trace does not depend on the rank.
@@ -89,6 +90,11 @@ inline void require_request(const kp_ctx* c, const kp_hp* hp, const kp_batch* bt
     int code = KP_EINVAL;
     if (const char* why = kp_check_margins(rq.margins, rq.n_probes(), rq.n_marks(), rank64, &code))
       throw KpError{code, who + ": margins: " + why};
+  }
+  if (rq.attrib) {
+    int code = KP_EINVAL;
+    if (const char* why = kp_check_attrib(c->model, hp, c->n_ent, bt->n_slots, bt->row_off, bt->pred, rq.attrib, &code))
+      throw KpError{code, who + ": attributions: " + why};
   }
 }
 

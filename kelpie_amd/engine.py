@@ -430,6 +430,55 @@ class PostTrainingEngine(RelevanceEngine):
         if self._sharded():
             raise NotImplementedError("margins with a slot sharding: their results are not gathered across ranks")
 
+    _attrib = False  # whether every post-training also reports its attributions
+
+    @property
+    def attributions(self):
+        """Whether every post-training also splits its score change over its facts (False: the
+        default; include/kelpie_hip.h, "Attributions").  ComplEx and DistMult score the target
+        linearly in the kelpie row and Adagrad / SGD apply a diagonal to a sum of per-row
+        gradients, so ``score - score0`` splits exactly into one number per training row plus the
+        regulariser's share.  Every slot's result gains ``"attrib"``: ``{"facts", "fit", "reg",
+        "delta"}`` -- the slot's facts in kelpie form (rows ``f`` and ``f + F``, a fact and its
+        inverse, fold to fact ``f``), what fitting each fact contributed, the regulariser's share
+        booked to it, and ``delta = <c, x_T - x_0>``; ``sum(fit) + sum(reg) = delta`` up to the
+        float32 rounding of the updates.  The relevances, the draws and the batches are those of
+        ``attributions`` = False.  Not offered for TransE and ConvE, with an Adam
+        ``optimizer_name``, ``precision="fp64"``, a slot sharding, ``compute_relevance_pipeline``,
+        ``submit_batch`` or a prediction ``<s, p, s>`` (NotImplementedError before any draw)."""
+        return self._attrib
+
+    @attributions.setter
+    def attributions(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise TypeError(f"attributions must be a bool, got {on!r}")
+        self._attrib = bool(on)
+
+    def _refuse_attrib(self, what=None, items=()):
+        """The attributions' refusals, before any work.  ``items``: the batch's (pred, rules[,
+        entities to convert])."""
+        if not self._attrib:
+            return
+        if what is not None:
+            raise NotImplementedError(f"attributions on {what}: batches with attributions run one at a time")
+        if self.model.name not in ("ComplEx", "DistMult"):
+            raise NotImplementedError(f"attributions: {self.model.name}'s score is not linear in the kelpie row "
+                                      "(ComplEx and DistMult only)")
+        if int(self._kp_hp.optimizer) == _lib.KP_OPT["Adam"]:
+            raise NotImplementedError("attributions with optimizer_name='Adam': its momentum would need one vector "
+                                      "per training row (Adagrad and SGD only)")
+        if self._fp64():
+            raise NotImplementedError("attributions with precision='fp64': kp_posttrain_rank_f64 does not offer them")
+        if self._sharded():
+            raise NotImplementedError("attributions with a slot sharding: their results are not gathered across "
+                                      "ranks")
+        for item in items:
+            pred = tuple(int(v) for v in item[0])
+            heads = [pred[0]] if len(item) < 3 else [int(e) for e in item[2]]
+            if pred[2] in heads:
+                raise NotImplementedError(f"attributions of a prediction <s, p, s> ({(pred[2], pred[1], pred[2])}): "
+                                          "its score is quadratic in the kelpie row")
+
     @property
     def top_k(self):
         """How many of each post-training's best tails the device also reports (0: none, the
@@ -767,6 +816,7 @@ class PostTrainingEngine(RelevanceEngine):
         """_schedule_multi, with every queued TransE call's draws made before it returns or raises."""
         self._refuse_keyed()  # before any work
         self._refuse_margins()  # before any draw
+        self._refuse_attrib(items=items)  # before any draw
         self._refuse_fp64()  # before any draw
         if self._top_k and self._sharded():
             # before any draw: the gather's records hold a score and a rank per slot
@@ -989,6 +1039,8 @@ class PostTrainingEngine(RelevanceEngine):
         tol = self._margin_tol
         if tol is not None:
             kw["margins"] = tol
+        if self._attrib:
+            kw["attrib"] = True
         if slots[0].keys is not None:  # keyed draws: the context generates x0 and the words from the keys
             scale, bound = self.model.keyed_params()
             ctx.arm_keyed([s.keys[0] for s in slots], [s.keys[1] for s in slots], scale, bound)
@@ -1010,6 +1062,16 @@ class PostTrainingEngine(RelevanceEngine):
                 mg = out.margins[0]
                 for i, s in enumerate(slots):
                     s.result["margins"] = {"tol": tol, **{name: mg[name][i].item() for name, _ in _lib.MARGIN_FIELDS}}
+            if self._attrib:
+                a_fit, a_reg, a_delta = out.attrib
+                row_off = packed[1]
+                for i, s in enumerate(slots):
+                    a, z = int(row_off[i]), int(row_off[i + 1])
+                    F = (z - a) // 2  # rows f and f + F are fact f and its inverse
+                    s.result["attrib"] = {
+                        "facts": [tuple(int(v) for v in t) for t in np.asarray(s.rows).reshape(-1, 3)[:F]],
+                        "fit": (a_fit[a:a + F] + a_fit[a + F:z]).tolist(),
+                        "reg": (a_reg[a:a + F] + a_reg[a + F:z]).tolist(), "delta": float(a_delta[i])}
             if traced:
                 for s, loss in zip(slots, out.loss):
                     s.result["loss"] = [float(v) for v in loss]
@@ -1258,6 +1320,44 @@ class PostTrainingEngine(RelevanceEngine):
             self._margin_tol = old
         return [self._mg_rule(rel, det, tol) for rel, det in zip(rels, self.last_results)]
 
+    def _at_side(self, res, entity):
+        """One post-training of an attributions report: its target score and rank, and (None each
+        when the result was cached without attributions) ``delta``, ``score0`` = score - delta
+        and its facts ``[{"triple", "fit", "reg"}]`` in the slot's order, the kelpie entity
+        written as ``entity``, the entity it clones."""
+        at = res.get("attrib")
+        side = {"score": res["target_score"], "rank": res["target_rank"], "delta": None, "score0": None, "facts": None}
+        if at is not None:
+            K = self.dataset.num_entities
+            side["delta"] = at["delta"]
+            side["score0"] = float(res["target_score"]) - at["delta"]
+            side["facts"] = [{"triple": tuple(int(entity) if v == K and k != 1 else v for k, v in enumerate(t)),
+                              "fit": f, "reg": r} for t, f, r in zip(at["facts"], at["fit"], at["reg"])]
+        return side
+
+    def _at_rule(self, pred, relevance, detail):
+        raise NotImplementedError
+
+    def compute_attributions(self, pred, rules):
+        """``compute_relevance_batch(pred, rules)`` -- the same schedule, draws, batches and
+        relevances, the generators left where it leaves them -- that also reports which of each
+        post-training's facts wrote its score (:attr:`attributions`): per rule ``{"relevance",
+        "base", "post"}`` (the sufficient engine: ``{"relevance", "conversions": [{"entity",
+        "base", "post"}, ...]}``), ``base`` / ``post`` = ``{"score", "rank", "score0", "delta",
+        "facts": [{"triple", "fit", "reg"}, ...]}``: the slot's facts (the subject's, or the
+        conversion entity's, after the rule's edit) in original ids, what fitting each one added
+        to the target score over the post-training, the regulariser's share booked to it, and
+        ``score0 + delta == score``.  No post-training runs for the sake of an attribution: a
+        base result cached without them reports None.  NotImplementedError for a combination not
+        offered, before any draw."""
+        old = self._attrib
+        self._attrib = True
+        try:
+            rels = self.compute_relevance_batch(pred, rules)
+        finally:
+            self._attrib = old
+        return [self._at_rule(pred, rel, det) for rel, det in zip(rels, self.last_results)]
+
     def _schedule_multi(self, items, checkpoints):
         raise NotImplementedError
 
@@ -1298,6 +1398,7 @@ class PostTrainingEngine(RelevanceEngine):
         from . import rng as _rng_mod
         self._refuse_keyed("submit_batch")
         self._refuse_margins("submit_batch")
+        self._refuse_attrib("submit_batch")
         ctxs = self.model.contexts(2)
         self._submit_n = getattr(self, "_submit_n", -1) + 1
         ctx = ctxs[self._submit_n % len(ctxs)]
@@ -1414,6 +1515,7 @@ class PostTrainingEngine(RelevanceEngine):
 
         self._refuse_keyed("compute_relevance_pipeline")
         self._refuse_margins("compute_relevance_pipeline")
+        self._refuse_attrib("compute_relevance_pipeline")
         if self._fp64():  # before any draw
             raise NotImplementedError("precision='fp64' on compute_relevance_pipeline: the fp64 path runs one "
                                       "batch at a time")
@@ -1721,6 +1823,64 @@ class NecessaryPostTrainingEngine(PostTrainingEngine):
         pt, base = detail
         return {"relevance": relevance, "base": self._tr_side(base), "post": self._tr_side(pt)}
 
+    def _at_rule(self, pred, relevance, detail):
+        pt, base = detail
+        s = int(pred[0])
+        return {"relevance": relevance, "base": self._at_side(base, s), "post": self._at_side(pt, s)}
+
+    def rank_facts(self, pred, k=None):
+        """The subject's facts by what fitting them contributed to ``pred``'s score in its base
+        post-training (:attr:`attributions`), largest first: ``[{"triple", "fit", "reg"}, ...]``,
+        the first ``k`` (None: all).  A model-aware ordering of the candidates beside the
+        topological prefilters', from the one post-training every explanation of ``pred`` runs
+        anyway.  The base slot runs alone.  With reference draws it takes its draws as a base
+        post-training does and puts the generators back where they were: like
+        ``compute_relevance_batch(pred, [])`` the call leaves them unchanged, so the result
+        depends on their state but later calls do not depend on this one.  With keyed draws it
+        asks the generators for nothing and is the base of every keyed relevance of ``pred``.  A
+        cached base result with attributions is reused; the result of this call is not cached.
+        NotImplementedError for a combination not offered, before any draw."""
+        if k is not None and (isinstance(k, bool) or int(k) != k or int(k) < 0):
+            raise ValueError(f"k must be a non-negative integer or None, got {k!r}")
+        pred = tuple(int(v) for v in pred)
+        old = self._attrib
+        self._attrib = True
+        try:
+            self._refuse_keyed()
+            self._refuse_margins()
+            self._refuse_attrib(items=[(pred, [])])
+            self._refuse_fp64()
+            res = self.base_pt_results.get(pred)
+            if res is None or res.get("attrib") is None:
+                res = self._base_alone(pred)
+        finally:
+            self._attrib = old
+        facts = self._at_side(res, pred[0])["facts"]
+        order = sorted(range(len(facts)), key=lambda i: (-facts[i]["fit"], i))
+        return [facts[i] for i in (order if k is None else order[:int(k)])]
+
+    def _base_alone(self, pred):
+        """The base post-training of ``pred`` in a batch of its own; the torch / numpy generators
+        end where they began."""
+        view = self._get_kelpie_dataset(pred[0])
+        kp = tuple(int(v) for v in view.as_kelpie_triple(pred))
+        filt = list(view.filter_for(kp[1]))
+        if self._keyed():
+            slot = _Slot(x0=None, rows=view.base_rows, rng=None, pred=kp, filt=filt,
+                         keys=(_keyed.init_key(self._seed, pred),
+                               _keyed.slot_key(self._seed, pred, _keyed.ROLE_BASE, "necessary")))
+            self._run([slot])
+            return slot.result
+        before = StateCheckpoint()
+        try:
+            with self.rng.deferred():
+                init = self.rng.rand_init(self.model.dimension)
+                slot = self._slot(self.model.kelpie_init(init, self.rng), view.base_rows, kp, filt)
+            self._run([slot])
+        finally:
+            before.restore()
+        return slot.result
+
     def _rel_of(self, base, pt):
         # _finalize_multi's formula, in its scalar form (the same bits)
         if self.model.is_minimizer():
@@ -1766,6 +1926,11 @@ class SufficientPostTrainingEngine(PostTrainingEngine):
     def _tr_rule(self, relevance, detail):
         return {"relevance": relevance,
                 "conversions": [{"entity": int(e), "base": self._tr_side(base), "post": self._tr_side(pt)}
+                                for e, (pt, base) in zip(self.entities_to_convert, detail)]}
+
+    def _at_rule(self, pred, relevance, detail):
+        return {"relevance": relevance,
+                "conversions": [{"entity": int(e), "base": self._at_side(base, e), "post": self._at_side(pt, e)}
                                 for e, (pt, base) in zip(self.entities_to_convert, detail)]}
 
     def _rel_of(self, base, pt):

@@ -15,7 +15,8 @@ Mirrors the reference's callers of the relevance engine:
   does to the subject's other held-out facts.  With ``trace`` every record also holds
   ``"traces"``: the optimizer's per-step loss of each rule's post-trainings.  With
   ``margins`` = a tolerance every record also holds ``"margins"``: how far each rule's ranks
-  are from changing, and the band of its relevance.
+  are from changing, and the band of its relevance.  With ``attributions`` every record also
+  holds ``"attributions"``: which of each post-training's facts wrote its score.
 
 The DP / CRIAGE baselines and summarisation are out of scope.
 """
@@ -64,10 +65,12 @@ class SufficientPipeline(Pipeline):
 
 def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="auto", entity_classes=None,
                    pipelined=False, top_k=0, side_effects=0, trace=False, draws="reference", seed=0,
-                   margins=None):
+                   margins=None, attributions=False):
     """explain.py:49-89 for the post-training engines (baseline=None, no summarisation).
     ``draws`` / ``seed``: the source of the post-training draws (PostTrainingEngine.draws).
-    ``margins``: the tolerance of the rank margins (PostTrainingEngine.margin_tol; None: none)."""
+    ``margins``: the tolerance of the rank margins (PostTrainingEngine.margin_tol; None: none).
+    ``attributions``: every post-training's score change split over its facts
+    (PostTrainingEngine.attributions)."""
     if prefilter == TYPE_PREFILTER:
         raise NotImplementedError("type_based prefilter: out of scope (kelpie_amd/prefilters.py)")
     cls = PREFILTERS.get(prefilter, TopologyPreFilter) if prefilter else PREFILTERS[TOPOLOGY_PREFILTER]
@@ -77,13 +80,15 @@ def build_pipeline(model, dataset, hp, mode, prefilter=None, xsi=None, window="a
         engine = NecessaryPostTrainingEngine(model, dataset, hp)
         return NecessaryPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
                                                                   top_k=top_k, side_effects=side_effects,
-                                                                  trace=trace, draws=draws, seed=seed, margins=margins))
+                                                                  trace=trace, draws=draws, seed=seed, margins=margins,
+                                                                  attributions=attributions))
     if mode == "sufficient":
         xsi = 0.9 if xsi is None else xsi
         engine = SufficientPostTrainingEngine(model, dataset, hp)
         return SufficientPipeline(dataset, pf, StochasticBuilder(xsi, engine, window=window, pipelined=pipelined,
                                                                   top_k=top_k, side_effects=side_effects,
-                                                                  trace=trace, draws=draws, seed=seed, margins=margins))
+                                                                  trace=trace, draws=draws, seed=seed, margins=margins,
+                                                                  attributions=attributions))
     raise ValueError(f"unknown mode {mode!r}")
 
 
@@ -157,7 +162,7 @@ def reference_construction_draws(model_name, num_entities, num_relations, model_
 
 def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefilter=None, prefilter_k=20,
                 xsi=None, skip=-1, output_path=None, device=0, top_k=0, side_effects=0, trace=False,
-                margins=None):
+                margins=None, attributions=False):
     """explain.py main() (explain.py:143-203) without the CLI: seeds 42 (explain.py:144),
     the reference model construction's random draws (:171-172), the checkpoint state dict
     (``torch.load(path, weights_only=True)``, :174) as a frozen model on the MI355X, the
@@ -174,5 +179,5 @@ def run_explain(model_name, dataset, state, model_params, hp, mode, preds, prefi
     reference_construction_draws(model_name, dataset.num_entities, dataset.num_relations, model_params)
     model = from_state_dict(model_name, dataset, state, model_params, device=device)
     pipe = build_pipeline(model, dataset, hp, mode, prefilter=prefilter, xsi=xsi, top_k=top_k,
-                          side_effects=side_effects, trace=trace, margins=margins)
+                          side_effects=side_effects, trace=trace, margins=margins, attributions=attributions)
     return explain_preds(pipe, dataset, preds, prefilter_k=prefilter_k, skip=skip, output_path=output_path)
